@@ -19,6 +19,11 @@ the compressor's first pass (include/choco_codec.h), compress of d = x_new - x_h
 exchange, accumulate; `--unfused` runs the consensus step as its own pass first, as the
 reference does (optim/utils.py:67-72), for the A/B.
 
+A plain run sets up, warms up, times --steps steps and prints the headline line
+(metric, value, ms_per_step, config); `--dump-outputs DIR` adds the last timed step's
+outputs as .npy files (inputs are seeded: the same arguments give the same arrays).
+Everything below except the metric is measured with `--full` only, after the timed steps.
+
 metric (BASELINE.json): compress+decompress GB/s = sum_r 4*n_r / max_r(step time).
 roofline: per STAGE of the step (compress, decompress), algorithmic bytes
 (SURVEY.md 8(d)) / the stage's kernel time from dispatch-attached HIP events;
@@ -109,8 +114,15 @@ def parse(argv=None):
     p.add_argument("--defer-receive", action="store_true",
                    help="step_* workloads: apply each step's received messages inside the NEXT step's first pass "
                         "(receive + consensus step + first compress pass in one kernel; same x / x_hat / memory)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-e2e", action="store_true", help="skip the host-resident (PCIe-inclusive) leg")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline figure, also measure everything else: per-kernel events (the dominant "
+                        "kernel's inside the timed steps), stages and roofline, exchange time, warm / cold start of "
+                        "the top-k, the host-resident leg and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one left (the packed message, x_hat, memory, and x "
+                        "for step_* workloads) as DIR/<name>.npy, 64 MB at most in all")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    p.add_argument("--no-e2e", action="store_true", help="--full: skip the host-resident (PCIe-inclusive) leg")
     p.add_argument("--lib", default=None, help=argparse.SUPPRESS)
     p.add_argument("--no-kernel-events", action="store_true", help=argparse.SUPPRESS)  # diagnostic
     p.add_argument("--dist-timeout", type=float, default=300.0,
@@ -632,6 +644,40 @@ def e2e_rate(w, reps=5):
                     f"{reps}"}
 
 
+DUMP_BYTES = 60_000_000  # --dump-outputs: all arrays together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(w, outdir, rank, world):
+    """--dump-outputs: what the last timed step left for its caller: the packed message it sent,
+    x_hat and memory after its accumulate, and x for the step_* workloads.  Float tensors are
+    written as float32; indices and packed words as float64 (exact).  An array over its share
+    of DUMP_BYTES is cut to a fixed sample: seeded positions in ascending order, the same for
+    every run with the same arguments.  Ranks of a multi-GPU run write <name>.rank<r>.npy and
+    divide DUMP_BYTES among them."""
+    import numpy as np
+    torch = w.torch
+    if w.op in ("topk", "topk_seg", "randk", "randk_seg"):
+        arrays = {"msg_values": w.msg[:w.k].view(torch.float32), "msg_indices": w.msg[w.k:]}
+    else:
+        payload, norms = w._parts(w.msg)
+        arrays = {"msg_payload": payload, "msg_norms": norms}
+    arrays["x_hat"], arrays["memory"] = w.hat, w.mem
+    if w.step_mode:
+        arrays["x"] = w.x
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BYTES // (len(arrays) * world)
+    suffix = f".rank{rank}" if world > 1 else ""
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        dt = torch.float32 if t.is_floating_point() else torch.float64
+        cap = share // (4 if dt == torch.float32 else 8)
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(64)  # x, x_hat and memory: the same positions
+            pos = torch.randint(t.numel(), (cap,), generator=g).sort().values
+            t = t[pos.to(t.device)]
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), t.to(dt).cpu().numpy())
+
+
 def cpu_model():
     try:
         with open("/proc/cpuinfo") as f:
@@ -796,79 +842,86 @@ def main():
     burn = args.burn_in if args.burn_in is not None else (200 if (w.step_mode and w.grads is not None) else 0)
     for _ in range(burn):  # untimed: the steady state of a training run (step_* workloads)
         w.step()
-    # warm-up; its last steps time every kernel to find the dominant stage
-    codec.profile_reset()
-    for i in range(args.warmup):
-        codec.profile_enable(i >= args.warmup // 2)
-        w.step()
-    barrier()
-    codec.profile_enable(False)
-    nw = args.warmup - args.warmup // 2
-    pre = stage_times(max(nw, 1))
-    t_comp = sum(pre[k][0] for k in comp_k if k in pre)
-    t_dec = sum(pre[k][0] for k in dec_k if k in pre)
-    dom_name, dom_k = ("decompress", dec_k) if t_dec > t_comp else ("compress", comp_k)
+    if args.full:
+        # warm-up; its last steps time every kernel to find the dominant stage
+        codec.profile_reset()
+        for i in range(args.warmup):
+            codec.profile_enable(i >= args.warmup // 2)
+            w.step()
+        barrier()
+        codec.profile_enable(False)
+        nw = args.warmup - args.warmup // 2
+        pre = stage_times(max(nw, 1))
+        t_comp = sum(pre[k][0] for k in comp_k if k in pre)
+        t_dec = sum(pre[k][0] for k in dec_k if k in pre)
+        dom_name, dom_k = ("decompress", dec_k) if t_dec > t_comp else ("compress", comp_k)
 
-    # timed region: only the dominant stage's longest kernel carries events (a
-    # dispatch-attached event pair costs ~4 us of GPU time: three pairs on the top-k
-    # compress made the step 176 -> 189 us, tools/host_overhead.py); the stage's other
-    # kernels are timed in the untimed pass below
-    dom_kernel = max((k for k in dom_k if k in pre), key=lambda k: pre[k][0], default=None)
-    codec.profile_reset()
-    codec.profile_filter([dom_kernel] if dom_kernel else dom_k)
-    warm0 = w.warm_counters()  # (synchronises: before the timed region)
-    codec.profile_enable(not args.no_kernel_events)
+        # timed region: only the dominant stage's longest kernel carries events (a
+        # dispatch-attached event pair costs ~4 us of GPU time: three pairs on the top-k
+        # compress made the step 176 -> 189 us, tools/host_overhead.py); the stage's other
+        # kernels are timed in the untimed pass below
+        dom_kernel = max((k for k in dom_k if k in pre), key=lambda k: pre[k][0], default=None)
+        codec.profile_reset()
+        codec.profile_filter([dom_kernel] if dom_kernel else dom_k)
+        warm0 = w.warm_counters()  # (synchronises: before the timed region)
+        codec.profile_enable(not args.no_kernel_events)
+    else:  # a plain run: the headline figure alone, no kernel carries events
+        for _ in range(args.warmup):
+            w.step()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         w.step()
     barrier()
     elapsed = time.perf_counter() - t0
-    codec.profile_enable(False)
-    timed = stage_times(args.steps)
-    # calls that took the exact fallback so far (top-k: the flat workspace's counter)
-    fallbacks = codec.topk_fallback_count() if w.op == "topk" else None
-    warm_start = w.warm_rates(warm0, args.steps)
+    if args.dump_outputs:  # the last timed step's outputs, before --full's passes run further steps
+        dump_outputs(w, args.dump_outputs, rank, world)
+    if args.full:
+        codec.profile_enable(False)
+        timed = stage_times(args.steps)
+        # calls that took the exact fallback so far (top-k: the flat workspace's counter)
+        fallbacks = codec.topk_fallback_count() if w.op == "topk" else None
+        warm_start = w.warm_rates(warm0, args.steps)
 
-    # untimed pass: every kernel, plus the exchange on its own events
-    codec.profile_reset()
-    codec.profile_filter(None)
-    codec.profile_enable(True)
-    npass = min(args.steps, 10)
-    ex_ms = []
-    if w.grads is not None:
-        w.grad_events = []
-    for _ in range(npass):
-        w.compress()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        w.exchange()
-        e1.record()
-        w.decompress()
-        ex_ms.append((e0, e1))
-    barrier()
-    codec.profile_enable(False)
-    untimed = stage_times(npass)
-    exchange_us = statistics.median(a.elapsed_time(b) * 1e3 for a, b in ex_ms) if w.peers else 0.0
-    grad_us = None
-    if w.grad_events:
-        grad_us = statistics.median(a.elapsed_time(b) * 1e3 for a, b in w.grad_events)
-        w.grad_events = None
-    # top-k: the same compress with the warm start off (every call samples its window
-    # in K1 / reads twice in the segmented path), beside the warm numbers above
-    cold = None
-    if w.op in ("topk", "topk_seg"):
-        lib = codec.lib()
-        lib.choco_topk_set_warm_start(0)
+        # untimed pass: every kernel, plus the exchange on its own events
         codec.profile_reset()
+        codec.profile_filter(None)
         codec.profile_enable(True)
+        npass = min(args.steps, 10)
+        ex_ms = []
+        if w.grads is not None:
+            w.grad_events = []
         for _ in range(npass):
             w.compress()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            w.exchange()
+            e1.record()
+            w.decompress()
+            ex_ms.append((e0, e1))
         barrier()
         codec.profile_enable(False)
-        lib.choco_topk_set_warm_start(1)
-        cold = stage_times(npass)
-    granule = w.granule_bytes_decompress()
+        untimed = stage_times(npass)
+        exchange_us = statistics.median(a.elapsed_time(b) * 1e3 for a, b in ex_ms) if w.peers else 0.0
+        grad_us = None
+        if w.grad_events:
+            grad_us = statistics.median(a.elapsed_time(b) * 1e3 for a, b in w.grad_events)
+            w.grad_events = None
+        # top-k: the same compress with the warm start off (every call samples its window
+        # in K1 / reads twice in the segmented path), beside the warm numbers above
+        cold = None
+        if w.op in ("topk", "topk_seg"):
+            lib = codec.lib()
+            lib.choco_topk_set_warm_start(0)
+            codec.profile_reset()
+            codec.profile_enable(True)
+            for _ in range(npass):
+                w.compress()
+            barrier()
+            codec.profile_enable(False)
+            lib.choco_topk_set_warm_start(1)
+            cold = stage_times(npass)
+        granule = w.granule_bytes_decompress()
 
     t_max = elapsed
     if world > 1:
@@ -878,6 +931,18 @@ def main():
     ms_per_step = t_max / args.steps * 1e3
     value = world * 4 * w.n * args.steps / t_max / 1e9
     if rank == 0:
+        out = {
+            "metric": METRIC, "value": round(value, 2), "unit": "GB/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": w.label + ("_fold" if w.fold else ""), "n_per_worker": w.n, "k_per_worker": w.k,
+                       "graph": ("ring3_loopback" if w.loop_sets else "self") if world == 1 else (
+                           "complete" if world == 2 else "ring"),
+                       "messages_per_step": len(w.ranks), "backend": args.backend if world > 1 else None,
+                       "step": "compress+exchange+decompress-accumulate", "parallelism": f"gossip{world}"},
+            "burn_in_steps": burn, "full": args.full,
+        }
+    if rank == 0 and args.full:
         comp_b, dec_b, bytes_note = w.stage_bytes()
 
         def stage_entry(name, kernels, nbytes, src):
@@ -947,15 +1012,7 @@ def main():
                             fl["known_t_floor_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
                         "compress_vs_floor": round(fl["known_t_floor_us"] / dom["us_per_step"], 4),
                         "source": fl["source"]}
-        out = {
-            "metric": METRIC, "value": round(value, 2), "unit": "GB/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": w.label + ("_fold" if w.fold else ""), "n_per_worker": w.n, "k_per_worker": w.k,
-                       "graph": ("ring3_loopback" if w.loop_sets else "self") if world == 1 else (
-                           "complete" if world == 2 else "ring"),
-                       "messages_per_step": len(w.ranks), "backend": args.backend if world > 1 else None,
-                       "step": "compress+exchange+decompress-accumulate", "parallelism": f"gossip{world}"},
+        out.update({
             "roofline": roofline,
             "stages": stages,
             "stage_bytes_note": bytes_note,
@@ -963,7 +1020,6 @@ def main():
             "exchange_us": round(exchange_us, 1),
             "topk_fallbacks": fallbacks,
             "warm_start": warm_start,
-            "burn_in_steps": burn,
             "apply_gradient": None if grad_us is None else {
                 "us": round(grad_us, 1), "lr": args.grad_lr, "scale": args.grad_scale,
                 "note": "g ~ N(0, scale^2) drawn fresh each step, then x -= lr * g (optim/utils.py:13-47, no "
@@ -972,11 +1028,12 @@ def main():
             "cold_start": cold_entry,
             "e2e": None,
             "cpu_baseline": None,
-        }
+        })
         if world == 1 and not args.no_e2e and not w.step_mode:
             out["e2e"] = e2e_rate(w)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(w)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
