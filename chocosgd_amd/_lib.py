@@ -25,6 +25,7 @@ _c_sz, _vp = ctypes.c_size_t, ctypes.c_void_p
 _pp = ctypes.POINTER(ctypes.c_void_p)
 _p_i64 = ctypes.POINTER(ctypes.c_int64)
 _p_f32 = ctypes.POINTER(ctypes.c_float)
+_p_i32 = ctypes.POINTER(ctypes.c_int32)
 
 # name -> (restype, argtypes); mirrors include/choco_codec.h one to one
 SIGNATURES = {
@@ -84,6 +85,9 @@ SIGNATURES = {
     "choco_qsgd_decompress_accumulate_range": (_c_i32, [_pp, _pp, _p_f32, _c_i32, _c_i32, _c_i64, _vp, _c_i32,
                                                         _c_i32, _c_i32, _c_i64, _c_i64, _vp, _vp, _vp]),
     "choco_gossip_step": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _vp]),
+    "choco_params_launches": (_c_i32, [_c_i32]),
+    "choco_params_pack": (_c_i32, [_pp, _p_i64, _p_i32, _c_i32, _vp, _c_i64, _vp]),
+    "choco_params_unpack": (_c_i32, [_pp, _p_i64, _p_i32, _c_i32, _vp, _c_i64, _vp]),
     "choco_gossip_topk_compress": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
     "choco_gossip_topk_compress_accumulate": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i64, _vp, _vp, _c_i32,
                                                        _c_f32, _vp, _c_sz, _vp]),

@@ -1059,6 +1059,48 @@ def gossip_step(x, memory, xhat, gamma):
                                        _stream(x.device)), "choco_gossip_step")
 
 
+# ----------------------------------------------------------------------------- parameter bridge
+PARAM_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # CHOCO_DT_*
+
+
+def params_launches(nseg):
+    """Launches one params_pack / params_unpack of `nseg` tensors takes."""
+    return int(lib().choco_params_launches(int(nseg)))
+
+
+def _param_tables(tensors, flat):
+    _require(flat, torch.float32, "flat")
+    nseg = len(tensors)
+    ptrs, lens, dts = (ctypes.c_void_p * nseg)(), (ctypes.c_int64 * nseg)(), (ctypes.c_int32 * nseg)()
+    for i, t in enumerate(tensors):
+        if not isinstance(t, torch.Tensor) or t.device != flat.device:
+            raise RuntimeError(f"tensor {i} must be a torch.Tensor on {flat.device}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"tensor {i} must be contiguous")
+        code = PARAM_DTYPES.get(t.dtype)
+        if code is None:
+            raise RuntimeError(f"tensor {i} must be float32, bfloat16 or float16, got {t.dtype}")
+        ptrs[i], lens[i], dts[i] = t.data_ptr(), t.numel(), code
+    return ptrs, lens, dts, nseg
+
+
+def params_pack(tensors, flat):
+    """flat[off_s : off_s + len_s] = tensors[s] widened to fp32, for every tensor in one batched
+    launch per chunk (flatten(), communication.py:58-76).  sum of the lengths == flat.numel()."""
+    ptrs, lens, dts, nseg = _param_tables(tensors, flat)
+    _lib.check(lib().choco_params_pack(ptrs, lens, dts, nseg, _ptr(flat), flat.numel(), _stream(flat.device)),
+               "choco_params_pack")
+
+
+def params_unpack(flat, tensors):
+    """tensors[s][...] = flat[off_s : off_s + len_s] narrowed to the tensor's dtype (round to
+    nearest even, as torch's converting copy), one batched launch per chunk
+    (TensorBuffer.unpack, tensor_buffer.py:38-40)."""
+    ptrs, lens, dts, nseg = _param_tables(tensors, flat)
+    _lib.check(lib().choco_params_unpack(ptrs, lens, dts, nseg, _ptr(flat), flat.numel(), _stream(flat.device)),
+               "choco_params_unpack")
+
+
 # ----------------------------------------------------------------------------- profiling
 def profile_enable(on=True):
     lib().choco_profile_enable(1 if on else 0)

@@ -1,4 +1,6 @@
 """Gossip-step helpers: drop-in for the CHOCO half of dl_code/pcode/optim/utils.py."""
+import torch
+
 from . import codec
 from .tensor_buffer import TensorBuffer
 
@@ -10,14 +12,21 @@ def _get_data(param_groups, idx, is_get_grad):
 
 
 def recover_params(param_groups, param_names, rank=None, neighbor_hat_params=None, get_hat_params=True):
-    """optim/utils.py:50-64: flat copies of the params (and of x_hat_i)."""
+    """optim/utils.py:50-64: flat copies of the params (and of x_hat_i).
+
+    The flat buffers of an fp32 / bf16 / fp16 model are fp32, as the reference's are
+    (communication.py:69-75 widens any model into the default dtype): the gossip step, the
+    delta and the message are computed from the unrounded fp32 copy, and only unpack() rounds
+    back to the model's precision (tensor_buffer.py:38-40)."""
     params = [_get_data(param_groups, idx, False) for idx, _ in param_names]
     params = [p for p in params if p is not None]
-    flatten_params = TensorBuffer(params)
+    floating = all(p.dtype in codec.PARAM_DTYPES for p in params)
+    flatten_params = TensorBuffer(params, dtype=torch.float32 if floating else None)
     if get_hat_params:
         assert neighbor_hat_params is not None and rank is not None
-        flatten_hat_params = TensorBuffer(params)
-        flatten_hat_params.buffer.data[:] = neighbor_hat_params[rank].buffer
+        hat = torch.empty_like(flatten_params.buffer)
+        hat.copy_(neighbor_hat_params[rank].buffer)
+        flatten_hat_params = TensorBuffer.from_flat(hat, [p.size() for p in params])
         return params, flatten_params, flatten_hat_params
     return params, flatten_params
 

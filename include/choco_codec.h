@@ -422,6 +422,39 @@ int choco_qsgd_decompress_accumulate_range(const uint8_t* const* packed_list, co
 int choco_gossip_step(float* x, const float* memory, const float* xhat, float gamma,
                       int64_t n, void* stream);
 
+/* ------------------------------------------- parameter pack / unpack
+ * The bridge between a model's parameter tensors and the flat fp32 buffer the
+ * entry points above work on: flatten() (pcode/utils/communication.py:58-76, one
+ * copy per tensor into a default-dtype -- fp32 -- buffer) and TensorBuffer.unpack
+ * (pcode/utils/tensor_buffer.py:38-40, one converting copy per tensor back), each
+ * as ONE launch per chunk of tensors.  Tensor s holds lens[s] contiguous elements
+ * of dtype dtypes[s] (CHOCO_DT_*) at DEVICE pointer ptrs[s] and owns flat elements
+ * [sum(lens[0..s)), + lens[s]); sum(lens) must equal n.  `ptrs`, `lens` and
+ * `dtypes` are HOST arrays, copied into the kernel arguments of each launch (no
+ * device-side table, nothing allocated, nothing synchronised), so they may be
+ * freed as soon as the call returns.
+ *   pack:   flat[..] = (float)tensor[..]       widening bf16 / fp16 is exact
+ *   unpack: tensor[..] = (dtype)flat[..]       round-to-nearest-even; +-0, +-inf and
+ *           NaN are kept, fp16 overflow gives inf, fp16 subnormals are produced
+ *           (torch's converting copy)
+ * Only the bytes of the layout's own elements are written: tensors may be views
+ * packed next to each other in one storage, `flat` may be a slice of a larger
+ * buffer.  Pointers need their element's alignment only (16-byte vectors are used
+ * where both sides of a group of 8 elements allow them).  Zero-length tensors are
+ * allowed (their pointer may be NULL).  Every argument is checked before the first
+ * launch without a HIP call; a bad one returns CHOCO_ERR_INVALID and launches
+ * nothing.  A layout takes choco_params_launches(nseg) launches of
+ * "param_pack_kernel" / "param_unpack_kernel" (choco_launch_count). */
+#define CHOCO_DT_F32 0
+#define CHOCO_DT_BF16 1
+#define CHOCO_DT_F16 2
+/* launches a layout of nseg tensors takes (host only); 0 for nseg <= 0 */
+int choco_params_launches(int32_t nseg);
+int choco_params_pack(const void* const* ptrs, const int64_t* lens, const int32_t* dtypes,
+                      int32_t nseg, float* flat, int64_t n, void* stream);
+int choco_params_unpack(void* const* ptrs, const int64_t* lens, const int32_t* dtypes,
+                        int32_t nseg, const float* flat, int64_t n, void* stream);
+
 /* ------------------------------------------- fused gossip step + compress
  * ParallelCHOCO_V.step's update_params_from_neighbor -> compress sequence
  * (pcode/optim/parallel_choco_v.py:116-142 -> :229-240, optim/utils.py:67-72) in

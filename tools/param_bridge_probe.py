@@ -1,0 +1,162 @@
+"""Cost of the bridge between a model's parameter tensors and the flat fp32 buffer:
+utils.recover_params(get_hat_params=True) + TensorBuffer.unpack, the pair every
+utils.fused_step runs around the codec work.  Uses only recover_params, unpack and torch,
+so the same script measures any commit of this repository.
+
+    python tools/param_bridge_probe.py [--out FILE] [--pairs 100] [--reps 5]
+
+Layouts (each parameter its own allocation): ResNet-50 in fp32, ResNet-50 in bf16, 3000
+tensors of 100 elements.  One JSON line per layout:
+  host_us_pair   host wall time per pair: `pairs` pairs queued, one synchronise, divided
+  gpu_us_pair    the same window between two device events
+  gpu_us_pack    recover_params(get_hat_params=False) alone between events (the pack)
+  launches_pair  device activities (kernels + copies) of one pair, from torch.profiler
+  copy_us_pair / copy_us_pack   the yardstick: one contiguous dst.copy_(src) that reads and
+                 writes as many bytes as the pair / the pack does, timed in the same run
+  kernel_us_*    dispatch-attached kernel times of the batched kernels, where the library
+                 has them
+(medians over `reps` windows after a warm-up window).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from chocosgd_amd import codec, utils  # noqa: E402
+from chocosgd_amd.tensor_buffer import TensorBuffer  # noqa: E402
+
+DEV = "cuda"
+
+
+def layouts():
+    with open(os.path.join(ROOT, "tests", "golden", "layouts.json")) as f:
+        r50 = json.load(f)["resnet50_imagenet"]
+    return [("resnet50_fp32", r50, torch.float32), ("resnet50_bf16", r50, torch.bfloat16),
+            ("t3000x100_fp32", [100] * 3000, torch.float32)]
+
+
+def events(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    host = (time.perf_counter() - t0) / iters * 1e6
+    return host, a.elapsed_time(b) / iters * 1e3
+
+
+def median_of(fn, iters, reps):
+    events(fn, max(2, iters // 10))  # warm-up: code objects, the allocator's blocks
+    runs = [events(fn, iters) for _ in range(reps)]
+    return statistics.median(r[0] for r in runs), statistics.median(r[1] for r in runs)
+
+
+def copy_yardstick(nbytes_moved, iters, reps):
+    """A contiguous copy that reads + writes `nbytes_moved` bytes in all."""
+    m = max(16, nbytes_moved // 2 // 4)
+    src, dst = torch.randn(m, device=DEV), torch.empty(m, device=DEV)
+    return median_of(lambda: dst.copy_(src), iters, reps)[1]
+
+
+def count_launches(fn):
+    """Device activities of one call; None (and the reason on stderr) where torch's profiler
+    cannot trace the device."""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    try:
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        cnt = sum(1 for e in prof.events() if str(e.device_type).endswith("CUDA"))
+    except Exception as e:  # noqa: BLE001
+        print(f"launch count not measured: {e}", file=sys.stderr)
+        return None
+    return cnt or None
+
+
+def kernel_times(fn, iters):
+    """Dispatch-attached times of the batched kernels (a library that has them)."""
+    if not hasattr(codec, "params_pack"):
+        return {}
+    names = ["param_pack_kernel", "param_unpack_kernel"]
+    codec.profile_reset()
+    codec.profile_filter(names)
+    codec.profile_enable(True)
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    codec.profile_enable(False)
+    out = {}
+    for nm in names:
+        t, c = codec.profile_read(nm)
+        if c:
+            out["kernel_us_" + nm.split("_")[1]] = round(t / c * 1e3, 2)
+            out["kernel_launches_" + nm.split("_")[1]] = c // iters
+    codec.profile_filter(None)
+    codec.profile_reset()
+    return out
+
+
+def measure(name, lens, dtype, pairs, reps):
+    g = torch.Generator(device=DEV).manual_seed(0)
+    params = [torch.randn(m, generator=g, device=DEV).to(dtype) for m in lens]
+    groups = [{"params": [p], "name": f"p{i}"} for i, p in enumerate(params)]
+    names = list(enumerate(gr["name"] for gr in groups))
+    n = sum(lens)
+    hat = TensorBuffer.from_flat(torch.randn(n, generator=g, device=DEV), [(m,) for m in lens])
+    nhp = {0: hat}
+
+    def pair():
+        _, fp, fh = utils.recover_params(groups, names, 0, nhp, get_hat_params=True)
+        fp.unpack(params)
+
+    def pack():
+        utils.recover_params(groups, names, get_hat_params=False)
+
+    host_pair, gpu_pair = median_of(pair, pairs, reps)
+    _, gpu_pack = median_of(pack, pairs, reps)
+    _, fp, _ = utils.recover_params(groups, names, 0, nhp, get_hat_params=True)
+    esz, fsz = params[0].element_size(), fp.buffer.element_size()
+    pack_bytes = n * (esz + fsz)                    # read the tensors, write the flat buffer
+    pair_bytes = 2 * pack_bytes + 2 * n * fsz       # + the x_hat copy, + the unpack
+    row = {"layout": name, "tensors": len(lens), "elements": n, "param_dtype": str(dtype).split(".")[-1],
+           "flat_dtype": str(fp.buffer.dtype).split(".")[-1], "pairs": pairs, "reps": reps,
+           "host_us_pair": round(host_pair, 1), "gpu_us_pair": round(gpu_pair, 1), "gpu_us_pack": round(gpu_pack, 1),
+           "launches_pair": count_launches(pair), "launches_pack": count_launches(pack),
+           "pair_bytes": pair_bytes, "pack_bytes": pack_bytes,
+           "copy_us_pair": round(copy_yardstick(pair_bytes, pairs, reps), 1),
+           "copy_us_pack": round(copy_yardstick(pack_bytes, pairs, reps), 1)}
+    row.update(kernel_times(pair, 20))
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--pairs", type=int, default=100)
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "the probe needs a ROCm device"
+    rows = []
+    for name, lens, dtype in layouts():
+        rows.append(measure(name, lens, dtype, args.pairs, args.reps))
+        print(json.dumps(rows[-1]), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
