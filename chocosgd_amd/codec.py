@@ -119,17 +119,7 @@ def topk_fallback_count(dev=None, plan=None):
     """Diagnostic: calls on this stream's flat top-k workspace that took the exact fallback,
     or (plan=...) segments of that plan whose warm window missed (include/choco_codec.h
     CHOCO_TOPK_FALLBACKS_OFFSET).  Synchronises the stream."""
-    dev = torch.device(dev) if dev is not None else torch.device("cuda", torch.cuda.current_device())
-    if plan is not None:
-        ws = plan.workspace(dev)
-    else:
-        with _ws_lock:
-            ws = _ws_cache.get((dev.index, torch.cuda.current_stream(dev).cuda_stream, "topk"))
-        if ws is None:
-            return 0
-    off = _lib.TOPK_FALLBACKS_OFFSET
-    torch.cuda.current_stream(dev).synchronize()
-    return int(ws[off:off + 4].view(torch.int32).item())
+    return topk_workspace_word(_lib.TOPK_FALLBACKS_OFFSET, dev=dev, plan=plan)
 
 
 def workspace_bytes():
@@ -185,6 +175,25 @@ def _gossip(gossip, x, xhat):
     return memory, float(gamma)
 
 
+def _sparse_outputs(x, xhat, k, out, what="k"):
+    """x (and xhat) checked, and the (values f32[k], indices i32[k]) outputs: the caller's
+    `out` buffers, or fresh ones."""
+    _require(x, torch.float32, "x")
+    if xhat is not None:
+        _require(xhat, torch.float32, "xhat")
+        if xhat.numel() != x.numel():
+            raise RuntimeError("x and xhat must have the same number of elements")
+    if out is None:
+        return (torch.empty(k, dtype=torch.float32, device=x.device),
+                torch.empty(k, dtype=torch.int32, device=x.device))
+    vals, idx = out
+    _require(vals, torch.float32, "out values")
+    _require(idx, torch.int32, "out indices")
+    if vals.numel() != k or idx.numel() != k:
+        raise RuntimeError(f"out buffers must hold exactly {what} elements")
+    return vals, idx
+
+
 # ----------------------------------------------------------------------------- top-k
 def topk_k(n, ratio):
     """k = max(1, int(n * (1 - ratio))) (sparsification.py:22,45)."""
@@ -202,22 +211,9 @@ def topk(x, k, xhat=None, out=None, gossip=None, fold=None):
     bit-identical to the reference when the self rank is the first message applied to
     memory (include/choco_codec.h, choco_topk_compress_accumulate).  With `gossip`,
     hat_self must be xhat and memory the gossip memory (or None)."""
-    _require(x, torch.float32, "x")
-    if xhat is not None:
-        _require(xhat, torch.float32, "xhat")
-        if xhat.numel() != x.numel():
-            raise RuntimeError("x and xhat must have the same number of elements")
+    vals, idx = _sparse_outputs(x, xhat, k, out)
     n = x.numel()
     dev = x.device
-    if out is not None:
-        vals, idx = out
-        _require(vals, torch.float32, "out values")
-        _require(idx, torch.int32, "out indices")
-        if vals.numel() != k or idx.numel() != k:
-            raise RuntimeError("out buffers must hold exactly k elements")
-    else:
-        vals = torch.empty(k, dtype=torch.float32, device=dev)
-        idx = torch.empty(k, dtype=torch.int32, device=dev)
     L = lib()
     ws = workspace(dev, "topk", L.choco_topk_workspace_size(n))
     st = topk_status(ws)
@@ -338,19 +334,7 @@ def _seg_outputs(x, xhat, plan, out):
     _require(x, torch.float32, "x")
     if x.numel() != plan.n:
         raise RuntimeError(f"x holds {x.numel()} elements, the segment plan {plan.n}")
-    if xhat is not None:
-        _require(xhat, torch.float32, "xhat")
-        if xhat.numel() != x.numel():
-            raise RuntimeError("x and xhat must have the same number of elements")
-    if out is not None:
-        vals, idx = out
-        _require(vals, torch.float32, "out values")
-        _require(idx, torch.int32, "out indices")
-        if vals.numel() != plan.k_total or idx.numel() != plan.k_total:
-            raise RuntimeError("out buffers must hold exactly the plan's K elements")
-        return vals, idx
-    return (torch.empty(plan.k_total, dtype=torch.float32, device=x.device),
-            torch.empty(plan.k_total, dtype=torch.int32, device=x.device))
+    return _sparse_outputs(x, xhat, plan.k_total, out, what="the plan's K")
 
 
 def topk_segmented(x, plan, xhat=None, out=None, gossip=None):
@@ -388,22 +372,9 @@ def randk(x, k, seed, is_biased=True, xhat=None, offset=0, out=None):
     """Uniform random k-subset (include/choco_codec.h: the device sampler of (seed, offset)),
     values x[i] (- xhat[i]) (* n / k unbiased), int32 indices in ascending order;
     `out=(values f32[k], indices i32[k])` writes into caller buffers."""
-    _require(x, torch.float32, "x")
-    if xhat is not None:
-        _require(xhat, torch.float32, "xhat")
-        if xhat.numel() != x.numel():
-            raise RuntimeError("x and xhat must have the same number of elements")
+    vals, idx = _sparse_outputs(x, xhat, k, out)
     n = x.numel()
     dev = x.device
-    if out is not None:
-        vals, idx = out
-        _require(vals, torch.float32, "out values")
-        _require(idx, torch.int32, "out indices")
-        if vals.numel() != k or idx.numel() != k:
-            raise RuntimeError("out buffers must hold exactly k elements")
-    else:
-        vals = torch.empty(k, dtype=torch.float32, device=dev)
-        idx = torch.empty(k, dtype=torch.int32, device=dev)
     L = lib()
     ws = workspace(dev, "randk", L.choco_randk_workspace_size(n))
     _lib.check(L.choco_randk_compress(_ptr(x), _ptr(xhat), n, int(k), int(seed) & (2**64 - 1),
@@ -679,13 +650,31 @@ def sign_unpack(packed, n):
 MAX_FUSED_MSGS = 8  # messages one fused accumulate launch takes (sign.hip kMaxMsg, qsgd.hip kQMaxMsg)
 
 
-def _msg_chunks(nmsg, self_slot):
-    """Consecutive chunks of <= MAX_FUSED_MSGS messages, in order, with the local
-    slot re-based into its chunk (-1 elsewhere).  memory is updated message by
-    message, so chunked launches give the same fp32 sequence as one launch."""
-    for c0 in range(0, nmsg, MAX_FUSED_MSGS):
-        c1 = min(nmsg, c0 + MAX_FUSED_MSGS)
-        yield c0, c1, (self_slot - c0) if c0 <= self_slot < c1 else -1
+def _msg_tables(messages, weights, self_slot, dtype, kind, size, unit, nseg):
+    """Checks the [(packed, norms)] messages of a multi-message call (`size` `unit`s of `dtype`
+    and nseg norms each, one weight per message) and returns the C tables of its launches:
+    [(packed**, norms**, weights*, count, slot, keep-alive)] for consecutive chunks of
+    <= MAX_FUSED_MSGS messages, in order, with the local slot re-based into its chunk (-1
+    elsewhere).  memory is updated message by message, so chunked launches give the same fp32
+    sequence as one launch."""
+    if len(messages) != len(weights):
+        raise RuntimeError("one weight per message")
+    for p, nm in messages:
+        _require(p, dtype, "packed")
+        _require(nm, torch.float32, "norms")
+        if p.numel() != size or nm.numel() != nseg:
+            raise RuntimeError(f"{kind} message must hold {size} {unit} and {nseg} norms, got {p.numel()} / "
+                               f"{nm.numel()}")
+    self_slot = int(self_slot)
+    calls = []
+    for c0 in range(0, len(messages), MAX_FUSED_MSGS):
+        part = messages[c0:c0 + MAX_FUSED_MSGS]
+        pp, keep1 = _lib.ptr_array([p.data_ptr() for p, _ in part])
+        nn, keep2 = _lib.ptr_array([nm.data_ptr() for _, nm in part])
+        ww, keep3 = _lib.f32_array([float(w) for w in weights[c0:c0 + len(part)]])
+        slot = self_slot - c0 if c0 <= self_slot < c0 + len(part) else -1
+        calls.append((pp, nn, ww, len(part), slot, (keep1, keep2, keep3)))
+    return calls
 
 
 def _check_layout(memory, xhat_self, n, seg_off, nseg):
@@ -706,21 +695,9 @@ def sign_accumulate(messages, weights, self_slot, n, memory, xhat_self=None, seg
     (launched in fused chunks of MAX_FUSED_MSGS)."""
     _require(memory, torch.float32, "memory")
     _check_layout(memory, xhat_self, n, seg_off, nseg)
-    if len(messages) != len(weights):
-        raise RuntimeError("one weight per message")
-    words = sign_words(n)
-    for p, nm in messages:
-        _require(p, torch.int32, "packed")
-        _require(nm, torch.float32, "norms")
-        if p.numel() != words or nm.numel() != nseg:
-            raise RuntimeError(f"sign message must hold {words} words and {nseg} norms, got {p.numel()} / "
-                               f"{nm.numel()}")
-    for c0, c1, slot in _msg_chunks(len(messages), int(self_slot)):
-        part = messages[c0:c1]
-        pp, keep1 = _lib.ptr_array([p.data_ptr() for p, _ in part])
-        nn, keep2 = _lib.ptr_array([nm.data_ptr() for _, nm in part])
-        ww, keep3 = _lib.f32_array([float(w) for w in weights[c0:c1]])
-        _lib.check(lib().choco_sign_decompress_accumulate(pp, nn, ww, len(part), slot, int(n), _ptr(seg_off),
+    for pp, nn, ww, m, slot, _keep in _msg_tables(messages, weights, self_slot, torch.int32, "sign", sign_words(n),
+                                                  "words", nseg):
+        _lib.check(lib().choco_sign_decompress_accumulate(pp, nn, ww, m, slot, int(n), _ptr(seg_off),
                                                           int(nseg), _ptr(xhat_self if slot >= 0 else None),
                                                           _ptr(memory), ctypes.c_void_p(0), 0,
                                                           _stream(memory.device)),
@@ -743,30 +720,22 @@ def sign_recv_gossip_compress(messages, weights, self_slot, x, memory, xhat, gam
     if len(messages) != len(weights) or not messages:
         raise RuntimeError("one weight per message, at least one message")
     words = sign_words(n)
-    for p, nm in messages:
-        _require(p, torch.int32, "packed")
-        _require(nm, torch.float32, "norms")
-        if p.numel() != words or nm.numel() != nseg:
-            raise RuntimeError(f"sign message must hold {words} words and {nseg} norms")
+    head = max(0, len(messages) - MAX_FUSED_MSGS)  # leading messages: applied first, in order
+    (pp, nn, ww, m, slot, _keep), = _msg_tables(messages[head:], weights[head:], self_slot - head, torch.int32, "sign",
+                                                words, "words", nseg)
     dev = x.device
     if out is not None:
         packed, norms = _out_views(out, words, torch.int32, nseg, dev)
     else:
         packed = torch.empty(words, dtype=torch.int32, device=dev)
         norms = torch.empty(nseg, dtype=torch.float32, device=dev)
-    head = len(messages) - MAX_FUSED_MSGS
-    if head > 0:  # leading messages first, in order
+    if head > 0:
         sign_accumulate(messages[:head], weights[:head], self_slot, n, memory,
                         xhat_self=xhat if 0 <= self_slot < head else None, seg_off=seg_off, nseg=nseg)
-        messages, weights, self_slot = messages[head:], weights[head:], self_slot - head
-    slot = self_slot if 0 <= self_slot < len(messages) else -1
     L = lib()
     # (its own workspace: the accumulator block plus bit planes of the messages and the output)
-    ws = workspace(dev, "signrecv", L.choco_sign_recv_workspace_size(n, nseg, len(messages)))
-    pp, keep1 = _lib.ptr_array([p.data_ptr() for p, _ in messages])
-    nn, keep2 = _lib.ptr_array([nm.data_ptr() for _, nm in messages])
-    ww, keep3 = _lib.f32_array([float(w) for w in weights])
-    _lib.check(L.choco_sign_recv_gossip_compress(pp, nn, ww, len(messages), slot, _ptr(x), _ptr(memory), _ptr(xhat),
+    ws = workspace(dev, "signrecv", L.choco_sign_recv_workspace_size(n, nseg, m))
+    _lib.check(L.choco_sign_recv_gossip_compress(pp, nn, ww, m, slot, _ptr(x), _ptr(memory), _ptr(xhat),
                                                  float(gamma), n, _ptr(seg_off), int(nseg), _ptr(packed),
                                                  _ptr(norms), _ptr(ws), ws.numel(), _stream(dev)),
                "choco_sign_recv_gossip_compress")
@@ -779,20 +748,9 @@ def sign_axpy(messages, weights, n, target, seg_off=None, nseg=1, two_roundings=
     over add_(u, alpha=w) (include/choco_codec.h)."""
     _require(target, torch.float32, "target")
     _check_layout(target, None, n, seg_off, nseg)
-    if len(messages) != len(weights):
-        raise RuntimeError("one weight per message")
-    words = sign_words(n)
-    for p, nm in messages:
-        _require(p, torch.int32, "packed")
-        _require(nm, torch.float32, "norms")
-        if p.numel() != words or nm.numel() != nseg:
-            raise RuntimeError(f"sign message must hold {words} words and {nseg} norms")
-    for c0, c1, _ in _msg_chunks(len(messages), -1):
-        part = messages[c0:c1]
-        pp, keep1 = _lib.ptr_array([p.data_ptr() for p, _ in part])
-        nn, keep2 = _lib.ptr_array([nm.data_ptr() for _, nm in part])
-        ww, keep3 = _lib.f32_array([float(w) for w in weights[c0:c1]])
-        _lib.check(lib().choco_sign_decompress_axpy(pp, nn, ww, len(part), int(n), _ptr(seg_off), int(nseg),
+    for pp, nn, ww, m, _slot, _keep in _msg_tables(messages, weights, -1, torch.int32, "sign", sign_words(n), "words",
+                                                   nseg):
+        _lib.check(lib().choco_sign_decompress_axpy(pp, nn, ww, m, int(n), _ptr(seg_off), int(nseg),
                                                     1 if two_roundings else 0, _ptr(target),
                                                     _stream(target.device)), "choco_sign_decompress_axpy")
 
@@ -892,21 +850,9 @@ def qsgd_accumulate(messages, weights, self_slot, n, q, memory, xhat_self=None, 
     (launched in fused chunks of MAX_FUSED_MSGS)."""
     _require(memory, torch.float32, "memory")
     _check_layout(memory, xhat_self, n, seg_off, nseg)
-    if len(messages) != len(weights):
-        raise RuntimeError("one weight per message")
-    nbytes = qsgd_packed_bytes(n, q)
-    for p, nm in messages:
-        _require(p, torch.uint8, "packed")
-        _require(nm, torch.float32, "norms")
-        if p.numel() != nbytes or nm.numel() != nseg:
-            raise RuntimeError(f"QSGD message must hold {nbytes} bytes and {nseg} norms, got {p.numel()} / "
-                               f"{nm.numel()}")
-    for c0, c1, slot in _msg_chunks(len(messages), int(self_slot)):
-        part = messages[c0:c1]
-        pp, keep1 = _lib.ptr_array([p.data_ptr() for p, _ in part])
-        nn, keep2 = _lib.ptr_array([nm.data_ptr() for _, nm in part])
-        ww, keep3 = _lib.f32_array([float(w) for w in weights[c0:c1]])
-        _lib.check(lib().choco_qsgd_decompress_accumulate(pp, nn, ww, len(part), slot, int(n), _ptr(seg_off),
+    for pp, nn, ww, m, slot, _keep in _msg_tables(messages, weights, self_slot, torch.uint8, "QSGD",
+                                                  qsgd_packed_bytes(n, q), "bytes", nseg):
+        _lib.check(lib().choco_qsgd_decompress_accumulate(pp, nn, ww, m, slot, int(n), _ptr(seg_off),
                                                           int(nseg), int(q), 1 if is_biased else 0,
                                                           _ptr(xhat_self if slot >= 0 else None), _ptr(memory),
                                                           _stream(memory.device)),
@@ -974,27 +920,18 @@ def qsgd_recv_gossip_norms(messages, weights, self_slot, x, memory, xhat, gamma,
     n = x.numel()
     if len(messages) != len(weights) or not messages:
         raise RuntimeError("one weight per message, at least one message")
-    nbytes = qsgd_packed_bytes(n, q)
-    for p, nm in messages:
-        _require(p, torch.uint8, "packed")
-        _require(nm, torch.float32, "norms")
-        if p.numel() != nbytes or nm.numel() != nseg:
-            raise RuntimeError(f"QSGD message must hold {nbytes} bytes and {nseg} norms")
+    head = max(0, len(messages) - MAX_FUSED_MSGS)  # leading messages: applied first, in order
+    (pp, nn, ww, m, slot, _keep), = _msg_tables(messages[head:], weights[head:], self_slot - head, torch.uint8, "QSGD",
+                                                qsgd_packed_bytes(n, q), "bytes", nseg)
     dev = x.device
     norms = out if out is not None else torch.empty(nseg, dtype=torch.float32, device=dev)
     _require(norms, torch.float32, "norms")
-    head = len(messages) - MAX_FUSED_MSGS
-    if head > 0:  # leading messages first, in order
+    if head > 0:
         qsgd_accumulate(messages[:head], weights[:head], self_slot, n, q, memory, xhat_self=xhat,
                         is_biased=is_biased, seg_off=seg_off, nseg=nseg)
-        messages, weights, self_slot = messages[head:], weights[head:], self_slot - head
-    slot = self_slot if 0 <= self_slot < len(messages) else -1
     L = lib()
     ws = workspace(dev, "acc", L.choco_qsgd_workspace_size(nseg))
-    pp, keep1 = _lib.ptr_array([p.data_ptr() for p, _ in messages])
-    nn, keep2 = _lib.ptr_array([nm.data_ptr() for _, nm in messages])
-    ww, keep3 = _lib.f32_array([float(w) for w in weights])
-    _lib.check(L.choco_qsgd_recv_gossip_norms(pp, nn, ww, len(messages), slot, _ptr(x), _ptr(memory), _ptr(xhat),
+    _lib.check(L.choco_qsgd_recv_gossip_norms(pp, nn, ww, m, slot, _ptr(x), _ptr(memory), _ptr(xhat),
                                               float(gamma), n, _ptr(seg_off), int(nseg), int(q),
                                               1 if is_biased else 0, _ptr(norms), _ptr(ws), ws.numel(),
                                               _stream(dev)), "choco_qsgd_recv_gossip_norms")
@@ -1020,21 +957,10 @@ def qsgd_accumulate_range(messages, weights, self_slot, n, q, memory, e0, e1, xh
     """qsgd_accumulate over elements [e0, e1); messages: list of (range message, norms)."""
     _require(memory, torch.float32, "memory")
     _check_layout(memory, xhat_self, n, seg_off, nseg)
-    if len(messages) != len(weights):
-        raise RuntimeError("one weight per message")
-    nbytes = qsgd_packed_bytes(e1 - e0, q)
-    for p, nm in messages:
-        _require(p, torch.uint8, "packed")
-        _require(nm, torch.float32, "norms")
-        if p.numel() != nbytes or nm.numel() != nseg:
-            raise RuntimeError(f"QSGD range message must hold {nbytes} bytes and {nseg} norms")
-    for c0, c1, slot in _msg_chunks(len(messages), int(self_slot)):
-        part = messages[c0:c1]
-        pp, keep1 = _lib.ptr_array([p.data_ptr() for p, _ in part])
-        nn, keep2 = _lib.ptr_array([nm.data_ptr() for _, nm in part])
-        ww, keep3 = _lib.f32_array([float(w) for w in weights[c0:c1]])
+    for pp, nn, ww, m, slot, _keep in _msg_tables(messages, weights, self_slot, torch.uint8, "QSGD range",
+                                                  qsgd_packed_bytes(e1 - e0, q), "bytes", nseg):
         _lib.check(lib().choco_qsgd_decompress_accumulate_range(
-            pp, nn, ww, len(part), slot, int(n), _ptr(seg_off), int(nseg), int(q), 1 if is_biased else 0, int(e0),
+            pp, nn, ww, m, slot, int(n), _ptr(seg_off), int(nseg), int(q), 1 if is_biased else 0, int(e0),
             int(e1), _ptr(xhat_self if slot >= 0 else None), _ptr(memory), _stream(memory.device)),
             "choco_qsgd_decompress_accumulate_range")
 

@@ -8,7 +8,6 @@
 #include <algorithm>
 #include <atomic>
 #include <map>
-#include <unordered_map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -33,71 +32,63 @@ int check_launch(const char* what) {
 
 // ---------------------------------------------------------------- profiling
 struct PendingEv {
-  std::string name;
+  const char* name;
   hipEvent_t a, b;
-  bool closed;
 };
 static std::atomic<bool> g_prof_on{false};
 static std::mutex g_prof_mu;
-static std::vector<PendingEv> g_pending;
+static std::vector<PendingEv> g_pending;   // pairs a launch has recorded, not yet read
 static std::map<std::string, std::pair<double, int64_t>> g_acc;
 static std::vector<std::string> g_filter;  // only these kernel names are timed (empty = all)
 static std::vector<hipEvent_t> g_free_ev;  // events are reused: no create/destroy per launch
 
-static thread_local ProfArm g_armed{nullptr, nullptr};
-// launches per kernel name, counted whether or not timing is on (choco_launch_count: the
-// bench's warm-hit rates; names are the string literals of the call sites)
-static std::mutex g_cnt_mu;
-static std::unordered_map<const char*, int64_t> g_launches;
+// the named call sites (choco_launch_count: the bench's warm-hit rates); a site registers
+// once, when its first launch constructs it, and lives as long as the library
+static std::mutex g_sites_mu;
+static std::vector<const LaunchSite*>& sites() {
+  static std::vector<const LaunchSite*> v;
+  return v;
+}
 
-void profile_begin(const char* name, hipStream_t) {
-  g_armed = ProfArm{nullptr, nullptr};
-  {
-    std::lock_guard<std::mutex> g(g_cnt_mu);
-    ++g_launches[name];
-  }
-  if (!g_prof_on.load(std::memory_order_relaxed)) return;
+LaunchSite::LaunchSite(const char* name) : name_(name) {
+  if (!name) return;
+  std::lock_guard<std::mutex> g(g_sites_mu);
+  sites().push_back(this);
+}
+
+EventPair LaunchSite::begin() {
+  EventPair ev{nullptr, nullptr};
+  if (!name_) return ev;
+  count_.fetch_add(1, std::memory_order_relaxed);
+  if (!g_prof_on.load(std::memory_order_relaxed)) return ev;
   std::lock_guard<std::mutex> g(g_prof_mu);
-  if (!g_filter.empty() && std::find(g_filter.begin(), g_filter.end(), std::string(name)) == g_filter.end()) return;
-  PendingEv p{name, nullptr, nullptr, false};  // closed once a launch takes the pair
-  for (hipEvent_t* e : {&p.a, &p.b}) {
+  if (!g_filter.empty() && std::find(g_filter.begin(), g_filter.end(), std::string(name_)) == g_filter.end())
+    return ev;
+  for (hipEvent_t* e : {&ev.a, &ev.b}) {
     if (!g_free_ev.empty()) {
       *e = g_free_ev.back();
       g_free_ev.pop_back();
     } else if (hipEventCreate(e) != hipSuccess) {
-      return;
+      if (ev.a) g_free_ev.push_back(ev.a);
+      return EventPair{nullptr, nullptr};
     }
   }
-  g_armed = ProfArm{p.a, p.b};
-  g_pending.push_back(p);
+  return ev;
 }
 
-void profile_end(const char*, hipStream_t) { g_armed = ProfArm{nullptr, nullptr}; }
-
-ProfArm profile_take() {
-  const ProfArm r = g_armed;
-  g_armed = ProfArm{nullptr, nullptr};
-  if (r.a) {  // the launch records this pair: only now may it be read (events are reused)
-    std::lock_guard<std::mutex> g(g_prof_mu);
-    for (auto it = g_pending.rbegin(); it != g_pending.rend(); ++it)
-      if (it->a == r.a) {
-        it->closed = true;
-        break;
-      }
-  }
-  return r;
+// the launch has recorded this pair: only now may it be read (events are reused)
+void LaunchSite::timed(EventPair ev) {
+  std::lock_guard<std::mutex> g(g_prof_mu);
+  g_pending.push_back(PendingEv{name_, ev.a, ev.b});
 }
 
 static void profile_drain_locked() {
   for (auto& p : g_pending) {
-    if (p.closed) {
-      float ms = 0.f;
-      // (an armed pair that never reached a launch is not closed: skipped)
-      if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-        auto& e = g_acc[p.name];
-        e.first += ms;
-        e.second += 1;
-      }
+    float ms = 0.f;
+    if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
+      auto& e = g_acc[p.name];
+      e.first += ms;
+      e.second += 1;
     }
     g_free_ev.push_back(p.a);
     g_free_ev.push_back(p.b);
@@ -149,10 +140,10 @@ CHOCO_API int choco_profile_read(const char* name, double* total_ms, int64_t* co
 }
 
 CHOCO_API int64_t choco_launch_count(const char* name) {
-  std::lock_guard<std::mutex> g(g_cnt_mu);
+  std::lock_guard<std::mutex> g(g_sites_mu);
   int64_t n = 0;
-  for (const auto& e : g_launches)
-    if (name && strcmp(e.first, name) == 0) n += e.second;
+  for (const LaunchSite* s : sites())
+    if (name && strcmp(s->name(), name) == 0) n += s->count();
   return n;
 }
 

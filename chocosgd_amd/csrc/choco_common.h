@@ -18,6 +18,9 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <atomic>
+#include <initializer_list>
+
 #include "../../include/choco_codec.h"
 
 #define CHOCO_DEV __device__ __forceinline__
@@ -37,9 +40,10 @@ int check_launch(const char* what);
                            hipGetErrorString(_e));                          \
   } while (0)
 
-#define CHOCO_LAUNCHED(what)                                                \
+// returns a failed step's status code from the calling function
+#define CHOCO_TRY(expr)                                                     \
   do {                                                                      \
-    int _rc = ::choco::check_launch(what);                                  \
+    const int _rc = (expr);                                                 \
     if (_rc) return _rc;                                                    \
   } while (0)
 
@@ -48,22 +52,45 @@ int check_launch(const char* what);
     if (!(cond)) return ::choco::fail(CHOCO_ERR_INVALID, __VA_ARGS__);      \
   } while (0)
 
-// Optional per-kernel timing (bench roofline).  profile_begin arms a pair of
-// events for the NEXT launch made by this thread; CHOCO_KLAUNCH attaches them to
-// the dispatch itself (hipExtLaunchKernelGGL), so they time the kernel and not
-// whatever is still queued ahead of it on the stream.  profile_end disarms.
-struct ProfArm {
+// One call per kernel launch.  A call site is a static LaunchSite: it registers its
+// profile name once and counts its launches in an atomic of its own, whether or not
+// timing is on (choco_launch_count sums the sites of a name).  With timing on and the
+// name in the filter, begin() hands out an event pair, the launch attaches it to the
+// dispatch itself (hipExtLaunchKernelGGL), so it times the kernel and not whatever is
+// still queued ahead of it on the stream, and timed() queues the pair for
+// choco_profile_read: a pair exists only for a launch that was made.  A null name is a
+// launch that is neither counted nor timed.
+struct EventPair {
   hipEvent_t a, b;
 };
-void profile_begin(const char* name, hipStream_t st);
-void profile_end(const char* name, hipStream_t st);
-ProfArm profile_take();
+class LaunchSite {
+ public:
+  explicit LaunchSite(const char* name);
+  EventPair begin();
+  void timed(EventPair ev);
+  const char* name() const { return name_; }
+  int64_t count() const { return count_.load(std::memory_order_relaxed); }
 
-#define CHOCO_KLAUNCH(kernel, grid, block, shm, st, ...)                                     \
-  do {                                                                                      \
-    const ::choco::ProfArm _pa = ::choco::profile_take();                                   \
-    hipExtLaunchKernelGGL(kernel, grid, block, shm, st, _pa.a, _pa.b, 0u, __VA_ARGS__);     \
-  } while (0)
+ private:
+  const char* name_;
+  std::atomic<int64_t> count_{0};
+};
+
+template <typename K, typename... A>
+int launch(LaunchSite& site, const char* what, K kernel, dim3 grid, dim3 block, hipStream_t st, A... args) {
+  const EventPair ev = site.begin();
+  hipExtLaunchKernelGGL(kernel, grid, block, 0, st, ev.a, ev.b, 0u, args...);
+  if (ev.a) site.timed(ev);
+  return check_launch(what);
+}
+
+// CHOCO_LAUNCH(profile name or nullptr, kernel name for the error text, kernel, grid, block,
+// stream, kernel arguments...): an int expression, CHOCO_OK or the failed launch's status.
+#define CHOCO_LAUNCH(prof, what, kernel, grid, block, st, ...)                              \
+  [&]() -> int {                                                                            \
+    static ::choco::LaunchSite site_(prof);                                                 \
+    return ::choco::launch(site_, what, kernel, grid, block, st, __VA_ARGS__);              \
+  }()
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -71,6 +98,25 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// ---------------------------------------------------------------- argument checks
+// Shared by the entry points; every check runs before the first HIP call.
+// A flat buffer of n elements in nseg segments, and the 16-byte alignment of `bufs`
+// (`what` names them in the error text; a null entry is an optional buffer left out).
+inline int check_flat(int64_t n, const int64_t* seg_off, int32_t nseg,
+                      std::initializer_list<const void*> bufs = {}, const char* what = "buffers") {
+  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
+  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
+  for (const void* p : bufs) CHOCO_REQUIRE(aligned16(p), "%s must be 16-byte aligned", what);
+  return CHOCO_OK;
+}
+// The message count and the slot of this rank's own message (-1: none) of a multi-message call.
+constexpr int kMaxMsg = 8;
+inline int check_msgs(int32_t nmsg, int32_t self_slot) {
+  CHOCO_REQUIRE(nmsg >= 1 && nmsg <= kMaxMsg, "nmsg must be in [1, %d]", kMaxMsg);
+  CHOCO_REQUIRE(self_slot >= -1 && self_slot < nmsg, "bad self_slot");
+  return CHOCO_OK;
+}
 
 // ---------------------------------------------------------------- device helpers
 CHOCO_DEV uint32_t fkey(float v) { return __float_as_uint(v) & 0x7fffffffu; }

@@ -8,6 +8,7 @@
 // All follow the reference's fp32 rounding sequence (no fused multiply-add:
 // the library is compiled with -ffp-contract=off).
 #include "choco_common.h"
+#include "dispatch.h"
 
 #include <algorithm>
 
@@ -225,17 +226,13 @@ int gossip_launch(float* x, const float* mem, const float* xh, float gamma, int6
   CHOCO_REQUIRE(x && mem && xh, "null pointer argument");
   CHOCO_REQUIRE(n > 0, "n must be positive");
   CHOCO_REQUIRE(aligned4(x) && aligned4(mem) && aligned4(xh), "buffers must be 4-byte aligned");
-  profile_begin("gossip_step", st);
   if (aligned16(x) && aligned16(mem) && aligned16(xh)) {
     const int64_t per = (int64_t)kEwThreads * 4 * kGossipU;
-    CHOCO_KLAUNCH(gossipu_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(kEwThreads), 0, st, x, mem, xh,
-                  gamma, n);
-  } else {
-    CHOCO_KLAUNCH(gossip1_kernel, dim3(ew_grid(n, 1)), dim3(kEwThreads), 0, st, x, mem, xh, gamma, n);
+    return CHOCO_LAUNCH("gossip_step", "gossip_kernel", gossipu_kernel, dim3((unsigned)((n + per - 1) / per)),
+                        dim3(kEwThreads), st, x, mem, xh, gamma, n);
   }
-  profile_end("gossip_step", st);
-  CHOCO_LAUNCHED("gossip_kernel");
-  return CHOCO_OK;
+  return CHOCO_LAUNCH("gossip_step", "gossip_kernel", gossip1_kernel, dim3(ew_grid(n, 1)), dim3(kEwThreads), st, x,
+                      mem, xh, gamma, n);
 }
 
 }  // namespace choco
@@ -254,22 +251,16 @@ CHOCO_API int choco_sparse_accumulate(const float* val, const int32_t* idx, int6
   CHOCO_REQUIRE(val && idx && memory, "null pointer argument");
   CHOCO_REQUIRE(n > 0, "n must be positive");
   if (k <= 0) return CHOCO_OK;
-  profile_begin("sparse_accumulate", st);
   if (aligned16(memory) && (!xhat_self || aligned16(xhat_self))) {
     const unsigned g = (unsigned)((kSegL * k + kEwThreads - 1) / kEwThreads);
-    if (xhat_self)
-      CHOCO_KLAUNCH((sparse_acc_seg_kernel<true>), dim3(g), dim3(kEwThreads), 0, st, val, idx, k, xhat_self, memory,
-                    n, weight, bad_count);
-    else
-      CHOCO_KLAUNCH((sparse_acc_seg_kernel<false>), dim3(g), dim3(kEwThreads), 0, st, val, idx, k, xhat_self,
-                    memory, n, weight, bad_count);
-  } else {
-    CHOCO_KLAUNCH(sparse_acc_kernel, dim3((unsigned)((k + kEwThreads - 1) / kEwThreads)), dim3(kEwThreads), 0, st,
-                  val, idx, k, xhat_self, memory, n, weight, bad_count);
+    return dispatch_bool(xhat_self != nullptr, [&](auto HS) {
+      return CHOCO_LAUNCH("sparse_accumulate", "sparse_acc_kernel", (sparse_acc_seg_kernel<HS>), dim3(g),
+                          dim3(kEwThreads), st, val, idx, k, xhat_self, memory, n, weight, bad_count);
+    });
   }
-  profile_end("sparse_accumulate", st);
-  CHOCO_LAUNCHED("sparse_acc_kernel");
-  return CHOCO_OK;
+  return CHOCO_LAUNCH("sparse_accumulate", "sparse_acc_kernel", sparse_acc_kernel,
+                      dim3((unsigned)((k + kEwThreads - 1) / kEwThreads)), dim3(kEwThreads), st, val, idx, k,
+                      xhat_self, memory, n, weight, bad_count);
 }
 
 CHOCO_API size_t choco_sparse_accumulate_multi_workspace_size(int64_t n, int32_t nmsg) {
@@ -308,9 +299,8 @@ CHOCO_API int choco_gather(const float* x, const float* xhat, const int64_t* idx
   hipStream_t st = as_stream(stream);
   CHOCO_REQUIRE(x && idx && out_val, "null pointer argument");
   if (k <= 0) return CHOCO_OK;
-  CHOCO_KLAUNCH(gather_kernel, dim3(ew_grid(k, 1)), dim3(kEwThreads), 0, st, x, xhat, idx, k, scale, out_val);
-  CHOCO_LAUNCHED("gather_kernel");
-  return CHOCO_OK;
+  return CHOCO_LAUNCH(nullptr, "gather_kernel", gather_kernel, dim3(ew_grid(k, 1)), dim3(kEwThreads), st, x, xhat,
+                      idx, k, scale, out_val);
 }
 
 CHOCO_API int choco_sparse_extrapolate(const float* val, const int32_t* idx, int64_t k, float* target, int64_t n,
@@ -319,10 +309,7 @@ CHOCO_API int choco_sparse_extrapolate(const float* val, const int32_t* idx, int
   CHOCO_REQUIRE(val && idx && target, "null pointer argument");
   CHOCO_REQUIRE(n > 0, "n must be positive");
   if (k <= 0) return CHOCO_OK;
-  profile_begin("sparse_accumulate", st);
-  CHOCO_KLAUNCH(sparse_extrap_kernel, dim3((unsigned)((k + kEwThreads - 1) / kEwThreads)), dim3(kEwThreads), 0, st,
-                val, idx, k, target, n, a, b, bad_count);
-  profile_end("sparse_accumulate", st);
-  CHOCO_LAUNCHED("sparse_extrap_kernel");
-  return CHOCO_OK;
+  return CHOCO_LAUNCH("sparse_accumulate", "sparse_extrap_kernel", sparse_extrap_kernel,
+                      dim3((unsigned)((k + kEwThreads - 1) / kEwThreads)), dim3(kEwThreads), st, val, idx, k, target,
+                      n, a, b, bad_count);
 }

@@ -248,14 +248,8 @@ static int params_run(const void* const* ptrs, const int64_t* lens, const int32_
     // the tiles the chunk [off[0], off[nt]) touches; an empty chunk still takes its launch
     const int64_t tile0 = tb.off[0] / kPbTile;
     const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
-    profile_begin(name, st);
-    if (PACK)
-      CHOCO_KLAUNCH(param_pack_kernel, dim3((unsigned)tiles), dim3(kPbThreads), 0, st, tb, flat, tile0, flat16);
-    else
-      CHOCO_KLAUNCH(param_unpack_kernel, dim3((unsigned)tiles), dim3(kPbThreads), 0, st, tb, flat, tile0, flat16);
-    profile_end(name, st);
-    if (PACK) CHOCO_LAUNCHED("param_pack_kernel");
-    else CHOCO_LAUNCHED("param_unpack_kernel");
+    CHOCO_TRY(CHOCO_LAUNCH(name, name, PACK ? param_pack_kernel : param_unpack_kernel, dim3((unsigned)tiles),
+                           dim3(kPbThreads), st, tb, flat, tile0, flat16));
   }
   return CHOCO_OK;
 }

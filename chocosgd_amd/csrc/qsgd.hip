@@ -21,6 +21,7 @@
 //                         norm pass streamed last is re-read from the 256 MB
 //                         Infinity Cache instead of HBM.
 #include "choco_common.h"
+#include "dispatch.h"
 
 #include <algorithm>
 #include <math.h>
@@ -41,7 +42,7 @@ static int64_t norm_tile(int64_t n) {
 }
 constexpr int kNormSegLds = 64;  // a tile spanning fewer segments sums them in LDS first
 static_assert(kNormTile % kNormTileMin == 0 && kNormTileMin % 8192 == 0, "whole load rounds per norm tile");
-constexpr int kQMaxMsg = 8;
+constexpr int kQMaxMsg = kMaxMsg;
 constexpr int kAccRep = 8;  // replicas of the fp64 norm accumulators (the fused receive pass)
 
 struct QsgdWs {
@@ -941,72 +942,22 @@ __global__ __launch_bounds__(kQThreads) void qsgd_recv_gossip_norm_kernel(
   }
 }
 
-template <int CW>
-static void launch_recv_gossip(const QMsgs& M, int64_t n, const int64_t* seg_off, int nseg, int s_levels,
-                               int biased, float* x, float* hat, float* mem, float gamma, QsgdWs* ws, float* norms,
-                               hipStream_t st) {
-  const unsigned grid = (unsigned)((n + kRTile - 1) / kRTile);
-#define CHOCO_RG(NMV)                                                                                      \
-  case NMV:                                                                                                \
-    if (nseg > 1)                                                                                          \
-      CHOCO_KLAUNCH((qsgd_recv_gossip_norm_kernel<CW, NMV, true>), dim3(grid), dim3(kQThreads), 0, st, M, n, \
-                    seg_off, nseg, s_levels, biased, x, hat, mem, gamma, ws, norms);                       \
-    else                                                                                                   \
-      CHOCO_KLAUNCH((qsgd_recv_gossip_norm_kernel<CW, NMV, false>), dim3(grid), dim3(kQThreads), 0, st, M,   \
-                    n, seg_off, nseg, s_levels, biased, x, hat, mem, gamma, ws, norms);                    \
-    break;
-  switch (M.nmsg) {
-    CHOCO_RG(1)
-    CHOCO_RG(2)
-    CHOCO_RG(3)
-    CHOCO_RG(4)
-    CHOCO_RG(5)
-    CHOCO_RG(6)
-    CHOCO_RG(7)
-    CHOCO_RG(8)
-  }
-#undef CHOCO_RG
-}
-
-// Elements [e0, e1) (e0 a multiple of kQTile; e1 a multiple of it or n).
-template <int CW, int NM, int MODE>
-static void launch_decode(const QMsgs& M, int64_t n, const int64_t* seg_off, int nseg, int s_levels, int biased,
-                          float* hat, float* mem, hipStream_t st, int64_t e0, int64_t e1) {
-  const unsigned grid = (unsigned)((e1 - e0 + kQTile - 1) / kQTile);
-  if (nseg > 1)
-    CHOCO_KLAUNCH((qsgd_decode_kernel<CW, NM, MODE, true>), dim3(grid), dim3(kQThreads), 0, st, M, n, seg_off, nseg,
-                  s_levels, biased, hat, mem, e0 / kQTile);
-  else
-    CHOCO_KLAUNCH((qsgd_decode_kernel<CW, NM, MODE, false>), dim3(grid), dim3(kQThreads), 0, st, M, n, seg_off, nseg,
-                  s_levels, biased, hat, mem, e0 / kQTile);
-}
-
-template <int CW, int MODE>
-static void launch_decode_nm(const QMsgs& M, int64_t n, const int64_t* seg_off, int nseg, int s_levels,
-                             int biased, float* hat, float* mem, hipStream_t st, int64_t e0, int64_t e1) {
-  switch (M.nmsg) {
-    case 1: launch_decode<CW, 1, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-    case 2: launch_decode<CW, 2, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-    case 3: launch_decode<CW, 3, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-    case 4: launch_decode<CW, 4, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-    case 5: launch_decode<CW, 5, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-    case 6: launch_decode<CW, 6, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-    case 7: launch_decode<CW, 7, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-    default: launch_decode<CW, 8, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-  }
-}
-
+// Decodes elements [e0, e1) (e0 a multiple of kQTile; e1 a multiple of it or n; -1: n).
+// MODE 1 is the accumulate ("qsgd_accumulate"), MODE 0 the plain decode, which has no profile section.
 template <int MODE>
-static void launch_decode_cw(int cw, const QMsgs& M, int64_t n, const int64_t* seg_off, int nseg, int s_levels,
-                             int biased, float* hat, float* mem, hipStream_t st, int64_t e0 = 0, int64_t e1 = -1) {
+static int launch_decode(int cw, const QMsgs& M, int64_t n, const int64_t* seg_off, int nseg, int s_levels,
+                         int biased, float* hat, float* mem, hipStream_t st, int64_t e0 = 0, int64_t e1 = -1) {
   if (e1 < 0) e1 = n;
-  switch (cw) {
-    case 1: launch_decode_nm<1, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-    case 2: launch_decode_nm<2, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-    case 4: launch_decode_nm<4, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-    case 8: launch_decode_nm<8, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-    default: launch_decode_nm<16, MODE>(M, n, seg_off, nseg, s_levels, biased, hat, mem, st, e0, e1); break;
-  }
+  const unsigned grid = (unsigned)((e1 - e0 + kQTile - 1) / kQTile);
+  return dispatch_width(cw, [&](auto CW) {
+    return dispatch_nmsg(M.nmsg, [&](auto NM) {
+      return dispatch_bool(nseg > 1, [&](auto SEG) {
+        return CHOCO_LAUNCH(MODE ? "qsgd_accumulate" : nullptr, "qsgd_decode_kernel",
+                            (qsgd_decode_kernel<CW, NM, MODE, SEG>), dim3(grid), dim3(kQThreads), st, M, n, seg_off,
+                            nseg, s_levels, biased, hat, mem, e0 / kQTile);
+      });
+    });
+  });
 }
 
 }  // namespace choco
@@ -1026,10 +977,7 @@ CHOCO_API size_t choco_qsgd_workspace_size(int32_t nseg) {
 
 static int qsgd_check(const float* x, const float* xhat, int64_t n, const int64_t* seg_off, int32_t nseg) {
   CHOCO_REQUIRE(x, "null pointer argument");
-  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
-  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
-  CHOCO_REQUIRE(aligned16(x) && (!xhat || aligned16(xhat)), "buffers must be 16-byte aligned");
-  return CHOCO_OK;
+  return check_flat(n, seg_off, nseg, {x, xhat});
 }
 
 // The norm pass (per-segment ||d||_2, fp64, rounded once); gs: the fused gossip step.
@@ -1041,19 +989,13 @@ static int qsgd_norms_launch(const float* x, const float* xhat, int64_t n, const
   const int64_t tile = norm_tile(n);
   const unsigned g1 = (unsigned)((n + tile - 1) / tile);
   QsgdWs* w = static_cast<QsgdWs*>(ws);
-  profile_begin("qsgd_norm", st);
-if (gs.mem)
-    CHOCO_KLAUNCH((qsgd_norm_kernel<true, true>), dim3(g1), dim3(kQThreads), 0, st, x, xhat, n, seg_off, nseg,
-                  norms_out, w, gs, tile);
-  else if (xhat)
-    CHOCO_KLAUNCH((qsgd_norm_kernel<true>), dim3(g1), dim3(kQThreads), 0, st, x, xhat, n, seg_off, nseg,
-                  norms_out, w, gs, tile);
-  else
-    CHOCO_KLAUNCH((qsgd_norm_kernel<false>), dim3(g1), dim3(kQThreads), 0, st, x, xhat, n, seg_off, nseg,
-                  norms_out, w, gs, tile);
-  profile_end("qsgd_norm", st);
-  CHOCO_LAUNCHED("qsgd_norm_kernel");
-  return CHOCO_OK;
+  auto norm = [&](auto XH, auto GS) {
+    return CHOCO_LAUNCH("qsgd_norm", "qsgd_norm_kernel", (qsgd_norm_kernel<XH, GS>), dim3(g1), dim3(kQThreads), st, x,
+                        xhat, n, seg_off, nseg, norms_out, w, gs, tile);
+  };
+  if (gs.mem) return norm(std::true_type{}, std::true_type{});
+  if (xhat) return norm(std::true_type{}, std::false_type{});
+  return norm(std::false_type{}, std::false_type{});
 }
 
 // The quantize pass over elements [e0, e1) into planes indexed by ABSOLUTE element
@@ -1074,32 +1016,17 @@ static int qsgd_quant_launch(const float* x, const float* xhat, int64_t n, const
   const int s_levels = (1 << q) - 1;
   const int64_t tile_lo = e0 / kQStreamTile;
   const int64_t tile_cnt = (e1 - e0 + kQStreamTile - 1) / kQStreamTile;
-  profile_begin("qsgd_quantize", st);
-#define CHOCO_Q1(CWV, XHV, UINV)                                                                              \
-  CHOCO_KLAUNCH((qsgd_quant_kernel<CWV, XHV, XHV ? 1 : kQH, UINV>), dim3((unsigned)tile_cnt),                  \
-                dim3(kQThreads * (XHV ? 1 : kQH)), 0,                                                          \
-                st, x, xhat, n, seg_off, nseg, s_levels, is_biased, norms, u_in, seed, offset, lvl_plane,      \
-                sign_plane, dense_out, tile_lo, tile_cnt, pad_e0, e1 - pad_e0)
-#define CHOCO_Q(CWV)                                                                                          \
-  case CWV:                                                                                                   \
-    if (xhat) {                                                                                               \
-      if (u_in) CHOCO_Q1(CWV, true, true); else CHOCO_Q1(CWV, true, false);                                   \
-    } else {                                                                                                  \
-      if (u_in) CHOCO_Q1(CWV, false, true); else CHOCO_Q1(CWV, false, false);                                 \
-    }                                                                                                         \
-    break;
-  switch (cw) {
-    CHOCO_Q(1)
-    CHOCO_Q(2)
-    CHOCO_Q(4)
-    CHOCO_Q(8)
-    CHOCO_Q(16)
-  }
-#undef CHOCO_Q
-#undef CHOCO_Q1
-  profile_end("qsgd_quantize", st);
-  CHOCO_LAUNCHED("qsgd_quant_kernel");
-  return CHOCO_OK;
+  return dispatch_width(cw, [&](auto CW) {
+    return dispatch_bool(xhat != nullptr, [&](auto XH) {
+      return dispatch_bool(u_in != nullptr, [&](auto UIN) {
+        constexpr int H = XH ? 1 : kQH;
+        return CHOCO_LAUNCH("qsgd_quantize", "qsgd_quant_kernel", (qsgd_quant_kernel<CW, XH, H, UIN>),
+                            dim3((unsigned)tile_cnt), dim3(kQThreads * H), st, x, xhat, n, seg_off, nseg, s_levels,
+                            is_biased, norms, u_in, seed, offset, lvl_plane, sign_plane, dense_out, tile_lo, tile_cnt,
+                            pad_e0, e1 - pad_e0);
+      });
+    });
+  });
 }
 
 static int qsgd_compress(const float* x, const float* xhat, int64_t n, const int64_t* seg_off, int32_t nseg,
@@ -1144,6 +1071,22 @@ static void range_planes(const uint8_t* packed_range, int64_t e0, int64_t len, i
   const uintptr_t base = reinterpret_cast<uintptr_t>(packed_range);
   *lvl = reinterpret_cast<const uint8_t*>(base - (uintptr_t)((e0 / kQPer) * cw));
   *sgn = reinterpret_cast<const uint8_t*>(base + (uintptr_t)plane_bytes(len, cw) - (uintptr_t)(e0 / kQPer));
+}
+
+// The message table of the decode kernels, with the per-message checks.  Each message holds the
+// planes of elements [e0, e0 + len): a range of a chunked wire, or the whole buffer [0, n).
+static int qsgd_msgs(QMsgs& M, const uint8_t* const* packed_list, const float* const* norms_list,
+                     const float* weights, int32_t nmsg, int32_t self_slot, int cw, int64_t e0, int64_t len) {
+  for (int m = 0; m < nmsg; ++m) {
+    CHOCO_REQUIRE(packed_list[m] && norms_list[m], "null message pointer");
+    CHOCO_REQUIRE(aligned16(packed_list[m]), "packed messages must be 16-byte aligned");
+    range_planes(packed_list[m], e0, len, cw, &M.lvl[m], &M.sgn[m]);
+    M.norms[m] = norms_list[m];
+    M.w[m] = weights[m];
+  }
+  M.nmsg = nmsg;
+  M.self_slot = self_slot;
+  return CHOCO_OK;
 }
 
 CHOCO_API int choco_qsgd_compress(const float* x, const float* xhat, int64_t n, const int64_t* seg_off, int32_t nseg,
@@ -1204,29 +1147,14 @@ CHOCO_API int choco_qsgd_decompress_accumulate_range(const uint8_t* const* packe
                                                      float* memory, void* stream) {
   hipStream_t st = as_stream(stream);
   CHOCO_REQUIRE(packed_list && norms_list && weights && memory, "null pointer argument");
-  CHOCO_REQUIRE(nmsg >= 1 && nmsg <= kQMaxMsg, "nmsg must be in [1, %d]", kQMaxMsg);
-  CHOCO_REQUIRE(self_slot >= -1 && self_slot < nmsg, "bad self_slot");
+  CHOCO_TRY(check_msgs(nmsg, self_slot));
   CHOCO_REQUIRE(q >= 1 && q <= 16, "q must be in [1, 16]");
-  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
-  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
-  CHOCO_REQUIRE(aligned16(memory) && (!xhat_self || aligned16(xhat_self)), "buffers must be 16-byte aligned");
-  if (int rc = qsgd_range_ok(n, e0, e1)) return rc;
+  CHOCO_TRY(check_flat(n, seg_off, nseg, {memory, xhat_self}));
+  CHOCO_TRY(qsgd_range_ok(n, e0, e1));
   const int cw = container_bits(q);
   QMsgs M{};
-  for (int m = 0; m < nmsg; ++m) {
-    CHOCO_REQUIRE(packed_list[m] && norms_list[m], "null message pointer");
-    CHOCO_REQUIRE(aligned16(packed_list[m]), "packed messages must be 16-byte aligned");
-    range_planes(packed_list[m], e0, e1 - e0, cw, &M.lvl[m], &M.sgn[m]);
-    M.norms[m] = norms_list[m];
-    M.w[m] = weights[m];
-  }
-  M.nmsg = nmsg;
-  M.self_slot = self_slot;
-  profile_begin("qsgd_accumulate", st);
-  launch_decode_cw<1>(cw, M, n, seg_off, nseg, (1 << q) - 1, is_biased, xhat_self, memory, st, e0, e1);
-  profile_end("qsgd_accumulate", st);
-  CHOCO_LAUNCHED("qsgd_decode_kernel");
-  return CHOCO_OK;
+  CHOCO_TRY(qsgd_msgs(M, packed_list, norms_list, weights, nmsg, self_slot, cw, e0, e1 - e0));
+  return launch_decode<1>(cw, M, n, seg_off, nseg, (1 << q) - 1, is_biased, xhat_self, memory, st, e0, e1);
 }
 
 CHOCO_API int choco_qsgd_decode(const uint8_t* packed, const float* norms, int64_t n, const int64_t* seg_off,
@@ -1234,9 +1162,7 @@ CHOCO_API int choco_qsgd_decode(const uint8_t* packed, const float* norms, int64
   hipStream_t st = as_stream(stream);
   CHOCO_REQUIRE(packed && norms && out, "null pointer argument");
   CHOCO_REQUIRE(q >= 1 && q <= 16, "q must be in [1, 16]");
-  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
-  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
-  CHOCO_REQUIRE(aligned16(packed) && aligned16(out), "buffers must be 16-byte aligned");
+  CHOCO_TRY(check_flat(n, seg_off, nseg, {packed, out}));
   const int cw = container_bits(q);
   QMsgs M{};
   M.lvl[0] = packed;
@@ -1245,9 +1171,7 @@ CHOCO_API int choco_qsgd_decode(const uint8_t* packed, const float* norms, int64
   M.w[0] = 1.0f;
   M.nmsg = 1;
   M.self_slot = -1;
-  launch_decode_cw<0>(cw, M, n, seg_off, nseg, (1 << q) - 1, is_biased, out, nullptr, st);
-  CHOCO_LAUNCHED("qsgd_decode_kernel");
-  return CHOCO_OK;
+  return launch_decode<0>(cw, M, n, seg_off, nseg, (1 << q) - 1, is_biased, out, nullptr, st);
 }
 
 CHOCO_API int choco_qsgd_decompress_accumulate(const uint8_t* const* packed_list, const float* const* norms_list,
@@ -1256,29 +1180,13 @@ CHOCO_API int choco_qsgd_decompress_accumulate(const uint8_t* const* packed_list
                                                float* xhat_self, float* memory, void* stream) {
   hipStream_t st = as_stream(stream);
   CHOCO_REQUIRE(packed_list && norms_list && weights && memory, "null pointer argument");
-  CHOCO_REQUIRE(nmsg >= 1 && nmsg <= kQMaxMsg, "nmsg must be in [1, %d]", kQMaxMsg);
-  CHOCO_REQUIRE(self_slot >= -1 && self_slot < nmsg, "bad self_slot");
+  CHOCO_TRY(check_msgs(nmsg, self_slot));
   CHOCO_REQUIRE(q >= 1 && q <= 16, "q must be in [1, 16]");
-  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
-  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
-  CHOCO_REQUIRE(aligned16(memory) && (!xhat_self || aligned16(xhat_self)), "buffers must be 16-byte aligned");
+  CHOCO_TRY(check_flat(n, seg_off, nseg, {memory, xhat_self}));
   const int cw = container_bits(q);
   QMsgs M{};
-  for (int m = 0; m < nmsg; ++m) {
-    CHOCO_REQUIRE(packed_list[m] && norms_list[m], "null message pointer");
-    CHOCO_REQUIRE(aligned16(packed_list[m]), "packed messages must be 16-byte aligned");
-    M.lvl[m] = packed_list[m];
-    M.sgn[m] = packed_list[m] + plane_bytes(n, cw);
-    M.norms[m] = norms_list[m];
-    M.w[m] = weights[m];
-  }
-  M.nmsg = nmsg;
-  M.self_slot = self_slot;
-  profile_begin("qsgd_accumulate", st);
-  launch_decode_cw<1>(cw, M, n, seg_off, nseg, (1 << q) - 1, is_biased, xhat_self, memory, st);
-  profile_end("qsgd_accumulate", st);
-  CHOCO_LAUNCHED("qsgd_decode_kernel");
-  return CHOCO_OK;
+  CHOCO_TRY(qsgd_msgs(M, packed_list, norms_list, weights, nmsg, self_slot, cw, 0, n));
+  return launch_decode<1>(cw, M, n, seg_off, nseg, (1 << q) - 1, is_biased, xhat_self, memory, st);
 }
 
 CHOCO_API int choco_qsgd_recv_gossip_norms(const uint8_t* const* packed_list, const float* const* norms_list,
@@ -1288,37 +1196,25 @@ CHOCO_API int choco_qsgd_recv_gossip_norms(const uint8_t* const* packed_list, co
                                            float* norms_out, void* ws, size_t ws_bytes, void* stream) {
   hipStream_t st = as_stream(stream);
   CHOCO_REQUIRE(packed_list && norms_list && weights && x && memory && xhat && norms_out, "null pointer argument");
-  CHOCO_REQUIRE(nmsg >= 1 && nmsg <= kQMaxMsg, "nmsg must be in [1, %d]", kQMaxMsg);
-  CHOCO_REQUIRE(self_slot >= -1 && self_slot < nmsg, "bad self_slot");
+  CHOCO_TRY(check_msgs(nmsg, self_slot));
   CHOCO_REQUIRE(q >= 1 && q <= 16, "q must be in [1, 16]");
-  if (int rc = qsgd_check(x, xhat, n, seg_off, nseg)) return rc;
-  CHOCO_REQUIRE(aligned16(memory), "buffers must be 16-byte aligned");
+  CHOCO_TRY(check_flat(n, seg_off, nseg, {x, xhat, memory}));
   CHOCO_REQUIRE(ws && ws_bytes >= choco_qsgd_workspace_size(nseg), "qsgd workspace too small");
   const int cw = container_bits(q);
   QMsgs M{};
-  for (int m = 0; m < nmsg; ++m) {
-    CHOCO_REQUIRE(packed_list[m] && norms_list[m], "null message pointer");
-    CHOCO_REQUIRE(aligned16(packed_list[m]), "packed messages must be 16-byte aligned");
-    M.lvl[m] = packed_list[m];
-    M.sgn[m] = packed_list[m] + plane_bytes(n, cw);
-    M.norms[m] = norms_list[m];
-    M.w[m] = weights[m];
-  }
-  M.nmsg = nmsg;
-  M.self_slot = self_slot;
+  CHOCO_TRY(qsgd_msgs(M, packed_list, norms_list, weights, nmsg, self_slot, cw, 0, n));
   const int s_levels = (1 << q) - 1;
   QsgdWs* w = static_cast<QsgdWs*>(ws);
-  profile_begin("qsgd_recv_norm", st);
-  switch (cw) {
-    case 1: launch_recv_gossip<1>(M, n, seg_off, nseg, s_levels, is_biased, x, xhat, memory, gamma, w, norms_out, st); break;
-    case 2: launch_recv_gossip<2>(M, n, seg_off, nseg, s_levels, is_biased, x, xhat, memory, gamma, w, norms_out, st); break;
-    case 4: launch_recv_gossip<4>(M, n, seg_off, nseg, s_levels, is_biased, x, xhat, memory, gamma, w, norms_out, st); break;
-    case 8: launch_recv_gossip<8>(M, n, seg_off, nseg, s_levels, is_biased, x, xhat, memory, gamma, w, norms_out, st); break;
-    default: launch_recv_gossip<16>(M, n, seg_off, nseg, s_levels, is_biased, x, xhat, memory, gamma, w, norms_out, st); break;
-  }
-  profile_end("qsgd_recv_norm", st);
-  CHOCO_LAUNCHED("qsgd_recv_gossip_norm_kernel");
-  return CHOCO_OK;
+  const unsigned grid = (unsigned)((n + kRTile - 1) / kRTile);
+  return dispatch_width(cw, [&](auto CW) {
+    return dispatch_nmsg(nmsg, [&](auto NM) {
+      return dispatch_bool(nseg > 1, [&](auto SEG) {
+        return CHOCO_LAUNCH("qsgd_recv_norm", "qsgd_recv_gossip_norm_kernel",
+                            (qsgd_recv_gossip_norm_kernel<CW, NM, SEG>), dim3(grid), dim3(kQThreads), st, M, n,
+                            seg_off, nseg, s_levels, is_biased, x, xhat, memory, gamma, w, norms_out);
+      });
+    });
+  });
 }
 
 CHOCO_API int choco_qsgd_decompress_extrapolate(const uint8_t* packed, const float* norms, int64_t n,
@@ -1327,9 +1223,7 @@ CHOCO_API int choco_qsgd_decompress_extrapolate(const uint8_t* packed, const flo
   hipStream_t st = as_stream(stream);
   CHOCO_REQUIRE(packed && norms && target, "null pointer argument");
   CHOCO_REQUIRE(q >= 1 && q <= 16, "q must be in [1, 16]");
-  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
-  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
-  CHOCO_REQUIRE(aligned16(packed) && aligned16(target), "buffers must be 16-byte aligned");
+  CHOCO_TRY(check_flat(n, seg_off, nseg, {packed, target}));
   const int cw = container_bits(q);
   QMsgs M{};
   M.lvl[0] = packed;
@@ -1340,9 +1234,5 @@ CHOCO_API int choco_qsgd_decompress_extrapolate(const uint8_t* packed, const flo
   M.self_slot = -1;
   M.extrap = 1;
   M.a = a;
-  profile_begin("qsgd_accumulate", st);
-  launch_decode_cw<1>(cw, M, n, seg_off, nseg, (1 << q) - 1, is_biased, nullptr, target, st);
-  profile_end("qsgd_accumulate", st);
-  CHOCO_LAUNCHED("qsgd_decode_kernel");
-  return CHOCO_OK;
+  return launch_decode<1>(cw, M, n, seg_off, nseg, (1 << q) - 1, is_biased, nullptr, target, st);
 }

@@ -36,6 +36,7 @@
 // offset) -- no atomics (round 3's per-tile counters, one 128-B line each, took
 // 382 device-scope adders per line at 100M: 12-27 us).
 #include "choco_common.h"
+#include "dispatch.h"
 
 #include <algorithm>
 #include <mutex>
@@ -403,31 +404,15 @@ int randk_launch(const float* x, const float* xh, const int64_t* plan_dev, int64
   uint32_t* H = reinterpret_cast<uint32_t*>(static_cast<char*>(counts) + 256);
   uint32_t* P = reinterpret_cast<uint32_t*>(static_cast<char*>(counts) + 256 + align_up((size_t)R * kRkGroups * 4, 256));
   const bool flat = plan_dev == nullptr;
-  profile_begin("randk_count", st);
-  if (flat)
-    CHOCO_KLAUNCH((randk_count_kernel<true>), dim3((unsigned)R), dim3(kRkThreads), 0, st, plan_dev, rk_base, n, k,
-                  key, H, P);
-  else
-    CHOCO_KLAUNCH((randk_count_kernel<false>), dim3((unsigned)R), dim3(kRkThreads), 0, st, plan_dev, rk_base, n, k,
-                  key, H, P);
-  profile_end("randk_count", st);
-  CHOCO_LAUNCHED("randk_count_kernel");
-  profile_begin("randk_tile", st);
-  if (flat && xh)
-    CHOCO_KLAUNCH((randk_tile_kernel<true, true>), dim3((unsigned)(R * kRkQ)), dim3(kRkQThreads), 0, st, x, xh, plan_dev,
-                  rk_base, n, k, key, is_biased, H, P, out_val, out_idx);
-  else if (flat)
-    CHOCO_KLAUNCH((randk_tile_kernel<true, false>), dim3((unsigned)(R * kRkQ)), dim3(kRkQThreads), 0, st, x, xh, plan_dev,
-                  rk_base, n, k, key, is_biased, H, P, out_val, out_idx);
-  else if (xh)
-    CHOCO_KLAUNCH((randk_tile_kernel<false, true>), dim3((unsigned)(R * kRkQ)), dim3(kRkQThreads), 0, st, x, xh, plan_dev,
-                  rk_base, n, k, key, is_biased, H, P, out_val, out_idx);
-  else
-    CHOCO_KLAUNCH((randk_tile_kernel<false, false>), dim3((unsigned)(R * kRkQ)), dim3(kRkQThreads), 0, st, x, xh, plan_dev,
-                  rk_base, n, k, key, is_biased, H, P, out_val, out_idx);
-  profile_end("randk_tile", st);
-  CHOCO_LAUNCHED("randk_tile_kernel");
-  return CHOCO_OK;
+  return dispatch_bool(flat, [&](auto FLAT) {
+    CHOCO_TRY(CHOCO_LAUNCH("randk_count", "randk_count_kernel", (randk_count_kernel<FLAT>), dim3((unsigned)R),
+                           dim3(kRkThreads), st, plan_dev, rk_base, n, k, key, H, P));
+    return dispatch_bool(xh != nullptr, [&](auto XH) {
+      return CHOCO_LAUNCH("randk_tile", "randk_tile_kernel", (randk_tile_kernel<FLAT, XH>),
+                          dim3((unsigned)(R * kRkQ)), dim3(kRkQThreads), st, x, xh, plan_dev, rk_base, n, k, key,
+                          is_biased, H, P, out_val, out_idx);
+    });
+  });
 }
 
 }  // namespace choco

@@ -24,6 +24,7 @@
 // per segment inside the wave.  The last workgroup (agent-scope ticket)
 // rounds the sums to fp32 and zeroes the accumulators for the next call.
 #include "choco_common.h"
+#include "dispatch.h"
 
 #include <algorithm>
 
@@ -633,7 +634,6 @@ __global__ __launch_bounds__(kSignThreads) void sign_unpack_kernel(const uint32_
 }
 
 // Fused receiver update over up to 8 messages (CHOCOSignCompressor.uncompress).
-constexpr int kMaxMsg = 8;
 struct SignMsgs {
   const uint32_t* packed[kMaxMsg];
   const float* norms[kMaxMsg];
@@ -1331,34 +1331,26 @@ constexpr int kPackSmallGrid = 2048;
 // 26.7 us, fused step 100.8 -> 85.3, ResNet-50's fused step 104 -> 95.6
 constexpr int kPackRS = 2;
 template <bool XH, bool NORM, bool GS>
-static void launch_pack(bool one, unsigned grid, hipStream_t st, const float* x, const float* xhat, int64_t n,
-                        int64_t Np, const int64_t* seg_off, int32_t nseg, uint32_t* pk, float* l1, SignWs* w,
-                        Gossip gs, int64_t blk0, int finish) {
+static int launch_pack(bool one, unsigned grid, hipStream_t st, const float* x, const float* xhat, int64_t n,
+                       int64_t Np, const int64_t* seg_off, int32_t nseg, uint32_t* pk, float* l1, SignWs* w,
+                       Gossip gs, int64_t blk0, int finish) {
+  if (!one)  // the realigning kernel: the only pack for n >= 2^30
+    return CHOCO_LAUNCH("sign_pack", "sign_pack_kernel", (sign_pack_kernel<XH, NORM, GS>), dim3(grid),
+                        dim3(kSignThreads), st, x, xhat, n, Np, seg_off, nseg, pk, l1, w, gs, blk0, finish);
   // a grid of under kPackSmallGrid workgroups (the ~25M-element buffers of one model) splits each
   // column block's rows over two waves, and runs the fused step in groups of 4 rows: more
   // waves per CU instead of more rows in flight per wave
   const bool small = grid < (unsigned)kPackSmallGrid;
-  if (one && small && GS && NORM && nseg > 1)
-    CHOCO_KLAUNCH((sign_pack1_kernel<XH, NORM, GS, NORM, 4, kPackRS>), dim3(grid), dim3(kPackRS * kSignThreads), 0, st, x, xhat,
-                  n, Np, pk, l1, w, gs, blk0, finish, seg_off, nseg);
-  else if (one && small && GS)
-    CHOCO_KLAUNCH((sign_pack1_kernel<XH, NORM, GS, false, 4, kPackRS>), dim3(grid), dim3(kPackRS * kSignThreads), 0, st, x, xhat,
-                  n, Np, pk, l1, w, gs, blk0, finish, seg_off, nseg);
-  else if (one && small && NORM && nseg > 1)
-    CHOCO_KLAUNCH((sign_pack1_kernel<XH, NORM, GS, NORM, 0, kPackRS>), dim3(grid), dim3(kPackRS * kSignThreads), 0, st, x, xhat,
-                  n, Np, pk, l1, w, gs, blk0, finish, seg_off, nseg);
-  else if (one && small)
-    CHOCO_KLAUNCH((sign_pack1_kernel<XH, NORM, GS, false, 0, kPackRS>), dim3(grid), dim3(kPackRS * kSignThreads), 0, st, x, xhat,
-                  n, Np, pk, l1, w, gs, blk0, finish, seg_off, nseg);
-  else if (one && NORM && nseg > 1)
-    CHOCO_KLAUNCH((sign_pack1_kernel<XH, NORM, GS, NORM>), dim3(grid), dim3(kSignThreads), 0, st, x, xhat, n, Np, pk,
-                  l1, w, gs, blk0, finish, seg_off, nseg);
-  else if (one)
-    CHOCO_KLAUNCH((sign_pack1_kernel<XH, NORM, GS, false>), dim3(grid), dim3(kSignThreads), 0, st, x, xhat, n, Np, pk,
-                  l1, w, gs, blk0, finish, seg_off, nseg);
-  else
-    CHOCO_KLAUNCH((sign_pack_kernel<XH, NORM, GS>), dim3(grid), dim3(kSignThreads), 0, st, x, xhat, n, Np, seg_off,
-                  nseg, pk, l1, w, gs, blk0, finish);
+  return dispatch_bool(NORM && nseg > 1, [&](auto SEG) {  // per-tensor norms
+    auto pack1 = [&](auto RUV, auto RS) {
+      return CHOCO_LAUNCH("sign_pack", "sign_pack_kernel", (sign_pack1_kernel<XH, NORM, GS, NORM && SEG, RUV, RS>),
+                          dim3(grid), dim3(RS * kSignThreads), st, x, xhat, n, Np, pk, l1, w, gs, blk0, finish,
+                          seg_off, nseg);
+    };
+    if (small && GS) return pack1(int_c<4>{}, int_c<kPackRS>{});
+    if (small) return pack1(int_c<0>{}, int_c<kPackRS>{});
+    return pack1(int_c<0>{}, int_c<1>{});
+  });
 }
 
 // Packs words [w0, w1) (the whole buffer: 0, N').  The per-segment L1 sums of a range
@@ -1368,11 +1360,8 @@ static int sign_compress(const float* x, const float* xhat, int64_t n, const int
                          int32_t* packed, float* l1_norms, void* ws, size_t ws_bytes, hipStream_t st, Gossip gs,
                          int64_t w0 = 0, int64_t w1 = -1, bool finish = true) {
   CHOCO_REQUIRE(x && packed, "null pointer argument");
-  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
-  CHOCO_REQUIRE(aligned16(x) && (!xhat || aligned16(xhat)) && aligned16(packed),
-                "x/xhat/packed must be 16-byte aligned");
+  CHOCO_TRY(check_flat(n, seg_off, nseg, {x, xhat, packed}, "x/xhat/packed"));
   CHOCO_REQUIRE(!gs.mem || (xhat && aligned16(gs.mem)), "the gossip step needs x_hat and a 16-byte aligned memory");
-  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
   const int64_t Np = choco_sign_words(n);
   if (w1 < 0) w1 = Np;
   CHOCO_REQUIRE(w0 >= 0 && w0 < w1 && w1 <= Np && w0 % kSignCols == 0 && (w1 % kSignCols == 0 || w1 == Np),
@@ -1386,20 +1375,14 @@ static int sign_compress(const float* x, const float* xhat, int64_t n, const int
   }
   const bool one = n < (int64_t(1) << 30);  // the one-pass column kernel: buffer offsets, n * 4 < 2^32 bytes
   const int fin = finish ? 1 : 0;
-  profile_begin("sign_pack", st);
-  if (gs.mem) {
-    if (l1_norms) launch_pack<true, true, true>(one, grid, st, x, xhat, n, Np, seg_off, nseg, pk, l1_norms, w, gs, blk0, fin);
-    else launch_pack<true, false, true>(one, grid, st, x, xhat, n, Np, seg_off, nseg, pk, l1_norms, w, gs, blk0, fin);
-  } else if (xhat) {
-    if (l1_norms) launch_pack<true, true, false>(one, grid, st, x, xhat, n, Np, seg_off, nseg, pk, l1_norms, w, gs, blk0, fin);
-    else launch_pack<true, false, false>(one, grid, st, x, xhat, n, Np, seg_off, nseg, pk, l1_norms, w, gs, blk0, fin);
-  } else {
-    if (l1_norms) launch_pack<false, true, false>(one, grid, st, x, xhat, n, Np, seg_off, nseg, pk, l1_norms, w, gs, blk0, fin);
-    else launch_pack<false, false, false>(one, grid, st, x, xhat, n, Np, seg_off, nseg, pk, l1_norms, w, gs, blk0, fin);
-  }
-  profile_end("sign_pack", st);
-  CHOCO_LAUNCHED("sign_pack_kernel");
-  return CHOCO_OK;
+  return dispatch_bool(l1_norms != nullptr, [&](auto NORM) {
+    auto pack = [&](auto XH, auto GS) {
+      return launch_pack<XH, NORM, GS>(one, grid, st, x, xhat, n, Np, seg_off, nseg, pk, l1_norms, w, gs, blk0, fin);
+    };
+    if (gs.mem) return pack(std::true_type{}, std::true_type{});
+    if (xhat) return pack(std::true_type{}, std::false_type{});
+    return pack(std::false_type{}, std::false_type{});
+  });
 }
 
 CHOCO_API int choco_sign_compress(const float* x, const float* xhat, int64_t n, const int64_t* seg_off,
@@ -1439,9 +1422,21 @@ CHOCO_API int choco_sign_unpack(const int32_t* packed, int64_t n, float* out, vo
   CHOCO_REQUIRE(aligned16(out), "out must be 16-byte aligned");
   const int64_t Np = choco_sign_words(n);
   const unsigned grid = (unsigned)((Np + kSignCols - 1) / kSignCols);
-  CHOCO_KLAUNCH(sign_unpack_kernel, dim3(grid), dim3(kSignThreads), 0, st,
-                     reinterpret_cast<const uint32_t*>(packed), n, Np, out);
-  CHOCO_LAUNCHED("sign_unpack_kernel");
+  return CHOCO_LAUNCH(nullptr, "sign_unpack_kernel", sign_unpack_kernel, dim3(grid), dim3(kSignThreads), st,
+                      reinterpret_cast<const uint32_t*>(packed), n, Np, out);
+}
+
+// The message table of the accumulate kernels, with the per-message checks.
+static int sign_msgs(SignMsgs& M, const int32_t* const* packed_list, const float* const* norms_list,
+                     const float* weights, int32_t nmsg, int32_t self_slot) {
+  for (int q = 0; q < nmsg; ++q) {
+    CHOCO_REQUIRE(packed_list[q] && norms_list[q], "null message pointer");
+    M.packed[q] = reinterpret_cast<const uint32_t*>(packed_list[q]);
+    M.norms[q] = norms_list[q];
+    M.w[q] = weights[q];
+  }
+  M.nmsg = nmsg;
+  M.self_slot = self_slot;
   return CHOCO_OK;
 }
 
@@ -1453,56 +1448,20 @@ CHOCO_API int choco_sign_decompress_accumulate(const int32_t* const* packed_list
   (void)ws_bytes;
   hipStream_t st = as_stream(stream);
   CHOCO_REQUIRE(packed_list && norms_list && weights && memory, "null pointer argument");
-  CHOCO_REQUIRE(nmsg >= 1 && nmsg <= kMaxMsg, "nmsg must be in [1, %d]", kMaxMsg);
-  CHOCO_REQUIRE(self_slot >= -1 && self_slot < nmsg, "bad self_slot");
-  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
-  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
-  CHOCO_REQUIRE(aligned16(memory) && (!xhat_self || aligned16(xhat_self)), "buffers must be 16-byte aligned");
+  CHOCO_TRY(check_msgs(nmsg, self_slot));
+  CHOCO_TRY(check_flat(n, seg_off, nseg, {memory, xhat_self}));
   SignMsgs M{};
-  for (int q = 0; q < nmsg; ++q) {
-    CHOCO_REQUIRE(packed_list[q] && norms_list[q], "null message pointer");
-    M.packed[q] = reinterpret_cast<const uint32_t*>(packed_list[q]);
-    M.norms[q] = norms_list[q];
-    M.w[q] = weights[q];
-  }
-  M.nmsg = nmsg;
-  M.self_slot = self_slot;
+  CHOCO_TRY(sign_msgs(M, packed_list, norms_list, weights, nmsg, self_slot));
   const int64_t Np = choco_sign_words(n);
   const unsigned grid = sign_acc_grid(Np);
-  profile_begin("sign_accumulate", st);
-#define CHOCO_SIGN_ACC_L(NM, HS, NT)                                                                          \
-  CHOCO_KLAUNCH((sign_accumulate_kernel<NM, HS, NT>), dim3(grid), dim3(kSignThreads), 0, st, M, n, Np, seg_off, \
-                nseg, xhat_self, memory)
-#define CHOCO_SIGN_ACC(NM)                                       \
-  case NM:                                                       \
-    if (self_slot >= 0 && xhat_self) {                           \
-      if (nt)                                                    \
-        CHOCO_SIGN_ACC_L(NM, true, true);                        \
-      else                                                       \
-        CHOCO_SIGN_ACC_L(NM, true, false);                       \
-    } else {                                                     \
-      if (nt)                                                    \
-        CHOCO_SIGN_ACC_L(NM, false, true);                       \
-      else                                                       \
-        CHOCO_SIGN_ACC_L(NM, false, false);                      \
-    }                                                            \
-    break;
-  const bool nt = n >= kSaccNtMin;
-  switch (nmsg) {
-    CHOCO_SIGN_ACC(1)
-    CHOCO_SIGN_ACC(2)
-    CHOCO_SIGN_ACC(3)
-    CHOCO_SIGN_ACC(4)
-    CHOCO_SIGN_ACC(5)
-    CHOCO_SIGN_ACC(6)
-    CHOCO_SIGN_ACC(7)
-    CHOCO_SIGN_ACC(8)
-  }
-#undef CHOCO_SIGN_ACC
-#undef CHOCO_SIGN_ACC_L
-  profile_end("sign_accumulate", st);
-  CHOCO_LAUNCHED("sign_accumulate_kernel");
-  return CHOCO_OK;
+  return dispatch_nmsg(nmsg, [&](auto NM) {
+    return dispatch_bool(self_slot >= 0 && xhat_self, [&](auto HS) {
+      return dispatch_bool(n >= kSaccNtMin, [&](auto NT) {
+        return CHOCO_LAUNCH("sign_accumulate", "sign_accumulate_kernel", (sign_accumulate_kernel<NM, HS, NT>),
+                            dim3(grid), dim3(kSignThreads), st, M, n, Np, seg_off, nseg, xhat_self, memory);
+      });
+    });
+  });
 }
 
 // ticket block, kRowRep replicas of the per-segment fp64 L1 sums, then the bit planes of the
@@ -1526,12 +1485,8 @@ CHOCO_API int choco_sign_recv_gossip_compress(const int32_t* const* packed_list,
   hipStream_t st = as_stream(stream);
   CHOCO_REQUIRE(packed_list && norms_list && weights && x && memory && xhat && packed && l1_norms,
                 "null pointer argument");
-  CHOCO_REQUIRE(nmsg >= 1 && nmsg <= kMaxMsg, "nmsg must be in [1, %d]", kMaxMsg);
-  CHOCO_REQUIRE(self_slot >= -1 && self_slot < nmsg, "bad self_slot");
-  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
-  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
-  CHOCO_REQUIRE(aligned16(x) && aligned16(memory) && aligned16(xhat) && aligned16(packed),
-                "x/memory/xhat/packed must be 16-byte aligned");
+  CHOCO_TRY(check_msgs(nmsg, self_slot));
+  CHOCO_TRY(check_flat(n, seg_off, nseg, {x, memory, xhat, packed}, "x/memory/xhat/packed"));
   CHOCO_REQUIRE(ws && ws_bytes >= choco_sign_workspace_size(nseg), "sign workspace too small");
   {
     // the output words must not overlap any message's words (the row-run pass reads the
@@ -1573,50 +1528,22 @@ CHOCO_API int choco_sign_recv_gossip_compress(const int32_t* const* packed_list,
     M.norms[q] = norms_list[q];
     M.w[q] = weights[q];
   }
-  profile_begin("sign_planes", st);
-  CHOCO_KLAUNCH(sign_to_planes_kernel, dim3(gp, (unsigned)nmsg), dim3(kPlaneThreads), 0, st, S, Np);
-  profile_end("sign_planes", st);
-  CHOCO_LAUNCHED("sign_to_planes_kernel");
+  CHOCO_TRY(CHOCO_LAUNCH("sign_planes", "sign_to_planes_kernel", sign_to_planes_kernel, dim3(gp, (unsigned)nmsg),
+                         dim3(kPlaneThreads), st, S, Np));
   M.self_slot = self_slot;
   uint32_t* outp = reinterpret_cast<uint32_t*>(wb + (size_t)nmsg * pb);
   const unsigned grid = (unsigned)(32 * ((Np + kRowRun - 1) / kRowRun));  // one workgroup per run
-  profile_begin("sign_recv_pack", st);
-#define CHOCO_SRR_LAUNCH(NM, HS, SEG)                                                                    \
-  CHOCO_KLAUNCH((sign_recv_rows_kernel<NM, HS, SEG>), dim3(grid), dim3(kSignThreads), 0, st, M, x, xhat, memory, \
-                gamma, n, Np, seg_off, nseg, outp, l1_norms, w)
-#define CHOCO_SRR_CASE(NM)                         \
-  case NM:                                         \
-    if (nseg > 1) {                                \
-      if (self_slot >= 0)                          \
-        CHOCO_SRR_LAUNCH(NM, true, true);          \
-      else                                         \
-        CHOCO_SRR_LAUNCH(NM, false, true);         \
-    } else {                                       \
-      if (self_slot >= 0)                          \
-        CHOCO_SRR_LAUNCH(NM, true, false);         \
-      else                                         \
-        CHOCO_SRR_LAUNCH(NM, false, false);        \
-    }                                              \
-    break;
-  switch (nmsg) {
-    CHOCO_SRR_CASE(1)
-    CHOCO_SRR_CASE(2)
-    CHOCO_SRR_CASE(3)
-    CHOCO_SRR_CASE(4)
-    CHOCO_SRR_CASE(5)
-    CHOCO_SRR_CASE(6)
-    CHOCO_SRR_CASE(7)
-    CHOCO_SRR_CASE(8)
-  }
-#undef CHOCO_SRR_CASE
-#undef CHOCO_SRR_LAUNCH
-  profile_end("sign_recv_pack", st);
-  CHOCO_LAUNCHED("sign_recv_rows_kernel");
-  profile_begin("sign_planes", st);
-  CHOCO_KLAUNCH(sign_from_planes_kernel, dim3(gp), dim3(kPlaneThreads), 0, st, outp, Np, pk);
-  profile_end("sign_planes", st);
-  CHOCO_LAUNCHED("sign_from_planes_kernel");
-  return CHOCO_OK;
+  CHOCO_TRY(dispatch_nmsg(nmsg, [&](auto NM) {
+    return dispatch_bool(self_slot >= 0, [&](auto HS) {
+      return dispatch_bool(nseg > 1, [&](auto SEG) {
+        return CHOCO_LAUNCH("sign_recv_pack", "sign_recv_rows_kernel", (sign_recv_rows_kernel<NM, HS, SEG>),
+                            dim3(grid), dim3(kSignThreads), st, M, x, xhat, memory, gamma, n, Np, seg_off, nseg, outp,
+                            l1_norms, w);
+      });
+    });
+  }));
+  return CHOCO_LAUNCH("sign_planes", "sign_from_planes_kernel", sign_from_planes_kernel, dim3(gp),
+                      dim3(kPlaneThreads), st, outp, Np, pk);
 }
 
 CHOCO_API int choco_sign_decompress_axpy(const int32_t* const* packed_list, const float* const* norms_list,
@@ -1624,54 +1551,27 @@ CHOCO_API int choco_sign_decompress_axpy(const int32_t* const* packed_list, cons
                                          int32_t nseg, int32_t two_roundings, float* target, void* stream) {
   hipStream_t st = as_stream(stream);
   CHOCO_REQUIRE(packed_list && norms_list && weights && target, "null pointer argument");
-  CHOCO_REQUIRE(nmsg >= 1 && nmsg <= kMaxMsg, "nmsg must be in [1, %d]", kMaxMsg);
-  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
-  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
-  CHOCO_REQUIRE(aligned16(target), "target must be 16-byte aligned");
+  CHOCO_TRY(check_msgs(nmsg, -1));
+  CHOCO_TRY(check_flat(n, seg_off, nseg, {target}, "target"));
   SignMsgs M{};
-  for (int q = 0; q < nmsg; ++q) {
-    CHOCO_REQUIRE(packed_list[q] && norms_list[q], "null message pointer");
-    M.packed[q] = reinterpret_cast<const uint32_t*>(packed_list[q]);
-    M.norms[q] = norms_list[q];
-    M.w[q] = weights[q];
-  }
-  M.nmsg = nmsg;
-  M.self_slot = -1;
+  CHOCO_TRY(sign_msgs(M, packed_list, norms_list, weights, nmsg, -1));
   M.mode = two_roundings ? 1 : 0;
   const int64_t Np = choco_sign_words(n);
   const unsigned grid = sign_acc_grid(Np);
-  profile_begin("sign_accumulate", st);
-#define CHOCO_SIGN_AXPY(NM)                                                                                 \
-  case NM:                                                                                                  \
-    CHOCO_KLAUNCH((sign_accumulate_kernel<NM, false>), dim3(grid), dim3(kSignThreads), 0, st, M, n, Np, seg_off, \
-                  nseg, nullptr, target);                                                                   \
-    break;
-  switch (nmsg) {
-    CHOCO_SIGN_AXPY(1)
-    CHOCO_SIGN_AXPY(2)
-    CHOCO_SIGN_AXPY(3)
-    CHOCO_SIGN_AXPY(4)
-    CHOCO_SIGN_AXPY(5)
-    CHOCO_SIGN_AXPY(6)
-    CHOCO_SIGN_AXPY(7)
-    CHOCO_SIGN_AXPY(8)
-  }
-#undef CHOCO_SIGN_AXPY
-  profile_end("sign_accumulate", st);
-  CHOCO_LAUNCHED("sign_accumulate_kernel");
-  return CHOCO_OK;
+  return dispatch_nmsg(nmsg, [&](auto NM) {
+    return CHOCO_LAUNCH("sign_accumulate", "sign_accumulate_kernel", (sign_accumulate_kernel<NM, false>), dim3(grid),
+                        dim3(kSignThreads), st, M, n, Np, seg_off, nseg, nullptr, target);
+  });
 }
 
 CHOCO_API int choco_sign_local_decode(const float* x, int64_t n, const int64_t* seg_off, int32_t nseg,
                                       const float* norms, float* out, void* stream) {
   hipStream_t st = as_stream(stream);
   CHOCO_REQUIRE(x && norms && out, "null pointer argument");
-  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
-  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
+  CHOCO_TRY(check_flat(n, seg_off, nseg));
   const unsigned grid = (unsigned)((n + kLocalTile - 1) / kLocalTile);
-  CHOCO_KLAUNCH(sign_local_kernel, dim3(grid), dim3(kSignThreads), 0, st, x, n, seg_off, nseg, norms, out);
-  CHOCO_LAUNCHED("sign_local_kernel");
-  return CHOCO_OK;
+  return CHOCO_LAUNCH(nullptr, "sign_local_kernel", sign_local_kernel, dim3(grid), dim3(kSignThreads), st, x, n,
+                      seg_off, nseg, norms, out);
 }
 
 CHOCO_API int choco_sign_decompress_extrapolate(const int32_t* packed, const float* norms, int64_t n,
@@ -1679,9 +1579,7 @@ CHOCO_API int choco_sign_decompress_extrapolate(const int32_t* packed, const flo
                                                 void* stream) {
   hipStream_t st = as_stream(stream);
   CHOCO_REQUIRE(packed && norms && target, "null pointer argument");
-  CHOCO_REQUIRE(n > 0 && n < (int64_t)INT32_MAX, "n out of range");
-  CHOCO_REQUIRE(nseg >= 1 && (nseg == 1 || seg_off), "need seg_off for nseg > 1");
-  CHOCO_REQUIRE(aligned16(target), "target must be 16-byte aligned");
+  CHOCO_TRY(check_flat(n, seg_off, nseg, {target}, "target"));
   SignMsgs M{};
   M.packed[0] = reinterpret_cast<const uint32_t*>(packed);
   M.norms[0] = norms;
@@ -1693,10 +1591,6 @@ CHOCO_API int choco_sign_decompress_extrapolate(const int32_t* packed, const flo
   M.b = b;
   const int64_t Np = choco_sign_words(n);
   const unsigned grid = sign_acc_grid(Np);
-  profile_begin("sign_accumulate", st);
-  CHOCO_KLAUNCH((sign_accumulate_kernel<1, false>), dim3(grid), dim3(kSignThreads), 0, st, M, n, Np, seg_off, nseg,
-                nullptr, target);
-  profile_end("sign_accumulate", st);
-  CHOCO_LAUNCHED("sign_accumulate_kernel");
-  return CHOCO_OK;
+  return CHOCO_LAUNCH("sign_accumulate", "sign_accumulate_kernel", (sign_accumulate_kernel<1, false>), dim3(grid),
+                      dim3(kSignThreads), st, M, n, Np, seg_off, nseg, nullptr, target);
 }

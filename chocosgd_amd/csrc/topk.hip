@@ -201,7 +201,7 @@ __global__ __launch_bounds__(kExactThreads) void topk_exact_kernel(
     float scale, float* __restrict__ out_val, int32_t* __restrict__ out_idx, int64_t idx_base) {
   __shared__ ExactSmem sm;
   Src<MODE, XH> src{x, xh, seed};
-  block_topk_exact(src, n, k, scale, out_val, out_idx, idx_base, sm);
+  block_topk_exact<kExactThreads>(src, n, k, scale, out_val, out_idx, idx_base, sm);
 }
 
 // k >= n (ratio 0): every element, in index order -- a plain multi-workgroup copy.
@@ -1175,45 +1175,6 @@ struct FinSmem {
 };
 static_assert(kK2Target <= kK4Threads, "K34 keeps one tile per thread");
 
-// Over hist[1 << kSelBits] (ascending), the bin holding the rank-th largest
-// entry and the rank inside it -> out[0], out[1].  Every thread of the
-// kK4Threads workgroup calls it; ends with a barrier.
-CHOCO_DEV void block_find_rank8k(const uint32_t* hist, uint32_t rank, uint32_t* scratch, uint32_t* out) {
-  constexpr int per = (1 << kSelBits) / kK4Threads;
-  const int tid = threadIdx.x;
-  uint32_t hv[per];
-  uint32_t local = 0;
-#pragma unroll
-  for (int j = 0; j < per; ++j) {
-    hv[j] = hist[tid * per + j];
-    local += hv[j];
-  }
-  uint32_t total;
-  const uint32_t pre = block_excl_scan(local, scratch, &total);
-  const uint32_t above = total - pre - local;  // entries in bins above mine
-  if (above < rank && rank <= above + local) {
-    uint32_t acc = above;
-#pragma unroll
-    for (int j = per - 1; j >= 0; --j) {
-      if (acc < rank && rank <= acc + hv[j]) { out[0] = (uint32_t)(tid * per + j); out[1] = rank - acc; }
-      acc += hv[j];
-    }
-  }
-  __syncthreads();
-}
-
-// The same over hist[nbins], nbins <= kK4Threads: one bin per thread.
-CHOCO_DEV void block_find_rank1k(const uint32_t* hist, uint32_t nbins, uint32_t rank, uint32_t* scratch,
-                                  uint32_t* out) {
-  const int tid = threadIdx.x;
-  const uint32_t hv = (uint32_t)tid < nbins ? hist[tid] : 0u;
-  uint32_t total;
-  const uint32_t pre = block_excl_scan(hv, scratch, &total);
-  const uint32_t above = total - pre - hv;  // entries in bins above mine
-  if (above < rank && rank <= above + hv) { out[0] = (uint32_t)tid; out[1] = rank - above; }
-  __syncthreads();
-}
-
 // Emission: a batch is kEmitRows rows of kK4Threads candidate positions; in
 // row i thread t owns position p0 + i * kK4Threads + t, so every load and
 // store instruction is contiguous across the wave.
@@ -1570,8 +1531,12 @@ __global__ __launch_bounds__(kK4Threads) void topk_finish_kernel(
       }
       __syncthreads();
       STAMP(28000 + b, 2);
-      if (narrow) block_find_rank1k(fs.hist, dmask + 1, krem, fs.scratch, fs.bc + 5);
-      else block_find_rank8k(fs.hist, krem, fs.scratch, fs.bc + 5);
+      if (narrow) {
+        const uint32_t hv[1] = {(uint32_t)tid <= dmask ? fs.hist[tid] : 0u};
+        block_find_rank(hv, krem, fs.scratch, fs.bc + 5);
+      } else {
+        block_find_rank_in<(1 << kSelBits) / kK4Threads>(fs.hist, krem, fs.scratch, fs.bc + 5);
+      }
       STAMP(28000 + b, 3);
       prefix |= fs.bc[5] << dsh;
       krem = fs.bc[6];
@@ -1787,18 +1752,13 @@ static int launch_topk(const float* x, const float* xh, int64_t n, int64_t k, ui
   };
   if (k >= n) {
     const unsigned g = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
-    profile_begin("topk_all", st);
-    CHOCO_KLAUNCH((topk_all_kernel<XH>), dim3(g), dim3(256), 0, st, x, xh, n, scale, out_val, out_idx, idx_base);
-    profile_end("topk_all", st);
-    CHOCO_LAUNCHED("topk_all_kernel");
+    CHOCO_TRY(CHOCO_LAUNCH("topk_all", "topk_all_kernel", (topk_all_kernel<XH>), dim3(g), dim3(256), st, x, xh, n,
+                           scale, out_val, out_idx, idx_base));
     return fold_after();
   }
   if (n <= kSmallN) {
-    profile_begin("topk_exact", st);
-    CHOCO_KLAUNCH((topk_exact_kernel<MODE, XH>), dim3(1), dim3(kExactThreads), 0, st, x, xh, n, k,
-                       seed, scale, out_val, out_idx, idx_base);
-    profile_end("topk_exact", st);
-    CHOCO_LAUNCHED("topk_exact_kernel");
+    CHOCO_TRY(CHOCO_LAUNCH("topk_exact", "topk_exact_kernel", (topk_exact_kernel<MODE, XH>), dim3(1),
+                           dim3(kExactThreads), st, x, xh, n, k, seed, scale, out_val, out_idx, idx_base));
     return fold_after();
   }
   const TopkLayout L = topk_layout(n);
@@ -1845,29 +1805,19 @@ static int launch_topk(const float* x, const float* xh, int64_t n, int64_t k, ui
                       hipMemsetAsync(&ctrl->overflow[par], 0, sizeof(uint32_t), st) == hipSuccess,
                   "hipMemsetAsync failed");
   }
-  if (MODE == kData && !warm) {
-    profile_begin("topk_bounds", st);
-    CHOCO_KLAUNCH((topk_bounds_kernel<XH, GS>), dim3(1), dim3(kK1Threads), 0, st, x, xh, n, k, par,
-                  sample_ranks(n, k), ctrl, gs);
-    profile_end("topk_bounds", st);
-    CHOCO_LAUNCHED("topk_bounds_kernel");
-  }
-  profile_begin("topk_stream", st);
-  CHOCO_KLAUNCH((topk_stream_kernel<MODE, XH, GS>), dim3(L.nb), dim3(kK2Threads), 0, st, x, xh, n, k, L.tile, L.nb,
-                par, L.side_cap, seed, hs_lo, hs_hi, ctrl, cum, cntw, side, cval, cidx,
-                reinterpret_cast<uint32_t*>(base + L.off_tinfo), gs, sample_ranks(n, k),
-                (uint32_t)(MODE == kData && warm && !GS ? 1 : 0));
-  profile_end("topk_stream", st);
-  CHOCO_LAUNCHED("topk_stream_kernel");
-  profile_begin("topk_finish", st);
-  CHOCO_KLAUNCH((topk_finish_kernel<MODE, XH>), dim3(L.nb), dim3(kK4Threads), 0, st, x, xh, n, k, L.tile, L.nb,
-                L.side_cap, seed, scale, ctrl, cum, cntw, side, cval, cidx, out_val, out_idx, idx_base,
-                reinterpret_cast<WideCtrl*>(base + L.off_wide), reinterpret_cast<uint32_t*>(base + L.off_gcnt),
-                reinterpret_cast<uint32_t*>(base + L.off_thist), par, status.dev, status.host,
-                reinterpret_cast<const uint32_t*>(base + L.off_tinfo), fold, cold_host);
-  profile_end("topk_finish", st);
-  CHOCO_LAUNCHED("topk_finish_kernel");
-  return CHOCO_OK;
+  if (MODE == kData && !warm)
+    CHOCO_TRY(CHOCO_LAUNCH("topk_bounds", "topk_bounds_kernel", (topk_bounds_kernel<XH, GS>), dim3(1),
+                           dim3(kK1Threads), st, x, xh, n, k, par, sample_ranks(n, k), ctrl, gs));
+  CHOCO_TRY(CHOCO_LAUNCH("topk_stream", "topk_stream_kernel", (topk_stream_kernel<MODE, XH, GS>), dim3(L.nb),
+                         dim3(kK2Threads), st, x, xh, n, k, L.tile, L.nb, par, L.side_cap, seed, hs_lo, hs_hi, ctrl,
+                         cum, cntw, side, cval, cidx, reinterpret_cast<uint32_t*>(base + L.off_tinfo), gs,
+                         sample_ranks(n, k), (uint32_t)(MODE == kData && warm && !GS ? 1 : 0)));
+  return CHOCO_LAUNCH("topk_finish", "topk_finish_kernel", (topk_finish_kernel<MODE, XH>), dim3(L.nb),
+                      dim3(kK4Threads), st, x, xh, n, k, L.tile, L.nb, L.side_cap, seed, scale, ctrl, cum, cntw, side,
+                      cval, cidx, out_val, out_idx, idx_base, reinterpret_cast<WideCtrl*>(base + L.off_wide),
+                      reinterpret_cast<uint32_t*>(base + L.off_gcnt), reinterpret_cast<uint32_t*>(base + L.off_thist),
+                      par, status.dev, status.host, reinterpret_cast<const uint32_t*>(base + L.off_tinfo), fold,
+                      cold_host);
 }
 
 template <int MODE>

@@ -243,33 +243,10 @@ CHOCO_DEV void tile_load_gossip(const float* __restrict__ x, const float* __rest
 
 CHOCO_DEV int tile_elem(int r, int q) { return r * 4 * kSegThreads + 4 * (int)threadIdx.x + q; }
 
-// Over hist[kH] in LDS or global memory (ascending key order), the bin holding
-// the rank-th largest entry and the rank inside it -> out[0], out[1].  kBpt
-// consecutive bins per thread of the kSegThreads workgroup (hv[b] = bin kBpt*tid + b);
-// ends with a barrier.
+// kBpt consecutive bins of hist[kH] per thread of the kSegThreads workgroup (select.h's
+// rank search: hv[b] = bin kBpt * tid + b)
 constexpr int kBpt = kH / kSegThreads;
 static_assert(kBpt * kSegThreads == kH, "whole bins per thread");
-CHOCO_DEV void block_find_rank(const uint32_t (&hv)[kBpt], uint32_t rank, uint32_t* scratch, uint32_t* out) {
-  const int tid = threadIdx.x;
-  uint32_t local = 0;
-#pragma unroll
-  for (int b = 0; b < kBpt; ++b) local += hv[b];
-  uint32_t total;
-  const uint32_t pre = block_excl_scan(local, scratch, &total);
-  uint32_t above = total - pre - local;  // entries in bins above mine
-  if (above < rank && rank <= above + local) {
-#pragma unroll
-    for (int b = kBpt - 1; b >= 0; --b) {
-      if (above < rank && rank <= above + hv[b]) { out[0] = kBpt * tid + b; out[1] = rank - above; }
-      above += hv[b];
-    }
-  }
-  __syncthreads();
-}
-CHOCO_DEV void load_bins(const uint32_t* h, uint32_t (&hv)[kBpt]) {
-#pragma unroll
-  for (int b = 0; b < kBpt; ++b) hv[b] = h[kBpt * threadIdx.x + b];
-}
 
 // ---------------------------------------------------------------- S1: coarse histogram (cold)
 template <bool XH, bool GS = false>
@@ -581,35 +558,6 @@ constexpr int kH3 = 512;  // bits 8..0 (cold) / the low sh <= 9 bits of a window
 // a candidate, so the shared select reads the tiles' candidate lists only.
 enum SegMode { kSegSelect = 0, kSegMissed = 1, kSegAll = 2, kSegMissedHigh = 3 };
 
-// Over hist[nb] in global memory (ascending key order), the bin holding the
-// rank-th largest entry and the rank inside it -> out[0], out[1], and the
-// histogram total -> out[2]; PER bins per thread of a kS3Threads workgroup.
-// Ends with a barrier.
-template <int PER>
-CHOCO_DEV void block_find_rank_g(const uint32_t* __restrict__ hist, uint32_t rank, uint32_t* scratch, uint32_t* out) {
-  const int tid = threadIdx.x;
-  uint32_t hv[PER];
-  uint32_t local = 0;
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    hv[j] = hist[tid * PER + j];
-    local += hv[j];
-  }
-  uint32_t total;
-  const uint32_t pre = block_excl_scan(local, scratch, &total);
-  const uint32_t above = total - pre - local;  // entries in bins above mine
-  if (tid == 0) out[2] = total;
-  if (above < rank && rank <= above + local) {
-    uint32_t acc = above;
-#pragma unroll
-    for (int j = PER - 1; j >= 0; --j) {
-      if (acc < rank && rank <= acc + hv[j]) { out[0] = (uint32_t)(tid * PER + j); out[1] = rank - acc; }
-      acc += hv[j];
-    }
-  }
-  __syncthreads();
-}
-
 // (cold calls; warm calls take S3w + S4w below)
 __global__ __launch_bounds__(kS3Threads) void seg_fine_kernel(
     const int64_t* __restrict__ trows, int nseg, uint32_t* __restrict__ hist1, const uint32_t* __restrict__ hist2,
@@ -626,7 +574,7 @@ __global__ __launch_bounds__(kS3Threads) void seg_fine_kernel(
   if (tid < 4) bc[tid] = 0u;
   __syncthreads();
   const uint32_t b1 = info[8 * c.s + 0], rank = info[8 * c.s + 1];
-  block_find_rank_g<kH / kS3Threads>(hist2 + (int64_t)c.s * kH, rank, scratch, bc);
+  block_find_rank_in<kH / kS3Threads, true>(hist2 + (int64_t)c.s * kH, rank, scratch, bc);
   const uint32_t b2 = bc[0];
   if (c.j == 0 && tid == 0) {
     info[8 * c.s + 3] = b2;
@@ -686,16 +634,12 @@ CHOCO_DEV void seg_next_window_v(const uint32_t (&hv)[kWinPer], uint32_t base, u
   const int tid = threadIdx.x;
   const uint64_t delta = (uint64_t)(0.03 * (double)k + 4.0 * sqrt((double)k)) + 8u;
   const uint64_t lo_t = (uint64_t)k + delta, hi_t = (uint64_t)k > delta ? (uint64_t)k - delta : 0u;
-  uint32_t local = 0;
-#pragma unroll
-  for (int j = 0; j < PER; ++j) local += hv[j];
-  uint32_t total;
-  const uint32_t pre = block_excl_scan(local, scratch, &total);
+  const BinScan bs = block_bin_scan(hv, scratch);
   // C(j) = #keys >= base + (j << shb) = above + total - (keys in bins below j)
-  uint32_t nlo = 0, nhi = 0, below = pre;
+  uint32_t nlo = 0, nhi = 0, below = bs.pre;
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
-    const uint64_t C = (uint64_t)above + total - below;
+    const uint64_t C = (uint64_t)above + bs.total - below;
     nlo += C >= lo_t ? 1u : 0u;
     nhi += C > hi_t ? 1u : 0u;
     below += hv[j];
@@ -743,7 +687,7 @@ __global__ __launch_bounds__(kS3Threads) void seg_count_kernel(
   const int tid = threadIdx.x;
   const uint32_t cnt = tilecnt[blockIdx.x];
   const uint32_t b2 = info[8 * c.s + 3], kc = info[8 * c.s + 4], b1 = info[8 * c.s + 0];
-  block_find_rank_g<kH3 / kS3Threads>(hist3 + (int64_t)c.s * kH3, kc, scratch, bc);
+  block_find_rank_in<kH3 / kS3Threads, true>(hist3 + (int64_t)c.s * kH3, kc, scratch, bc);
   const uint32_t T = (b1 << 20) | (b2 << 9) | bc[0];
   if (c.j == 0) {
     if (tid == 0) {
@@ -805,28 +749,6 @@ __global__ __launch_bounds__(kS3Threads) void seg_count_kernel(
 // (info 3/4/6).  A tile with more than kTileList DISTINCT keys in bin b2 sends its
 // segment to S4w's exact select (not counted as a window miss).
 // Kept over the round-4 sequence S3a + S3b + S4 (same-box A/B, profiles/r05_ab_summary.txt).
-template <int PER>
-CHOCO_DEV void block_find_rank_v(const uint32_t (&hv)[PER], uint32_t rank, uint32_t* scratch, uint32_t* out) {
-  // block_find_rank_g over bins already in registers (hv[j] = bin tid * PER + j)
-  const int tid = threadIdx.x;
-  uint32_t local = 0;
-#pragma unroll
-  for (int j = 0; j < PER; ++j) local += hv[j];
-  uint32_t total;
-  const uint32_t pre = block_excl_scan(local, scratch, &total);
-  const uint32_t above = total - pre - local;
-  if (tid == 0) out[2] = total;
-  if (above < rank && rank <= above + local) {
-    uint32_t acc = above;
-#pragma unroll
-    for (int j = PER - 1; j >= 0; --j) {
-      if (acc < rank && rank <= acc + hv[j]) { out[0] = (uint32_t)(tid * PER + j); out[1] = rank - acc; }
-      acc += hv[j];
-    }
-  }
-  __syncthreads();
-}
-
 __global__ __launch_bounds__(kS3Threads) void seg_bin_kernel(
     const int64_t* __restrict__ trows, const uint32_t* __restrict__ hist2, uint32_t* __restrict__ info,
     const uint32_t* __restrict__ tilecnt, const float* __restrict__ cval, const SegWin* __restrict__ win,
@@ -856,7 +778,7 @@ __global__ __launch_bounds__(kS3Threads) void seg_bin_kernel(
   __syncthreads();
   const uint32_t lo = w.lo, sh = min(w.sh, kWinShMax);
   const uint32_t rank = (uint32_t)c.R.k;
-  block_find_rank_v<PER>(hv, rank, scratch, bc);
+  block_find_rank<true>(hv, rank, scratch, bc);
   const uint32_t b2 = bc[0];
   uint32_t mode = kSegSelect;
   if (c.R.k >= c.R.len) mode = kSegAll;
@@ -1202,7 +1124,7 @@ __global__ __launch_bounds__(kS4Threads, 7) void seg_emit_w_kernel(
       for (int i = 0; i < kTileList; ++i)
         if ((uint32_t)i < tn[q]) atomicAdd(&h3[(kk[q][i].x - lo) & fmask], kk[q][i].y);
     __syncthreads();
-    block_find_rank_g<kH3 / kS4Threads>(h3, rb, scratch, bc);
+    block_find_rank_in<kH3 / kS4Threads, true>(h3, rb, scratch, bc);
     T = lo + (b2 << sh) + bc[0];
     r = bc[1];
   }
@@ -1387,55 +1309,31 @@ static int launch_batched(const float* x, const float* xh, const int64_t* plan_d
   const int64_t* w2_order = plan_dev + rkb + 1 + 4 * plan_host[rkb];
   // the per-tile rows (after the dispatch records): S1 / S3 / S4 look their tile up in one round trip
   const int64_t* trows = plan_dev + rkb + 1 + 4 * plan_host[rkb] + 4 * (int64_t)ntile;
-  if (!warm) {
-    profile_begin("topk_seg_hist", st);
-    CHOCO_KLAUNCH((seg_hist_kernel<XH, GS>), dim3(ntile), dim3(kSegThreads), 0, st, x, xh, trows, nseg, W.hist1,
-                  gs);
-    profile_end("topk_seg_hist", st);
-    CHOCO_LAUNCHED("seg_hist_kernel");
-    profile_begin("topk_seg_collect", st);
-    CHOCO_KLAUNCH((seg_collect_kernel<XH, false, false>), dim3(ntile), dim3(kSegThreads), 0, st, x, xh, plan_dev,
-                  nseg, W.hist1, W.hist2, W.info, W.tilecnt, W.cval, W.cidx, W.win, Gossip{nullptr, 0.f}, out_val,
-                  out_idx, (int64_t)ntile, w2_order);
-  } else {
-    profile_begin("topk_seg_collect", st);
-    CHOCO_KLAUNCH((seg_collect_kernel<XH, true, GS>), dim3(ntile), dim3(kSegThreads), 0, st, x, xh, plan_dev, nseg,
-                  W.hist1, W.hist2, W.info, W.tilecnt, W.cval, W.cidx, W.win, gs, out_val, out_idx, (int64_t)ntile,
-                  w2_order);
-  }
-  profile_end("topk_seg_collect", st);
-  CHOCO_LAUNCHED("seg_collect_kernel");
   if (warm) {
-    profile_begin("topk_seg_bin", st);
-    CHOCO_KLAUNCH(seg_bin_kernel, dim3(ntile), dim3(kS3Threads), 0, st, trows, W.hist2, W.info, W.tilecnt, W.cval,
-                  W.win, W.tcount, W.blist);
-    profile_end("topk_seg_bin", st);
-    CHOCO_LAUNCHED("seg_bin_kernel");
-    profile_begin("topk_seg_emit", st);
-    CHOCO_KLAUNCH((seg_emit_w_kernel<XH>), dim3(ntile + (unsigned)nseg), dim3(kS4Threads), 0, st, x, xh, plan_dev,
-                  trows, (uint32_t)nseg, W.info, W.tilecnt, W.tcount, W.hist2, W.cval, W.cidx, out_val, out_idx, W.win, W.misses,
-                  W.miss_flag, W.blist, W.wide, W.wcnt, W.whist, W.status, W.host_status);
-    profile_end("topk_seg_emit", st);
-    CHOCO_LAUNCHED("seg_emit_w_kernel");
-    return CHOCO_OK;
+    CHOCO_TRY(CHOCO_LAUNCH("topk_seg_collect", "seg_collect_kernel", (seg_collect_kernel<XH, true, GS>), dim3(ntile),
+                           dim3(kSegThreads), st, x, xh, plan_dev, nseg, W.hist1, W.hist2, W.info, W.tilecnt, W.cval,
+                           W.cidx, W.win, gs, out_val, out_idx, (int64_t)ntile, w2_order));
+    CHOCO_TRY(CHOCO_LAUNCH("topk_seg_bin", "seg_bin_kernel", seg_bin_kernel, dim3(ntile), dim3(kS3Threads), st, trows,
+                           W.hist2, W.info, W.tilecnt, W.cval, W.win, W.tcount, W.blist));
+    return CHOCO_LAUNCH("topk_seg_emit", "seg_emit_w_kernel", (seg_emit_w_kernel<XH>), dim3(ntile + (unsigned)nseg),
+                        dim3(kS4Threads), st, x, xh, plan_dev, trows, (uint32_t)nseg, W.info, W.tilecnt, W.tcount,
+                        W.hist2, W.cval, W.cidx, out_val, out_idx, W.win, W.misses, W.miss_flag, W.blist, W.wide,
+                        W.wcnt, W.whist, W.status, W.host_status);
   }
-  // cold calls: S3a, S3b, S4
-  profile_begin("topk_seg_fine", st);
-  CHOCO_KLAUNCH(seg_fine_kernel, dim3(ntile), dim3(kS3Threads), 0, st, trows, nseg, W.hist1, W.hist2, W.hist3,
-                W.info, W.tilecnt, W.cval);
-  profile_end("topk_seg_fine", st);
-  CHOCO_LAUNCHED("seg_fine_kernel");
-  profile_begin("topk_seg_count", st);
-  CHOCO_KLAUNCH(seg_count_kernel, dim3(ntile), dim3(kS3Threads), 0, st, trows, nseg, W.hist2, W.hist3, W.info,
-                W.tilecnt, W.cval, W.tcount, W.win, W.shadow);
-  profile_end("topk_seg_count", st);
-  CHOCO_LAUNCHED("seg_count_kernel");
-  profile_begin("topk_seg_emit", st);
-  CHOCO_KLAUNCH(seg_emit_kernel, dim3(ntile), dim3(kS4Threads), 0, st, trows, W.info, W.tilecnt, W.tcount,
-                W.hist3, W.cval, W.cidx, out_val, out_idx, W.shadow, W.shadow_host);
-  profile_end("topk_seg_emit", st);
-  CHOCO_LAUNCHED("seg_emit_kernel");
-  return CHOCO_OK;
+  // cold calls: S1, S2, S3a, S3b, S4
+  CHOCO_TRY(CHOCO_LAUNCH("topk_seg_hist", "seg_hist_kernel", (seg_hist_kernel<XH, GS>), dim3(ntile),
+                         dim3(kSegThreads), st, x, xh, trows, nseg, W.hist1, gs));
+  CHOCO_TRY(CHOCO_LAUNCH("topk_seg_collect", "seg_collect_kernel", (seg_collect_kernel<XH, false, false>),
+                         dim3(ntile), dim3(kSegThreads), st, x, xh, plan_dev, nseg, W.hist1, W.hist2, W.info,
+                         W.tilecnt, W.cval, W.cidx, W.win, Gossip{nullptr, 0.f}, out_val, out_idx, (int64_t)ntile,
+                         w2_order));
+  CHOCO_TRY(CHOCO_LAUNCH("topk_seg_fine", "seg_fine_kernel", seg_fine_kernel, dim3(ntile), dim3(kS3Threads), st, trows,
+                         nseg, W.hist1, W.hist2, W.hist3, W.info, W.tilecnt, W.cval));
+  CHOCO_TRY(CHOCO_LAUNCH("topk_seg_count", "seg_count_kernel", seg_count_kernel, dim3(ntile), dim3(kS3Threads), st,
+                         trows, nseg, W.hist2, W.hist3, W.info, W.tilecnt, W.cval, W.tcount, W.win, W.shadow));
+  return CHOCO_LAUNCH("topk_seg_emit", "seg_emit_kernel", seg_emit_kernel, dim3(ntile), dim3(kS4Threads), st, trows,
+                      W.info, W.tilecnt, W.tcount, W.hist3, W.cval, W.cidx, out_val, out_idx, W.shadow,
+                      W.shadow_host);
 }
 
 // Segments over kSegBatchMax elements: one flat-pipeline workspace EACH (after the

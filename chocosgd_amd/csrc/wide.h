@@ -25,41 +25,6 @@ CHOCO_DEV uint32_t ld_sc1(const uint32_t* p) {
   return __hip_atomic_load(const_cast<uint32_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Over hist[2048] in LDS (ascending key order), the bins holding the r0-th and r1-th
-// largest entries and the ranks inside them -> out[0..1], out[2..3] (a rank of 0 is
-// skipped).  Every thread of the NT-thread workgroup calls it; 2048 / NT consecutive
-// bins per thread.
-template <int NT = 1024>
-CHOCO_DEV void block_find_two(const uint32_t* hist, uint32_t r0, uint32_t r1, uint32_t* scratch, uint32_t* out) {
-  constexpr int kB = 2048 / NT;
-  static_assert(kB * NT == 2048, "whole bins per thread");
-  const int tid = threadIdx.x;
-  uint32_t h[kB];
-  uint32_t local = 0;
-#pragma unroll
-  for (int b = 0; b < kB; ++b) {
-    h[b] = hist[kB * tid + b];
-    local += h[b];
-  }
-  uint32_t total;
-  const uint32_t pre = block_excl_scan(local, scratch, &total);
-  const uint32_t above0 = total - pre - local;  // entries in bins above mine
-  const uint32_t rs[2] = {r0, r1};
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const uint32_t r = rs[q];
-    if (r != 0u && above0 < r && r <= above0 + local) {
-      uint32_t above = above0;
-#pragma unroll
-      for (int b = kB - 1; b >= 0; --b) {
-        if (above < r && r <= above + h[b]) { out[2 * q] = kB * tid + b; out[2 * q + 1] = r - above; }
-        above += h[b];
-      }
-    }
-  }
-  __syncthreads();
-}
-
 // every wave's stores drained, the workgroup joined, one lane adds
 CHOCO_DEV void publish_add(uint32_t* counter) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
