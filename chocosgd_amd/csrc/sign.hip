@@ -1278,8 +1278,9 @@ __global__ __launch_bounds__(kSignThreads) void sign_recv_rows_kernel(PlaneMsgs 
 }
 
 // DeepSqueezeSignCompressor.compress's local copy of the message
-// (deep_squeeze.py:416-422): out = (norm_s * torch.sign(x)) / numel_s -- sign(0) = 0
-// and NaN stays NaN, unlike the wire's decode (zero encodes as "+").  One float4
+// (deep_squeeze.py:416-422): out = (norm_s * torch.sign(x)) / numel_s -- sign(+-0) = 0
+// and sign(NaN) = 0 as torch.sign gives them, unlike the wire's decode (zero encodes as
+// "+"); a NaN in x does not reach out, a NaN or infinite norm does.  One float4
 // per thread; the segment is found once per workgroup and walked per element only
 // when the workgroup straddles a boundary.
 constexpr int kLocalTile = kSignThreads * 4;
@@ -1307,7 +1308,7 @@ __global__ __launch_bounds__(kSignThreads) void sign_local_kernel(const float* _
       while (sgi + 1 < nseg && seg_off[sgi + 1] <= e) ++sgi;
     const int64_t numel = nseg > 1 ? seg_off[sgi + 1] - seg_off[sgi] : n;
     const float v = x[e];
-    const float sg = v > 0.f ? 1.0f : (v < 0.f ? -1.0f : (v == v ? 0.0f : v));  // torch.sign: NaN -> NaN
+    const float sg = v > 0.f ? 1.0f : (v < 0.f ? -1.0f : 0.0f);  // torch.sign: +-0 and NaN -> +0
     out[e] = (norms[sgi] * sg) / (float)numel;
   }
 }

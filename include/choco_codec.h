@@ -313,7 +313,8 @@ int choco_sign_decompress_extrapolate(const int32_t* packed, const float* norms,
                                       float* target, void* stream);
 
 /* DeepSqueezeSignCompressor.compress's local compressed copy (deep_squeeze.py:416-422):
- * out = (norms[s] * torch.sign(x)) / numel_s, sign(0) = 0, NaN stays NaN. */
+ * out = (norms[s] * torch.sign(x)) / numel_s with torch.sign's values: sign(+-0) = +0 and
+ * sign(NaN) = +0 (so out is 0 at a NaN of x), +-1 for infinities and subnormals. */
 int choco_sign_local_decode(const float* x, int64_t n, const int64_t* seg_off, int32_t nseg,
                             const float* norms, float* out, void* stream);
 

@@ -549,6 +549,44 @@ def test_oracle_sampled_helpers_agree_with_full_forms():
         assert np.array_equal(gl, levels[idx].astype(np.int64)) and np.array_equal(gn, neg[idx])
 
 
+@pytest.mark.parametrize("q", [1, 2, 3, 4, 5, 8, 9, 16])
+@pytest.mark.parametrize("n", [5, 8, 2049, 18_445])
+def test_oracle_qsgd_wire_round_trips_at_every_width(q, n):
+    """qsgd_pack -> qsgd_unpack gives back the levels and signs, and qsgd_wire_at reads the
+    same, at every q the receiver tests use -- the widths that do not fill their container
+    (3, 5, 9) included -- with levels 0 and 2^q - 1 present and a partial last group."""
+    s = 2 ** q - 1
+    rng = np.random.default_rng(1000 * q + n)
+    lvl = rng.integers(0, s + 1, size=n)
+    lvl[[0, n - 2]] = 0
+    lvl[[1, n - 1]] = s
+    d = rng.standard_normal(n).astype(np.float32)
+    packed = O.qsgd_pack(lvl.astype(np.float32), d, q)
+    cw = O.container_bits(q)
+    assert cw in (1, 2, 4, 8, 16) and q <= cw < 2 * q
+    assert packed.size == O.plane_bytes(n, cw) + O.plane_bytes(n, 1)
+    levels, neg = O.qsgd_unpack(packed, n, q)
+    assert np.array_equal(levels.astype(np.int64), lvl) and np.array_equal(neg, d < 0)
+    idx = np.unique(np.array([0, 1, 2, 3, 4, n // 2, n - 2, n - 1]))
+    gl, gn = O.qsgd_wire_at(packed, n, q, idx)
+    assert np.array_equal(gl, lvl[idx]) and np.array_equal(gn, neg[idx])
+
+
+def test_oracle_torch_sign_is_torch_sign():
+    """The oracle's torch_sign against the installed torch.sign on the values where sign
+    conventions differ: NaN and both zeros give +0 (so the reference's (norm * sign(x)) / numel
+    is 0 at a NaN), infinities and subnormals give +-1."""
+    import torch
+    x = np.array([np.nan, 0.0, -0.0, np.inf, -np.inf, 1e-41, -1e-41, 1.0, -1.0], dtype=np.float32)
+    want = np.array([0, 0, 0, 1, -1, 1, -1, 1, -1], dtype=np.float32)
+    got = torch.sign(torch.from_numpy(x)).numpy()
+    assert got.view(np.uint32).tolist() == want.view(np.uint32).tolist()
+    assert O.torch_sign(x).view(np.uint32).tolist() == got.view(np.uint32).tolist()
+    # torch's vectorised path (whole SIMD lanes) and its scalar tail give the same
+    big = np.tile(x, 37)
+    assert O.torch_sign(big).view(np.uint32).tolist() == torch.sign(torch.from_numpy(big)).numpy().view(np.uint32).tolist()
+
+
 def test_oracle_segmented_randk():
     lens = [3, 70, 5, 1000, 17]
     d = np.random.default_rng(1).standard_normal(sum(lens)).astype(np.float32)
