@@ -26,6 +26,7 @@ _pp = ctypes.POINTER(ctypes.c_void_p)
 _p_i64 = ctypes.POINTER(ctypes.c_int64)
 _p_f32 = ctypes.POINTER(ctypes.c_float)
 _p_i32 = ctypes.POINTER(ctypes.c_int32)
+_p_f64 = ctypes.POINTER(ctypes.c_double)
 
 # name -> (restype, argtypes); mirrors include/choco_codec.h one to one
 SIGNATURES = {
@@ -88,6 +89,9 @@ SIGNATURES = {
     "choco_params_launches": (_c_i32, [_c_i32]),
     "choco_params_pack": (_c_i32, [_pp, _p_i64, _p_i32, _c_i32, _vp, _c_i64, _vp]),
     "choco_params_unpack": (_c_i32, [_pp, _p_i64, _p_i32, _c_i32, _vp, _c_i64, _vp]),
+    "choco_params_sgd_launches": (_c_i32, [_c_i32]),
+    "choco_params_sgd": (_c_i32, [_pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64, _p_i32, _c_i32, _vp,
+                                  _c_i64, _c_i32, _vp]),
     "choco_gossip_topk_compress": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
     "choco_gossip_topk_compress_accumulate": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i64, _vp, _vp, _c_i32,
                                                        _c_f32, _vp, _c_sz, _vp]),

@@ -9,6 +9,7 @@ fallback anywhere in the product path.
 import ctypes
 import math
 import threading
+import weakref
 
 import torch
 
@@ -1025,6 +1026,110 @@ def params_unpack(flat, tensors):
     ptrs, lens, dts, nseg = _param_tables(tensors, flat)
     _lib.check(lib().choco_params_unpack(ptrs, lens, dts, nseg, _ptr(flat), flat.numel(), _stream(flat.device)),
                "choco_params_unpack")
+
+
+# ----------------------------------------------------------------------------- SGD update + pack
+SGD_F_NESTEROV, SGD_F_FIRST, SGD_F_NOGRAD = 1, 2, 4                    # CHOCO_SGD_F_*
+SGD_MODE_GRAD, SGD_MODE_WRITE_PARAMS, SGD_MODE_WRITE_GRADS = 1, 2, 4   # CHOCO_SGD_MODE_*
+
+
+def params_sgd_launches(nseg):
+    """Launches one params_sgd of `nseg` tensors takes."""
+    return int(lib().choco_params_sgd_launches(int(nseg)))
+
+
+class ParamSgdPlan:
+    """The host tables of choco_params_sgd for one parameter list, built once: lengths and
+    dtype codes are fixed; a step rewrites only what changes -- the data pointers
+    (`param_ptrs`, `grad_ptrs`, `buf_ptrs`), `flags` (SGD_F_*) and the hyperparameters
+    (`lr`, `weight_decay`, `momentum`, `dampening`, doubles) -- by index, then calls run().
+    Holds weak references to the parameters only."""
+
+    def __init__(self, params):
+        params = list(params)
+        if not params:
+            raise RuntimeError("ParamSgdPlan needs at least one parameter")
+        nseg = len(params)
+        self.nseg, self.device = nseg, params[0].device
+        self.param_ptrs, self.grad_ptrs, self.buf_ptrs = ((ctypes.c_void_p * nseg)() for _ in range(3))
+        self.lens, self.dts, self.flags = (ctypes.c_int64 * nseg)(), (ctypes.c_int32 * nseg)(), (ctypes.c_int32 * nseg)()
+        self.lr, self.weight_decay, self.momentum, self.dampening = ((ctypes.c_double * nseg)() for _ in range(4))
+        self.dtypes, self.numels = [], []
+        for i, p in enumerate(params):
+            _require(p, None, f"param {i}")
+            if p.device != self.device:
+                raise RuntimeError(f"param {i} is on {p.device}, param 0 on {self.device}")
+            code = PARAM_DTYPES.get(p.dtype)
+            if code is None:
+                raise RuntimeError(f"param {i} must be float32, bfloat16 or float16, got {p.dtype}")
+            self.lens[i], self.dts[i] = p.numel(), code
+            self.dtypes.append(p.dtype)
+            self.numels.append(p.numel())
+        self.n = sum(self.numels)
+        self.seen = [None] * nseg  # the hyperparameter tuple last written, per tensor
+        self._refs = [weakref.ref(p) for p in params]
+
+    def holds(self, params):
+        """Whether the plan was built for exactly these tensor objects."""
+        return len(params) == self.nseg and all(r() is p for r, p in zip(self._refs, params))
+
+    def fits(self, i, t):
+        """Whether tensor t can stand as the gradient or momentum buffer of parameter i."""
+        return (t.dtype == self.dtypes[i] and t.device == self.device and t.numel() == self.numels[i]
+                and t.is_contiguous())
+
+    def run(self, flat=None, grad_mode=False, write=True):
+        """One choco_params_sgd over the tables as they stand.  apply mode (grad_mode False):
+        write -> the params are updated; grad mode: write -> d_p goes into the grads' storage.
+        flat (fp32, n elements, or None) receives the new params / d_p in the same pass."""
+        if flat is not None:
+            _require(flat, torch.float32, "flat")
+            if flat.device != self.device or flat.numel() != self.n:
+                raise RuntimeError(f"flat must hold {self.n} elements on {self.device}")
+        mode = (SGD_MODE_GRAD | (SGD_MODE_WRITE_GRADS if write else 0)) if grad_mode else \
+            (SGD_MODE_WRITE_PARAMS if write else 0)
+        _lib.check(lib().choco_params_sgd(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts, self.lr,
+                                          self.weight_decay, self.momentum, self.dampening, self.flags, self.nseg,
+                                          _ptr(flat), self.n, mode, _stream(self.device)), "choco_params_sgd")
+
+
+def _per_tensor(v, nseg, name):
+    if isinstance(v, (list, tuple)):
+        if len(v) != nseg:
+            raise RuntimeError(f"{name}: {len(v)} values for {nseg} tensors")
+        return v
+    return [v] * nseg
+
+
+def params_sgd(params, grads, bufs, lr, weight_decay=0.0, momentum=0.0, dampening=0.0, nesterov=False, first=False,
+               flat=None, grad_mode=False, write=True, plan=None):
+    """apply_gradient (optim/utils.py:13-47) over a list of tensors in one batched launch per
+    chunk (include/choco_codec.h, choco_params_sgd).  grads[s] None: p.grad is None (apply mode:
+    the tensor is only packed into `flat`).  bufs[s]: the momentum buffer, written when
+    momentum != 0 and read unless first[s].  The hyperparameters, `nesterov` and `first` are
+    scalars or per-tensor lists.  Returns the plan (pass it back in to reuse its tables)."""
+    params = list(params)
+    nseg = len(params)
+    if plan is None:
+        plan = ParamSgdPlan(params)
+    elif not plan.holds(params):
+        raise RuntimeError("the plan was built for another parameter list")
+    cols = [_per_tensor(v, nseg, nm) for v, nm in ((grads, "grads"), (bufs, "bufs"), (lr, "lr"),
+                                                   (weight_decay, "weight_decay"), (momentum, "momentum"),
+                                                   (dampening, "dampening"), (nesterov, "nesterov"), (first, "first"))]
+    for i, (p, g, b, a, wd, mom, damp, nest, fst) in enumerate(zip(params, *cols)):
+        for t, nm in ((g, "grad"), (b, "buf")):
+            if t is not None and not plan.fits(i, t):
+                raise RuntimeError(f"{nm} {i} must match its parameter's dtype, device and size, and be contiguous")
+        plan.param_ptrs[i] = p.data_ptr()
+        plan.grad_ptrs[i] = g.data_ptr() if g is not None else None
+        plan.buf_ptrs[i] = b.data_ptr() if b is not None else None
+        plan.flags[i] = ((SGD_F_NESTEROV if nest else 0) | (SGD_F_FIRST if fst else 0)
+                         | (SGD_F_NOGRAD if g is None else 0))
+        plan.lr[i], plan.weight_decay[i], plan.momentum[i], plan.dampening[i] = a, wd, mom, damp
+        plan.seen[i] = None
+    plan.run(flat, grad_mode, write)
+    return plan
 
 
 # ----------------------------------------------------------------------------- profiling

@@ -1,0 +1,384 @@
+// apply_gradient (dl_code/pcode/optim/utils.py:13-47), the SGD update every optimizer of the
+// reference starts its step with, for a whole list of parameter tensors in one batched launch
+// per chunk, fused with the pack into the flat fp32 buffer (flatten(),
+// dl_code/pcode/utils/communication.py:58-76) that follows it in a CHOCO step.
+//
+// Per tensor s, element j, each line one reference op with one rounding:
+//     d = g
+//     if wd  != 0:  d   = fma(wd, p, d)                         d_p.add_(p, alpha=wd)
+//     if mom != 0:  t   = buf_in * mom                          buf.mul_(momentum)
+//                   buf = first ? fma(1, d, 0 * mom) : fma(1 - damp, d, t)
+//                   d   = nesterov ? fma(mom, buf, d) : buf
+//     apply mode:   p_new = fma(-lr, d, p)   -> params (optional), flat (optional)
+//     grad mode:    d                        -> grads (optional),  flat (optional)
+// `first`: the tensor has no momentum buffer yet; the reference builds it as
+// zeros.mul_(mom).add_(d_p), so buf_in is never read.  A skipped op (wd == 0, mom == 0) is
+// skipped, not run with a zero coefficient.  bf16 / fp16 tensors: every line is computed in
+// fp32 from the widened operands and narrowed round-to-nearest-even to the storage dtype after
+// that line (the scalars stay fp32); the flat value is the narrowed result widened again.
+// The arithmetic is written with fmaf / __fmul_rn: no contraction can merge the rounded
+// buf * mom into its neighbour.
+//
+// The launch has the parameter bridge's shape (params.hip): workgroups own 8192-element tiles
+// at absolute flat offsets, the table of a chunk of tensors travels in the kernel arguments
+// (scalar loads), the first tensor of a tile is found by the same uniform upper-bound search,
+// zero-length tensors are skipped.  A tensor whose p, g, buf and flat sides (those the update
+// touches) are all 16-byte aligned at group starts moves its whole groups as 16-byte vectors,
+// kSgdU groups in flight per thread, non-temporal, every load issued before the first store;
+// cut groups and every other tensor move element by element, coalesced.  A launch writes only
+// the bytes of its own elements.  g and buf of one tensor may be the same memory (the update
+// is elementwise; where both are written, d is stored last); distinct tensors must not
+// overlap, which is not checked.
+#include "param_common.h"
+
+#include <algorithm>
+
+namespace choco {
+
+constexpr int kSgdCap = 72;  // tensors per launch (ResNet-50's 161: three launches)
+constexpr int kSgdU = 1;     // 8-element groups in flight per thread: three operands each, and more
+                             // would take the fp32 build below the pack kernel's occupancy
+
+// flags of the table: the ABI's three bits, then what the host derives from the doubles
+constexpr uint32_t kSgdHasWd = 8u, kSgdHasMom = 16u;
+
+struct SgdTable {
+  void* p[kSgdCap];
+  void* g[kSgdCap];
+  void* buf[kSgdCap];
+  int64_t off[kSgdCap + 1];  // absolute flat offsets; off[nt] = end of the chunk
+  float wd[kSgdCap], mom[kSgdCap], omd[kSgdCap], nlr[kSgdCap];  // (float)wd, mom, 1 - damp, -lr
+  uint8_t dt[kSgdCap];       // CHOCO_DT_*
+  uint8_t fl[kSgdCap];       // CHOCO_SGD_F_* | kSgdHas*
+  int32_t nt;
+};
+// the table, the flat pointer and three words: a launch carries at most 4 KB of arguments
+static_assert(sizeof(SgdTable) + 24 <= 4096 - 256, "SgdTable must fit in the kernel arguments");
+
+// what one tensor's update needs (workgroup-uniform)
+struct SgdTensor {
+  void* p;
+  void* g;
+  void* buf;
+  float* flat;        // nullptr: no flat side
+  float wd, mom, omd, nlr;
+  bool has_wd, has_mom, nesterov, first;
+  bool rd_p, rd_g, rd_b;   // operands read
+  bool wr_p, wr_g, wr_b;   // tensors written (flat: flat != nullptr)
+  bool grad_mode, pack_only;
+};
+
+// The value as the storage dtype holds it.  v is the fp32 result of its line and is narrowed
+// from there (two roundings, as a torch op on a 16-bit tensor has): the empty asm keeps the
+// compiler from merging an fma and the conversion into one v_fma_mixlo_f16, which rounds the
+// exact sum straight to fp16.
+template <int DT>
+CHOCO_DEV float rnd(float v) {
+  if (DT == CHOCO_DT_F32) return v;
+  asm("" : "+v"(v));
+  return widen16<DT>(narrow16<DT>(v));
+}
+
+// one element; out = what goes to params / grads and to flat
+template <int DT>
+CHOCO_DEV void sgd_math(const SgdTensor& t, float p, float g, float b, float& buf_out, float& out) {
+  if (t.pack_only) {
+    out = p;
+    return;
+  }
+  float d = g;
+  if (t.has_wd) d = rnd<DT>(fmaf(t.wd, p, d));
+  if (t.has_mom) {
+    float nb;
+    if (t.first) {
+      nb = rnd<DT>(fmaf(1.0f, d, __fmul_rn(0.0f, t.mom)));
+    } else {
+      const float m = rnd<DT>(__fmul_rn(b, t.mom));
+      nb = rnd<DT>(fmaf(t.omd, d, m));
+    }
+    buf_out = nb;
+    d = t.nesterov ? rnd<DT>(fmaf(t.mom, nb, d)) : nb;
+  }
+  out = t.grad_mode ? d : rnd<DT>(fmaf(t.nlr, d, p));
+}
+
+template <int DT>
+CHOCO_DEV float ld1(const void* base, int64_t j) {
+  if (DT == CHOCO_DT_F32) return reinterpret_cast<const float*>(base)[j];
+  return widen16<DT>(reinterpret_cast<const unsigned short*>(base)[j]);
+}
+template <int DT>
+CHOCO_DEV void st1(void* base, int64_t j, float v) {
+  if (DT == CHOCO_DT_F32) reinterpret_cast<float*>(base)[j] = v;
+  else reinterpret_cast<unsigned short*>(base)[j] = narrow16<DT>(v);
+}
+
+// flat index i, element j of the tensor
+template <int DT>
+CHOCO_DEV void sgd_elem(const SgdTensor& t, int64_t i, int64_t j) {
+  const float p = t.rd_p ? ld1<DT>(t.p, j) : 0.0f;
+  const float g = t.rd_g ? ld1<DT>(t.g, j) : 0.0f;
+  const float b = t.rd_b ? ld1<DT>(t.buf, j) : 0.0f;
+  float nb = 0.0f, out;
+  sgd_math<DT>(t, p, g, b, nb, out);
+  if (t.wr_b) st1<DT>(t.buf, j, nb);
+  if (t.wr_p) st1<DT>(t.p, j, out);
+  if (t.wr_g) st1<DT>(t.g, j, out);
+  if (t.flat) t.flat[i] = out;
+}
+
+// a group of 8 elements as loaded: two float4 (fp32) or one 16-byte vector of halves
+struct Raw8 {
+  float4 lo, hi;
+  choco_u16x8 h;
+};
+template <int DT>
+CHOCO_DEV void ld8(Raw8& r, const void* base, int64_t j) {
+  if (DT == CHOCO_DT_F32) {
+    const float* s = reinterpret_cast<const float*>(base) + j;
+    r.lo = ld_nt4(s);
+    r.hi = ld_nt4(s + 4);
+  } else {
+    r.h = __builtin_nontemporal_load(
+        reinterpret_cast<const choco_u16x8*>(reinterpret_cast<const unsigned short*>(base) + j));
+  }
+}
+template <int DT>
+CHOCO_DEV void widen8(const Raw8& r, float (&v)[8]) {
+  if (DT == CHOCO_DT_F32) {
+    v[0] = r.lo.x; v[1] = r.lo.y; v[2] = r.lo.z; v[3] = r.lo.w;
+    v[4] = r.hi.x; v[5] = r.hi.y; v[6] = r.hi.z; v[7] = r.hi.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = widen16<DT>(r.h[k]);
+  }
+}
+template <int DT>
+CHOCO_DEV void st8(void* base, int64_t j, const float (&v)[8]) {
+  if (DT == CHOCO_DT_F32) {
+    float* s = reinterpret_cast<float*>(base) + j;
+    st_nt4(s, make_float4(v[0], v[1], v[2], v[3]));
+    st_nt4(s + 4, make_float4(v[4], v[5], v[6], v[7]));
+  } else {
+    choco_u16x8 o;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = narrow16<DT>(v[k]);
+    __builtin_nontemporal_store(o, reinterpret_cast<choco_u16x8*>(reinterpret_cast<unsigned short*>(base) + j));
+  }
+}
+
+// Flat elements [a, b) of a tensor at flat offset o0, a < b inside this workgroup's tile.
+// vec: every side the update touches is 16-byte aligned at every whole group's start.
+template <int DT>
+CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, bool vec) {
+  const int tid = threadIdx.x;
+  if (!vec) {
+    for (int64_t i = a + tid; i < b; i += kPbThreads) sgd_elem<DT>(t, i, i - o0);
+    return;
+  }
+  const int64_t g0 = a >> 3, g1 = (b - 1) >> 3;  // groups at absolute flat offsets, inclusive
+  for (int64_t gb = g0; gb <= g1; gb += (int64_t)kPbThreads * kSgdU) {
+    bool full[kSgdU];
+    Raw8 rp[kSgdU], rg[kSgdU], rb[kSgdU];
+    // every load of the thread's kSgdU groups is issued before the first store
+#pragma unroll
+    for (int u = 0; u < kSgdU; ++u) {
+      const int64_t e = (gb + u * kPbThreads + tid) * kPbGroup;
+      full[u] = e >= a && e + kPbGroup <= b;
+      if (full[u]) {
+        if (t.rd_p) ld8<DT>(rp[u], t.p, e - o0);
+        if (t.rd_g) ld8<DT>(rg[u], t.g, e - o0);
+        if (t.rd_b) ld8<DT>(rb[u], t.buf, e - o0);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kSgdU; ++u) {
+      const int64_t e = (gb + u * kPbThreads + tid) * kPbGroup;
+      if (full[u]) {
+        float p[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bi[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        float nb[8] = {0, 0, 0, 0, 0, 0, 0, 0}, out[8];
+        if (t.rd_p) widen8<DT>(rp[u], p);
+        if (t.rd_g) widen8<DT>(rg[u], g);
+        if (t.rd_b) widen8<DT>(rb[u], bi);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) sgd_math<DT>(t, p[k], g[k], bi[k], nb[k], out[k]);
+        if (t.wr_b) st8<DT>(t.buf, e - o0, nb);
+        if (t.wr_p) st8<DT>(t.p, e - o0, out);
+        if (t.wr_g) st8<DT>(t.g, e - o0, out);
+        if (t.flat) st8<CHOCO_DT_F32>(t.flat, e, out);
+      } else {
+        // a group cut by the tensor's start or end (or past the span): its own elements only
+        const int64_t ea = e > a ? e : a, eb = e + kPbGroup < b ? e + kPbGroup : b;
+        for (int64_t i = ea; i < eb; ++i) sgd_elem<DT>(t, i, i - o0);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb, float* flat, int64_t tile0,
+                                                               int32_t flat16, int32_t mode) {
+  const int nt = tb.nt;
+  const int64_t tile = tile0 + blockIdx.x;
+  const int64_t tlo = i64max(tile * kPbTile, tb.off[0]);
+  const int64_t thi = i64min((tile + 1) * kPbTile, tb.off[nt]);
+  if (tlo >= thi) return;
+  // the first s in [1, nt] with off[s] > tlo (off[nt] >= thi > tlo): tensor s - 1 holds tlo
+  int lo = 1, hi = nt;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (tb.off[mid] > tlo) hi = mid; else lo = mid + 1;
+  }
+  const bool grad_mode = (mode & CHOCO_SGD_MODE_GRAD) != 0;
+  for (int s = lo - 1; s < nt; ++s) {
+    const int64_t o0 = tb.off[s];
+    if (o0 >= thi) break;
+    const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);
+    if (a >= b) continue;  // zero-length tensor
+    const uint32_t fl = tb.fl[s];
+    const int dt = tb.dt[s];
+    SgdTensor t;
+    t.p = tb.p[s]; t.g = tb.g[s]; t.buf = tb.buf[s]; t.flat = flat;
+    t.wd = tb.wd[s]; t.mom = tb.mom[s]; t.omd = tb.omd[s]; t.nlr = tb.nlr[s];
+    t.pack_only = (fl & CHOCO_SGD_F_NOGRAD) != 0;
+    t.has_wd = (fl & kSgdHasWd) != 0;
+    t.has_mom = (fl & kSgdHasMom) != 0;
+    t.nesterov = (fl & CHOCO_SGD_F_NESTEROV) != 0;
+    t.first = (fl & CHOCO_SGD_F_FIRST) != 0;
+    t.grad_mode = grad_mode;
+    t.rd_p = t.pack_only || t.has_wd || !grad_mode;
+    t.rd_g = !t.pack_only;
+    t.rd_b = !t.pack_only && t.has_mom && !t.first;
+    t.wr_b = !t.pack_only && t.has_mom;
+    t.wr_p = !t.pack_only && !grad_mode && (mode & CHOCO_SGD_MODE_WRITE_PARAMS) != 0;
+    t.wr_g = !t.pack_only && grad_mode && (mode & CHOCO_SGD_MODE_WRITE_GRADS) != 0;
+    // flat + 4 e is 16-byte aligned at every group start e (a multiple of 8) when flat is; a
+    // tensor's side q + esz (e - o0) is when q - esz o0 is, esz e being a multiple of 16
+    const uintptr_t esz = dt == CHOCO_DT_F32 ? 4u : 2u, back = esz * (uintptr_t)o0;
+    uintptr_t mis = 0;
+    if (t.rd_p || t.wr_p) mis |= reinterpret_cast<uintptr_t>(t.p) - back;
+    if (t.rd_g || t.wr_g) mis |= reinterpret_cast<uintptr_t>(t.g) - back;
+    if (t.rd_b || t.wr_b) mis |= reinterpret_cast<uintptr_t>(t.buf) - back;
+    const bool vec = (flat == nullptr || flat16) && (mis & 15u) == 0;
+    if (dt == CHOCO_DT_F32) sgd_span<CHOCO_DT_F32>(t, o0, a, b, vec);
+    else if (dt == CHOCO_DT_BF16) sgd_span<CHOCO_DT_BF16>(t, o0, a, b, vec);
+    else sgd_span<CHOCO_DT_F16>(t, o0, a, b, vec);
+  }
+}
+
+static int sgd_launches(int32_t nseg) { return nseg <= 0 ? 0 : (nseg + kSgdCap - 1) / kSgdCap; }
+
+struct SgdArgs {
+  void* const* params;
+  const void* const* grads;
+  void* const* bufs;
+  const int64_t* lens;
+  const int32_t* dtypes;
+  const double* lr;
+  const double* wd;
+  const double* mom;
+  const double* damp;
+  const int32_t* flags;
+  int32_t nseg;
+  float* flat;
+  int64_t n;
+  int32_t mode;
+};
+
+static bool elem_aligned(const void* p, uintptr_t esz) { return (reinterpret_cast<uintptr_t>(p) & (esz - 1)) == 0; }
+
+// Every argument is checked before the first launch, with no HIP call.
+static int sgd_check(const SgdArgs& a) {
+  CHOCO_REQUIRE(a.params && a.grads && a.bufs && a.lens && a.dtypes && a.lr && a.wd && a.mom && a.damp && a.flags,
+                "null table argument");
+  CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
+  CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
+  constexpr int32_t kModes = CHOCO_SGD_MODE_GRAD | CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS;
+  CHOCO_REQUIRE((a.mode & ~kModes) == 0, "unknown mode bits 0x%x", (unsigned)a.mode);
+  const bool grad_mode = (a.mode & CHOCO_SGD_MODE_GRAD) != 0;
+  CHOCO_REQUIRE(!(grad_mode && (a.mode & CHOCO_SGD_MODE_WRITE_PARAMS)), "grad mode does not write the params");
+  CHOCO_REQUIRE(!(!grad_mode && (a.mode & CHOCO_SGD_MODE_WRITE_GRADS)), "apply mode does not write the grads");
+  CHOCO_REQUIRE(a.flat || (a.mode & (CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS)),
+                "nothing to write: flat is null and the mode writes neither params nor grads");
+  CHOCO_REQUIRE(aligned4(a.flat), "the flat buffer must be 4-byte aligned");
+  int64_t sum = 0;
+  for (int32_t s = 0; s < a.nseg; ++s) {
+    const int i = (int)s;
+    CHOCO_REQUIRE(a.lens[s] >= 0, "tensor %d: negative length", i);
+    CHOCO_REQUIRE(a.dtypes[s] >= CHOCO_DT_F32 && a.dtypes[s] <= CHOCO_DT_F16, "tensor %d: unknown dtype code %d", i,
+                  (int)a.dtypes[s]);
+    CHOCO_REQUIRE(a.lens[s] <= a.n - sum, "the lengths add up to more than n = %lld", (long long)a.n);
+    sum += a.lens[s];
+    constexpr int32_t kFlags = CHOCO_SGD_F_NESTEROV | CHOCO_SGD_F_FIRST | CHOCO_SGD_F_NOGRAD;
+    CHOCO_REQUIRE((a.flags[s] & ~kFlags) == 0, "tensor %d: unknown flag bits 0x%x", i, (unsigned)a.flags[s]);
+    const bool nograd = (a.flags[s] & CHOCO_SGD_F_NOGRAD) != 0;
+    CHOCO_REQUIRE(!(nograd && grad_mode), "tensor %d: a no-grad tensor in grad mode", i);
+    const uintptr_t esz = a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u;
+    CHOCO_REQUIRE(elem_aligned(a.params[s], esz) && elem_aligned(a.grads[s], esz) && elem_aligned(a.bufs[s], esz),
+                  "tensor %d: pointer not aligned to its element size", i);
+    if (!nograd) {
+      // the reference's constructors refuse these (torch.optim.SGD's rule)
+      CHOCO_REQUIRE(!((a.flags[s] & CHOCO_SGD_F_NESTEROV) && (!(a.mom[s] > 0.0) || a.damp[s] != 0.0)),
+                    "tensor %d: nesterov needs momentum > 0 and dampening == 0", i);
+    }
+    if (a.lens[s] == 0) continue;
+    CHOCO_REQUIRE(a.params[s], "tensor %d: null param pointer", i);
+    if (nograd) continue;
+    CHOCO_REQUIRE(a.grads[s], "tensor %d: null grad pointer without the no-grad flag", i);
+    CHOCO_REQUIRE(a.bufs[s] || a.mom[s] == 0.0, "tensor %d: null momentum buffer with momentum != 0", i);
+  }
+  CHOCO_REQUIRE(sum == a.n, "the lengths add up to %lld, n is %lld", (long long)sum, (long long)a.n);
+  return CHOCO_OK;
+}
+
+static int sgd_run(const SgdArgs& a, hipStream_t st) {
+  const int rc = sgd_check(a);
+  if (rc) return rc;
+  const int32_t flat16 = aligned16(a.flat) ? 1 : 0;
+  SgdTable tb;
+  int64_t base = 0;
+  for (int32_t s0 = 0; s0 < a.nseg; s0 += kSgdCap) {
+    const int nt = std::min<int32_t>(kSgdCap, a.nseg - s0);
+    tb.nt = nt;
+    tb.off[0] = base;
+    for (int i = 0; i < kSgdCap; ++i) {
+      const bool in = i < nt;
+      const int32_t s = s0 + i;
+      const bool upd = in && !(a.flags[s] & CHOCO_SGD_F_NOGRAD);
+      tb.p[i] = in ? a.params[s] : nullptr;
+      tb.g[i] = upd ? const_cast<void*>(a.grads[s]) : nullptr;
+      tb.buf[i] = upd ? a.bufs[s] : nullptr;
+      // torch's conversion of a Python scalar for an fp32 tensor
+      tb.wd[i] = upd ? (float)a.wd[s] : 0.0f;
+      tb.mom[i] = upd ? (float)a.mom[s] : 0.0f;
+      tb.omd[i] = upd ? (float)(1.0 - a.damp[s]) : 0.0f;
+      tb.nlr[i] = upd ? (float)(-a.lr[s]) : 0.0f;
+      tb.dt[i] = in ? (uint8_t)a.dtypes[s] : (uint8_t)0;
+      uint32_t fl = in ? (uint32_t)a.flags[s] : 0u;
+      if (upd && a.wd[s] != 0.0) fl |= kSgdHasWd;
+      if (upd && a.mom[s] != 0.0) fl |= kSgdHasMom;
+      tb.fl[i] = (uint8_t)fl;
+      base += in ? a.lens[s] : 0;
+      tb.off[i + 1] = base;
+    }
+    // the tiles the chunk [off[0], off[nt]) touches; an empty chunk still takes its launch
+    const int64_t tile0 = tb.off[0] / kPbTile;
+    const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
+    CHOCO_TRY(CHOCO_LAUNCH("param_sgd_kernel", "param_sgd_kernel", param_sgd_kernel, dim3((unsigned)tiles),
+                           dim3(kPbThreads), st, tb, a.flat, tile0, flat16, a.mode));
+  }
+  return CHOCO_OK;
+}
+
+}  // namespace choco
+
+using namespace choco;
+
+CHOCO_API int choco_params_sgd_launches(int32_t nseg) { return sgd_launches(nseg); }
+
+CHOCO_API int choco_params_sgd(void* const* params, const void* const* grads, void* const* bufs, const int64_t* lens,
+                               const int32_t* dtypes, const double* lr, const double* weight_decay,
+                               const double* momentum, const double* dampening, const int32_t* flags, int32_t nseg,
+                               float* flat, int64_t n, int32_t mode, void* stream) {
+  const SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, flat, n, mode};
+  return sgd_run(a, as_stream(stream));
+}

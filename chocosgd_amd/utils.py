@@ -1,14 +1,138 @@
-"""Gossip-step helpers: drop-in for the CHOCO half of dl_code/pcode/optim/utils.py."""
+"""Optimizer-step helpers: drop-in for dl_code/pcode/optim/utils.py (apply_gradient and the
+CHOCO half)."""
 import torch
 
 from . import codec
-from .tensor_buffer import TensorBuffer
+from .tensor_buffer import TensorBuffer, flatten
 
 
 def _get_data(param_groups, idx, is_get_grad):
     if is_get_grad:
         return param_groups[idx]["params"][0].grad
     return param_groups[idx]["params"][0]
+
+
+def apply_gradient_loop(param_groups, state, apply_grad_to_model=True):
+    """apply_gradient as one torch op per line and tensor (optim/utils.py:13-47): the path CPU
+    tensors, and anything the batched kernel does not take, keep.  Same results as the
+    reference, with the two differences apply_gradient documents."""
+    for group in param_groups:
+        weight_decay, momentum = group["weight_decay"], group["momentum"]
+        dampening, nesterov = group["dampening"], group["nesterov"]
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            d_p = p.grad.data
+            if weight_decay != 0:
+                d_p = d_p.add(p.data, alpha=weight_decay)  # out of place: p.grad keeps its values
+            if momentum != 0:
+                param_state = state[p]
+                if "momentum_buffer" not in param_state:
+                    buf = param_state["momentum_buffer"] = torch.zeros_like(p.data)
+                    buf.mul_(momentum).add_(d_p)
+                else:
+                    buf = param_state["momentum_buffer"]
+                    buf.mul_(momentum).add_(d_p, alpha=1 - dampening)
+                d_p = d_p.add(buf, alpha=momentum) if nesterov else buf
+            if apply_grad_to_model:
+                p.data.add_(d_p, alpha=-group["lr"])
+            else:
+                p.grad.data.copy_(d_p)  # into the grad's own storage: p.grad is not rebound
+
+
+_plans = {}  # id of a list's first parameter -> its ParamSgdPlan (which holds weak references only)
+
+
+def _sgd_plan(params):
+    """The cached plan of this parameter list, or None where the batched kernel does not take
+    it (CPU tensors, other dtypes, non-contiguous or several devices)."""
+    plan = _plans.get(id(params[0]))
+    if plan is not None and plan.holds(params):
+        return plan
+    dev = params[0].device
+    if not all(p.is_cuda and p.device == dev and p.dtype in codec.PARAM_DTYPES and p.is_contiguous()
+               for p in params):
+        return None
+    if len(_plans) >= 64:  # plans of parameter lists long gone
+        _plans.clear()
+    plan = _plans[id(params[0])] = codec.ParamSgdPlan(params)
+    return plan
+
+
+def _sgd_batched(entries, state, apply_grad_to_model, flat, write):
+    """One batched launch (per chunk) for `entries`, a list of (group, param) in flat order.
+    Returns False, with nothing changed, where a tensor cannot take it."""
+    if not entries:
+        return False
+    params = [p for _, p in entries]
+    plan = _sgd_plan(params)
+    if plan is None or (flat is not None and (flat.dtype != torch.float32 or flat.device != plan.device
+                                              or flat.numel() != plan.n or not flat.is_contiguous())):
+        return False
+    pp, gp, bp, flags, seen = plan.param_ptrs, plan.grad_ptrs, plan.buf_ptrs, plan.flags, plan.seen
+    created = []
+    ok = True
+    for i, (group, p) in enumerate(entries):
+        momentum = group["momentum"]
+        g = p.grad
+        if g is None:
+            if not apply_grad_to_model:  # the reference skips it; a flat gradient has no slot to skip
+                ok = False
+                break
+            pp[i], gp[i], bp[i], flags[i] = p.data_ptr(), None, None, codec.SGD_F_NOGRAD
+            continue
+        fl = codec.SGD_F_NESTEROV if group["nesterov"] else 0
+        b_ptr = None
+        if momentum != 0:
+            param_state = state[p]
+            buf = param_state.get("momentum_buffer")
+            if buf is None:  # written, not read, by its first step
+                buf = param_state["momentum_buffer"] = torch.zeros_like(p.data)
+                created.append(param_state)
+                fl |= codec.SGD_F_FIRST
+            if not plan.fits(i, buf):
+                ok = False
+                break
+            b_ptr = buf.data_ptr()
+        if not plan.fits(i, g):
+            ok = False
+            break
+        pp[i], gp[i], bp[i], flags[i] = p.data_ptr(), g.data_ptr(), b_ptr, fl
+        hp = (group["lr"], group["weight_decay"], momentum, group["dampening"])
+        if hp != seen[i]:
+            plan.lr[i], plan.weight_decay[i], plan.momentum[i], plan.dampening[i] = hp
+            seen[i] = hp
+    if not ok:
+        for param_state in created:
+            del param_state["momentum_buffer"]
+        return False
+    plan.run(flat, grad_mode=not apply_grad_to_model, write=write)
+    return True
+
+
+def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None):
+    """optim/utils.py:13-47: weight decay, momentum with dampening, optional Nesterov, then
+    p -= lr * d_p (apply_grad_to_model) or d_p left as the gradient.  Missing
+    state[p]["momentum_buffer"] entries are created.  fp32 / bf16 / fp16 ROCm tensors take ONE
+    batched HIP launch per chunk of tensors (codec.params_sgd); CPU tensors, and anything else,
+    the per-tensor loop above.
+
+    flat_out (a TensorBuffer or a flat fp32 tensor over every parameter, in group order): it
+    receives, in the same pass, the new parameters (what recover_params' flatten would build
+    next) or, with apply_grad_to_model=False, d_p (what get_data(is_get_grad=True) +
+    TensorBuffer would).
+
+    Two differences from the reference, by design: with apply_grad_to_model the grad tensors
+    are never written (the reference adds the weight decay into p.grad in place); without it
+    d_p is written into the existing grad tensors' storage and p.grad is not rebound to the
+    momentum buffer object."""
+    entries = [(group, p) for group in param_groups for p in group["params"]]
+    flat = getattr(flat_out, "buffer", flat_out)
+    if _sgd_batched(entries, state, apply_grad_to_model, flat, write=True):
+        return
+    apply_gradient_loop(param_groups, state, apply_grad_to_model)
+    if flat is not None:
+        flat.copy_(flatten([p.data if apply_grad_to_model else p.grad.data for _, p in entries], dtype=flat.dtype))
 
 
 def recover_params(param_groups, param_names, rank=None, neighbor_hat_params=None, get_hat_params=True):
@@ -32,7 +156,7 @@ def recover_params(param_groups, param_names, rank=None, neighbor_hat_params=Non
 
 
 def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_params, neighbors_info,
-               consensus_stepsize, rank, defer_receive=False):
+               consensus_stepsize, rank, defer_receive=False, state=None):
     """ParallelCHOCO_V.step after apply_gradient (parallel_choco_v.py:115-155), with the
     consensus step fused into the compressor's first pass: recover_params, then
     compress (x += gamma * (memory - x_hat_i) and d = x_new - x_hat_i in one pass), sync,
@@ -45,15 +169,34 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
     -- which touches x alone -- in between, parallel_choco_v.py:104-131).  x is the same
     after every step; x_hat / memory lag by one step until the next step or
     compressor.flush_receive() (call it before reading or saving them).  flatten_hat_params
-    is x_hat_i itself, not a copy (the pass updates it in place)."""
+    is x_hat_i itself, not a copy (the pass updates it in place).
+
+    state (optimizer.state; default None: the caller has run apply_gradient, as above): the
+    step runs apply_gradient itself, as the fused SGD + pack launch -- one pass that reads p,
+    g and the momentum buffer and writes the buffer and the flat x.  The launch does not write
+    the params (the unpack at the end writes them and nothing in between reads them) and
+    recover_params' pack is skipped.  Every group must hold one parameter, named in
+    param_names, as the reference's groups do."""
+    flatten_params = None
+    if state is not None:
+        flatten_params = _sgd_packed(param_groups, param_names, state)
     if defer_receive:
-        params, flatten_params = recover_params(param_groups, param_names, get_hat_params=False)
+        if flatten_params is None:
+            params, flatten_params = recover_params(param_groups, param_names, get_hat_params=False)
+        else:
+            params = [_get_data(param_groups, idx, False) for idx, _ in param_names]
         flatten_hat_params = neighbor_hat_params[rank]
     else:
         if hasattr(compressor, "flush_receive"):  # a receive an earlier deferred step left
             compressor.flush_receive()
-        params, flatten_params, flatten_hat_params = recover_params(param_groups, param_names, rank,
-                                                                    neighbor_hat_params, get_hat_params=True)
+        if flatten_params is None:
+            params, flatten_params, flatten_hat_params = recover_params(param_groups, param_names, rank,
+                                                                        neighbor_hat_params, get_hat_params=True)
+        else:
+            params = [_get_data(param_groups, idx, False) for idx, _ in param_names]
+            hat = torch.empty_like(flatten_params.buffer)
+            hat.copy_(neighbor_hat_params[rank].buffer)
+            flatten_hat_params = TensorBuffer.from_flat(hat, [p.size() for p in params])
     sync_buffer = {"original_shapes": shapes, "flatten_params": flatten_params,
                    "flatten_hat_params": flatten_hat_params,
                    "gossip": (neighbor_hat_params["memory"].buffer, consensus_stepsize)}
@@ -62,6 +205,22 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
     compressor.pipeline(sync_buffer, neighbor_hat_params, neighbors_info)
     flatten_params.unpack(params)
     return sync_buffer
+
+
+def _sgd_packed(param_groups, param_names, state):
+    """fused_step(state=...): apply_gradient and the pack of the new params in one launch.
+    Returns the flat TensorBuffer, or None after the per-tensor loop has updated the params
+    (tensors the batched kernel does not take: recover_params packs them as before)."""
+    if len(param_names) != len(param_groups) or any(len(g["params"]) != 1 for g in param_groups) \
+            or sorted(idx for idx, _ in param_names) != list(range(len(param_groups))):
+        raise RuntimeError("fused_step(state=...) needs one parameter per group, each named once in param_names")
+    entries = [(param_groups[idx], param_groups[idx]["params"][0]) for idx, _ in param_names]
+    dev = entries[0][1].device
+    flat = torch.empty(sum(p.numel() for _, p in entries), dtype=torch.float32, device=dev)
+    if dev.type == "cuda" and _sgd_batched(entries, state, True, flat, write=False):
+        return TensorBuffer.from_flat(flat, [p.size() for _, p in entries])
+    apply_gradient_loop(param_groups, state, True)
+    return None
 
 
 def update_params_from_neighbor(neighbor_hat_params, flatten_params, consensus_stepsize, self_rank):

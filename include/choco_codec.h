@@ -456,6 +456,65 @@ int choco_params_pack(const void* const* ptrs, const int64_t* lens, const int32_
 int choco_params_unpack(void* const* ptrs, const int64_t* lens, const int32_t* dtypes,
                         int32_t nseg, const float* flat, int64_t n, void* stream);
 
+/* ------------------------------------------- SGD update fused with the pack
+ * apply_gradient (pcode/optim/utils.py:13-47), the update every optimizer of the
+ * reference starts its step with, for a whole parameter list as ONE launch per chunk
+ * of tensors, optionally writing the flat fp32 buffer flatten() would build next in
+ * the same pass.  Tensor s holds lens[s] contiguous elements of dtype dtypes[s] in
+ * each of params[s], grads[s] and bufs[s] (its momentum buffer) and owns flat elements
+ * [sum(lens[0..s)), + lens[s]); sum(lens) must equal n.  Per element, every line one
+ * reference op with one rounding:
+ *     d = g
+ *     if weight_decay != 0:  d   = fma(wd, p, d)
+ *     if momentum != 0:      t   = buf * mom
+ *                            buf = FIRST ? fma(1, d, 0 * mom) : fma(1 - damp, d, t)
+ *                            d   = NESTEROV ? fma(mom, buf, d) : buf
+ *     apply mode:  p_new = fma(-lr, d, p)  -> params (WRITE_PARAMS), flat (if not NULL)
+ *     grad mode:   d                       -> grads  (WRITE_GRADS),  flat (if not NULL)
+ * with the scalars converted as torch converts a Python scalar for an fp32 tensor:
+ * (float)wd, (float)mom, (float)(1.0 - dampening), (float)(-lr).  A skipped op
+ * (weight_decay == 0, momentum == 0, tested on the doubles) is skipped, not run with a
+ * zero coefficient.  fp32 tensors match the reference bit for bit.  bf16 / fp16
+ * tensors: every line is computed in fp32 from the widened operands and narrowed
+ * round-to-nearest-even to the tensor's dtype after that line; the scalars stay fp32;
+ * the flat value is the narrowed result widened again.  buf is written whenever
+ * momentum != 0.
+ *   flags[s]: CHOCO_SGD_F_NESTEROV; CHOCO_SGD_F_FIRST: the tensor has no momentum
+ *     buffer yet (the reference builds it as zeros.mul_(mom).add_(d_p)): bufs[s] is
+ *     written and never read; CHOCO_SGD_F_NOGRAD (p.grad is None): in apply mode a pure
+ *     pack, flat = p and nothing else written; grads[s] and bufs[s] are ignored.
+ *   mode: CHOCO_SGD_MODE_APPLY or CHOCO_SGD_MODE_GRAD, | CHOCO_SGD_MODE_WRITE_PARAMS
+ *     (apply mode only) | CHOCO_SGD_MODE_WRITE_GRADS (grad mode only).
+ * All tables are HOST arrays copied into the kernel arguments (nothing allocated or
+ * synchronised); the pointers in them are DEVICE pointers.  grads[s] and bufs[s] of one
+ * tensor may be the same memory (where both are written, d is stored last).  Distinct
+ * tensors, and the flat buffer, must not overlap: this is NOT checked.  Only the bytes
+ * of the layout's own elements are written; pointers need their element's alignment
+ * only.  Zero-length tensors are allowed (their pointers may be NULL).  Every argument
+ * is checked before the first launch without a HIP call -- null tables, nseg <= 0,
+ * negative or oversumming lengths, lengths that do not sum to n, unknown dtype, flag or
+ * mode bits, misaligned pointers, a NULL param, a NULL grad without NOGRAD, a NULL buf
+ * with momentum != 0, NESTEROV with momentum <= 0 or dampening != 0 (the reference's
+ * constructors refuse it), NOGRAD in grad mode, flat == NULL with nothing else to
+ * write -- and a bad one returns CHOCO_ERR_INVALID and launches nothing.  A layout
+ * takes choco_params_sgd_launches(nseg) launches of "param_sgd_kernel". */
+#define CHOCO_SGD_F_NESTEROV 1
+#define CHOCO_SGD_F_FIRST 2
+#define CHOCO_SGD_F_NOGRAD 4
+#define CHOCO_SGD_MODE_APPLY 0
+#define CHOCO_SGD_MODE_GRAD 1
+#define CHOCO_SGD_MODE_WRITE_PARAMS 2
+#define CHOCO_SGD_MODE_WRITE_GRADS 4
+/* launches an update of nseg tensors takes (pcode/optim/utils.py:13-47 is one loop
+ * over them; host only); 0 for nseg <= 0 */
+int choco_params_sgd_launches(int32_t nseg);
+/* pcode/optim/utils.py:13-47 */
+int choco_params_sgd(void* const* params, const void* const* grads, void* const* bufs,
+                     const int64_t* lens, const int32_t* dtypes, const double* lr,
+                     const double* weight_decay, const double* momentum, const double* dampening,
+                     const int32_t* flags, int32_t nseg, float* flat, int64_t n, int32_t mode,
+                     void* stream);
+
 /* ------------------------------------------- fused gossip step + compress
  * ParallelCHOCO_V.step's update_params_from_neighbor -> compress sequence
  * (pcode/optim/parallel_choco_v.py:116-142 -> :229-240, optim/utils.py:67-72) in

@@ -1,0 +1,238 @@
+"""Cost of the optimizer update in front of a CHOCO step, and its parity with torch's own ops.
+
+    python tools/param_sgd_probe.py [--out FILE] [--steps 100] [--reps 5]
+
+Timing rows (one JSON line per layout: ResNet-50 in fp32 and in bf16, 3000 tensors of 100
+elements; each parameter its own allocation; weight decay + momentum, no Nesterov):
+  (a) loop_*    what runs without the batched kernel: apply_gradient as one torch op per line
+                and tensor (written out below with torch alone, so that any commit of this
+                repository can run it), then utils.recover_params(get_hat_params=False)
+  (b) fused_*   utils.apply_gradient(..., flat_out=flat): the update and the pack in one launch
+                per chunk of tensors
+  host_us       host wall time per step: `steps` steps queued, one synchronise, divided
+  gpu_us        the same window between two device events
+  launches      device activities (kernels + copies) of one step, from torch.profiler
+  kernel_us_*, kernel_tbps_*   dispatch-attached time of param_sgd_kernel (in (b)) and of
+                param_pack_kernel (in (a)), and the bytes each moves divided by it
+(medians over `reps` windows after a warm-up window).
+
+Parity rows: elements of p, buf and flat on which three steps of the kernel differ from the
+same three steps of torch's own op sequence on the device, per dtype, on the fixture layout
+(tests/golden/sgd_inputs.npz) and on one tensor of 2^20 elements.
+"""
+import argparse
+import collections
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from chocosgd_amd import codec, utils  # noqa: E402
+
+DEV = "cuda"
+HP = {"lr": 0.1, "weight_decay": 1e-4, "momentum": 0.9, "dampening": 0.0, "nesterov": False}
+
+
+def torch_loop(groups, state):
+    """apply_gradient (apply mode) as torch runs it: in-place ops, one launch each."""
+    for group in groups:
+        wd, mom, damp = group["weight_decay"], group["momentum"], group["dampening"]
+        for p in group["params"]:
+            d_p = p.grad.data
+            if wd != 0:
+                d_p.add_(p.data, alpha=wd)
+            if mom != 0:
+                st = state[p]
+                if "momentum_buffer" not in st:
+                    buf = st["momentum_buffer"] = torch.zeros_like(p.data)
+                    buf.mul_(mom).add_(d_p)
+                else:
+                    buf = st["momentum_buffer"]
+                    buf.mul_(mom).add_(d_p, alpha=1 - damp)
+                d_p = d_p.add(buf, alpha=mom) if group["nesterov"] else buf
+            p.data.add_(d_p, alpha=-group["lr"])
+
+
+def layouts():
+    with open(os.path.join(ROOT, "tests", "golden", "layouts.json")) as f:
+        r50 = json.load(f)["resnet50_imagenet"]
+    return [("resnet50_fp32", r50, torch.float32), ("resnet50_bf16", r50, torch.bfloat16),
+            ("t3000x100_fp32", [100] * 3000, torch.float32)]
+
+
+def events(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e6, a.elapsed_time(b) / iters * 1e3
+
+
+def median_of(fn, iters, reps):
+    events(fn, max(2, iters // 10))  # warm-up: code objects, the allocator's blocks, first-step buffers
+    runs = [events(fn, iters) for _ in range(reps)]
+    return statistics.median(r[0] for r in runs), statistics.median(r[1] for r in runs)
+
+
+def count_launches(fn):
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    try:
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        cnt = sum(1 for e in prof.events() if str(e.device_type).endswith("CUDA"))
+    except Exception as e:  # noqa: BLE001
+        print(f"launch count not measured: {e}", file=sys.stderr)
+        return None
+    return cnt or None
+
+
+def kernel_time(fn, name, iters=20):
+    """Dispatch-attached time of kernel `name` per call of fn (us, all its launches summed)."""
+    codec.profile_reset()
+    codec.profile_filter([name])
+    codec.profile_enable(True)
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    codec.profile_enable(False)
+    t, c = codec.profile_read(name)
+    codec.profile_filter(None)
+    codec.profile_reset()
+    return (t / iters * 1e3, c // iters) if c else (None, 0)
+
+
+def model(lens, dtype, seed=0):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    params = [torch.nn.Parameter(torch.randn(m, generator=g, device=DEV).to(dtype)) for m in lens]
+    for p in params:
+        p.grad = (0.01 * torch.randn(p.shape, generator=g, device=DEV)).to(dtype)
+    groups = [dict(HP, params=[p], name=f"p{i}") for i, p in enumerate(params)]
+    return params, groups, list(enumerate(gr["name"] for gr in groups))
+
+
+def measure(name, lens, dtype, steps, reps):
+    n, esz = sum(lens), torch.empty(0, dtype=dtype).element_size()
+    pa, ga, na = model(lens, dtype)
+    sa = collections.defaultdict(dict)
+
+    def loop_step():
+        torch_loop(ga, sa)
+        utils.recover_params(ga, na, get_hat_params=False)
+
+    pb, gb, _ = model(lens, dtype)
+    sb = collections.defaultdict(dict)
+    flat = torch.empty(n, device=DEV)
+
+    def fused_step():
+        utils.apply_gradient(gb, sb, flat_out=flat)
+
+    loop_host, loop_gpu = median_of(loop_step, steps, reps)
+    fused_host, fused_gpu = median_of(fused_step, steps, reps)
+    sgd_bytes = n * (5 * esz + 4)   # reads p, g, buf; writes buf, p and the fp32 flat
+    pack_bytes = n * (esz + 4)
+    k_sgd, l_sgd = kernel_time(fused_step, "param_sgd_kernel")
+    k_pack, l_pack = kernel_time(loop_step, "param_pack_kernel")
+    row = {"layout": name, "tensors": len(lens), "elements": n, "param_dtype": str(dtype).split(".")[-1],
+           "steps": steps, "reps": reps,
+           "loop_host_us": round(loop_host, 1), "loop_gpu_us": round(loop_gpu, 1), "loop_launches": count_launches(loop_step),
+           "fused_host_us": round(fused_host, 1), "fused_gpu_us": round(fused_gpu, 1),
+           "fused_launches": count_launches(fused_step), "sgd_bytes": sgd_bytes, "pack_bytes": pack_bytes}
+    if k_sgd:
+        row.update(kernel_us_sgd=round(k_sgd, 2), kernel_launches_sgd=l_sgd,
+                   kernel_tbps_sgd=round(sgd_bytes / k_sgd / 1e6, 3))
+    if k_pack:
+        row.update(kernel_us_pack=round(k_pack, 2), kernel_launches_pack=l_pack,
+                   kernel_tbps_pack=round(pack_bytes / k_pack / 1e6, 3))
+    return row
+
+
+def _differ(a, b):
+    a, b = a.float().reshape(-1), b.float().reshape(-1)
+    same = (a.view(torch.int32) == b.view(torch.int32)) | (torch.isnan(a) & torch.isnan(b))
+    return int((~same).sum().item())
+
+
+def parity(name, p0, gs, lens, dtype):
+    """Three steps of the kernel against three steps of torch's ops, from the same inputs."""
+    def build():
+        params, o = [], 0
+        for m in lens:
+            params.append(torch.nn.Parameter(p0[o:o + m].clone().to(dtype)))
+            o += m
+        return params, [dict(HP, params=[p]) for p in params]
+
+    def set_grads(params, g):
+        o = 0
+        for p, m in zip(params, lens):
+            p.grad = g[o:o + m].clone().to(dtype)
+            o += m
+
+    (pk, gk), (pt, gt) = build(), build()
+    sk, st = collections.defaultdict(dict), collections.defaultdict(dict)
+    flat = torch.empty(sum(lens), device=DEV)
+    row = {"parity": name, "dtype": str(dtype).split(".")[-1], "elements": sum(lens)}
+    for k, g in enumerate(gs):
+        set_grads(pk, g)
+        set_grads(pt, g)
+        utils.apply_gradient(gk, sk, flat_out=flat)
+        torch_loop(gt, st)
+        cat = lambda ts: torch.cat([t.detach().reshape(-1) for t in ts])  # noqa: E731
+        row[f"step{k}"] = {"p": _differ(cat(pk), cat(pt)),
+                           "buf": _differ(cat([sk[p]["momentum_buffer"] for p in pk]),
+                                          cat([st[p]["momentum_buffer"] for p in pt])),
+                           "flat": _differ(flat, cat(pt).float())}
+    return row
+
+
+def parity_rows():
+    with np.load(os.path.join(ROOT, "tests", "golden", "sgd_inputs.npz")) as z:
+        lens = z["lens"].tolist()
+        p0 = torch.from_numpy(z["p0"]).to(DEV)
+        gs = [torch.from_numpy(z[f"g{k}"]).to(DEV) for k in range(3)]
+    g = torch.Generator(device=DEV).manual_seed(11)
+    m = 1 << 20
+    big_p = torch.randn(m, generator=g, device=DEV)
+    big_g = [0.01 * torch.randn(m, generator=g, device=DEV) for _ in range(3)]
+    rows = []
+    for dtype in (torch.float32, torch.bfloat16, torch.float16):
+        rows.append(parity("fixture_layout", p0, gs, lens, dtype))
+        rows.append(parity("one_tensor_1M", big_p, big_g, [m], dtype))
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "the probe needs a ROCm device"
+    rows = []
+    for name, lens, dtype in layouts():
+        rows.append(measure(name, lens, dtype, args.steps, args.reps))
+        print(json.dumps(rows[-1]), flush=True)
+    for row in parity_rows():
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
