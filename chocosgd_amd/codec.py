@@ -1031,6 +1031,7 @@ def params_unpack(flat, tensors):
 # ----------------------------------------------------------------------------- SGD update + pack
 SGD_F_NESTEROV, SGD_F_FIRST, SGD_F_NOGRAD = 1, 2, 4                    # CHOCO_SGD_F_*
 SGD_MODE_GRAD, SGD_MODE_WRITE_PARAMS, SGD_MODE_WRITE_GRADS = 1, 2, 4   # CHOCO_SGD_MODE_*
+SGD_MODE_ADD_FLAT = 8                                                  # choco_params_sgd_clip only
 
 
 def params_sgd_launches(nseg):
@@ -1067,6 +1068,7 @@ class ParamSgdPlan:
             self.numels.append(p.numel())
         self.n = sum(self.numels)
         self.seen = [None] * nseg  # the hyperparameter tuple last written, per tensor
+        self._norms = self._norm_ws = None  # sqnorm()'s output and workspace, allocated on first use
         self._refs = [weakref.ref(p) for p in params]
 
     def holds(self, params):
@@ -1078,16 +1080,51 @@ class ParamSgdPlan:
         return (t.dtype == self.dtypes[i] and t.device == self.device and t.numel() == self.numels[i]
                 and t.is_contiguous())
 
-    def run(self, flat=None, grad_mode=False, write=True):
+    def sqnorm(self):
+        """One choco_params_sqnorm over the tables as they stand: the per-tensor L2 norms of
+        d = g (+ wd * p), what DGC._clip_gradient sees (dgc.py:254-256).  Returns the plan's own
+        fp32 tensor of nseg norms (overwritten by the next call)."""
+        L = lib()
+        if self._norms is None:
+            self._norms = torch.empty(self.nseg, dtype=torch.float32, device=self.device)
+            self._norm_ws = torch.empty(int(L.choco_params_sqnorm_workspace_size(self.nseg, self.n)),
+                                        dtype=torch.uint8, device=self.device)
+        _lib.check(L.choco_params_sqnorm(self.param_ptrs, self.grad_ptrs, self.lens, self.dts, self.weight_decay,
+                                         self.flags, self.nseg, self.n, _ptr(self._norms), _ptr(self._norm_ws),
+                                         self._norm_ws.numel(), _stream(self.device)), "choco_params_sqnorm")
+        return self._norms
+
+    def run(self, flat=None, grad_mode=False, write=True, norms=None, clip_threshold=None, add_flat=False):
         """One choco_params_sgd over the tables as they stand.  apply mode (grad_mode False):
         write -> the params are updated; grad mode: write -> d_p goes into the grads' storage.
-        flat (fp32, n elements, or None) receives the new params / d_p in the same pass."""
+        flat (fp32, n elements, or None) receives the new params / d_p in the same pass.
+
+        norms (fp32 device tensor of nseg, e.g. sqnorm()'s) with clip_threshold (a Python float,
+        clip_grad_val / sqrt(n_nodes)): DGC's per-tensor clipping between the weight decay and
+        the momentum; add_flat (grad mode): flat += d_p instead of flat = d_p.  Either one takes
+        choco_params_sgd_clip; the defaults are choco_params_sgd, as before."""
         if flat is not None:
             _require(flat, torch.float32, "flat")
             if flat.device != self.device or flat.numel() != self.n:
                 raise RuntimeError(f"flat must hold {self.n} elements on {self.device}")
         mode = (SGD_MODE_GRAD | (SGD_MODE_WRITE_GRADS if write else 0)) if grad_mode else \
             (SGD_MODE_WRITE_PARAMS if write else 0)
+        if clip_threshold is not None and norms is None:
+            raise RuntimeError("clip_threshold needs norms (sqnorm()'s, or recorded ones): nothing would be clipped")
+        if norms is not None or add_flat:
+            if norms is not None:
+                _require(norms, torch.float32, "norms")
+                if norms.device != self.device or norms.numel() != self.nseg:
+                    raise RuntimeError(f"norms must hold {self.nseg} elements on {self.device}")
+                if clip_threshold is None:
+                    raise RuntimeError("norms needs a clip_threshold")
+            _lib.check(lib().choco_params_sgd_clip(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts,
+                                                   self.lr, self.weight_decay, self.momentum, self.dampening,
+                                                   self.flags, self.nseg, _ptr(flat), self.n,
+                                                   mode | (SGD_MODE_ADD_FLAT if add_flat else 0), _ptr(norms),
+                                                   float(clip_threshold) if norms is not None else 0.0,
+                                                   _stream(self.device)), "choco_params_sgd_clip")
+            return
         _lib.check(lib().choco_params_sgd(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts, self.lr,
                                           self.weight_decay, self.momentum, self.dampening, self.flags, self.nseg,
                                           _ptr(flat), self.n, mode, _stream(self.device)), "choco_params_sgd")
@@ -1130,6 +1167,82 @@ def params_sgd(params, grads, bufs, lr, weight_decay=0.0, momentum=0.0, dampenin
         plan.seen[i] = None
     plan.run(flat, grad_mode, write)
     return plan
+
+
+def params_sqnorm_launches(nseg):
+    """Launches one params_sqnorm of `nseg` tensors takes."""
+    return int(lib().choco_params_sqnorm_launches(int(nseg)))
+
+
+def params_sqnorm(params, grads, weight_decay=0.0, plan=None):
+    """Per-tensor L2 norms of d = g, or fma(wd, p, g) where weight_decay != 0 (scalar or
+    per-tensor list): DGC._clip_gradient's grad.norm(p=2) (dgc.py:254-256) for a whole list in
+    one batched launch per chunk plus a finish launch, fp64 accumulation in a fixed order.
+    grads[s] None: norm 0.  Returns the plan's fp32 norms tensor (pass `plan` back in to reuse
+    its tables and workspace; the tensor is overwritten by the plan's next sqnorm)."""
+    params = list(params)
+    nseg = len(params)
+    if plan is None:
+        plan = ParamSgdPlan(params)
+    elif not plan.holds(params):
+        raise RuntimeError("the plan was built for another parameter list")
+    grads, wds = _per_tensor(grads, nseg, "grads"), _per_tensor(weight_decay, nseg, "weight_decay")
+    for i, (p, g, wd) in enumerate(zip(params, grads, wds)):
+        if g is not None and not plan.fits(i, g):
+            raise RuntimeError(f"grad {i} must match its parameter's dtype, device and size, and be contiguous")
+        plan.param_ptrs[i] = p.data_ptr()
+        plan.grad_ptrs[i] = g.data_ptr() if g is not None else None
+        plan.flags[i] = SGD_F_NOGRAD if g is None else 0
+        plan.weight_decay[i] = wd
+        plan.seen[i] = None
+    return plan.sqnorm()
+
+
+def params_mask_launches(nseg):
+    """Launches one params_mask of `nseg` tensors takes."""
+    return int(lib().choco_params_mask_launches(int(nseg)))
+
+
+def params_mask(bufs, values, indices, k_per_seg, memory=None, lens=None, dtypes=None):
+    """DGC's momentum-factor masking (dgc.py:178-182) and the clear of the error-feedback memory
+    at the selected positions (:174-176), one batched launch per chunk of tensors: for slot j of
+    tensor s, bufs[s].view(-1)[indices[j] - off_s] *= 0 and memory[indices[j]] = v + (-v), v =
+    values[j].  values / indices: a segmented selection (global ascending int32 indices) with
+    k_per_seg[s] slots per tensor.  bufs[s] may be None (no buffer to mask); then `lens` (and,
+    for 16-bit layouts, `dtypes`) give the layout, which otherwise comes from the buffers."""
+    bufs = list(bufs)
+    nseg = len(bufs)
+    _require(values, torch.float32, "values")
+    _require(indices, torch.int32, "indices")
+    dev = values.device
+    if len(k_per_seg) != nseg or indices.numel() != values.numel():
+        raise RuntimeError("k_per_seg needs one entry per tensor, indices one per value")
+    if lens is None:
+        if any(b is None for b in bufs):
+            raise RuntimeError("params_mask needs `lens` when a buffer is None")
+        lens = [b.numel() for b in bufs]
+    if len(lens) != nseg:
+        raise RuntimeError(f"lens: {len(lens)} values for {nseg} tensors")
+    ptrs, c_lens, dts, ks = ((ctypes.c_void_p * nseg)(), (ctypes.c_int64 * nseg)(), (ctypes.c_int32 * nseg)(),
+                             (ctypes.c_int64 * nseg)())
+    for i, b in enumerate(bufs):
+        if b is not None:
+            _require(b, None, f"buf {i}")
+            if b.device != dev or b.numel() != lens[i] or b.dtype not in PARAM_DTYPES:
+                raise RuntimeError(f"buf {i} must hold {lens[i]} fp32 / bf16 / fp16 elements on {dev}")
+            if dtypes is not None and dtypes[i] != b.dtype:
+                raise RuntimeError(f"buf {i} is {b.dtype}, dtypes says {dtypes[i]}")
+            ptrs[i], dts[i] = b.data_ptr(), PARAM_DTYPES[b.dtype]
+        else:
+            ptrs[i], dts[i] = None, PARAM_DTYPES[dtypes[i]] if dtypes is not None else 0
+        c_lens[i], ks[i] = int(lens[i]), int(k_per_seg[i])
+    n = sum(int(m) for m in lens)
+    if memory is not None:
+        _require(memory, torch.float32, "memory")
+        if memory.device != dev or memory.numel() != n:
+            raise RuntimeError(f"memory must hold {n} elements on {dev}")
+    _lib.check(lib().choco_params_mask(ptrs, c_lens, dts, ks, nseg, _ptr(values), _ptr(indices), values.numel(),
+                                       _ptr(memory), n, _stream(dev)), "choco_params_mask")
 
 
 # ----------------------------------------------------------------------------- profiling

@@ -52,8 +52,8 @@ struct SgdTable {
   uint8_t fl[kSgdCap];       // CHOCO_SGD_F_* | kSgdHas*
   int32_t nt;
 };
-// the table, the flat pointer and three words: a launch carries at most 4 KB of arguments
-static_assert(sizeof(SgdTable) + 24 <= 4096 - 256, "SgdTable must fit in the kernel arguments");
+// the table, the flat and norms pointers and four words: a launch carries at most 4 KB of arguments
+static_assert(sizeof(SgdTable) + 40 <= 4096 - 256, "SgdTable must fit in the kernel arguments");
 
 // what one tensor's update needs (workgroup-uniform)
 struct SgdTensor {
@@ -66,6 +66,8 @@ struct SgdTensor {
   bool rd_p, rd_g, rd_b;   // operands read
   bool wr_p, wr_g, wr_b;   // tensors written (flat: flat != nullptr)
   bool grad_mode, pack_only;
+  bool clip, add_flat;     // choco_params_sgd_clip: d = c * d after the weight decay; flat += out
+  float c;                 // the tensor's clip coefficient
 };
 
 // The value as the storage dtype holds it.  v is the fp32 result of its line and is narrowed
@@ -88,6 +90,7 @@ CHOCO_DEV void sgd_math(const SgdTensor& t, float p, float g, float b, float& bu
   }
   float d = g;
   if (t.has_wd) d = rnd<DT>(fmaf(t.wd, p, d));
+  if (t.clip) d = rnd<DT>(__fmul_rn(t.c, d));
   if (t.has_mom) {
     float nb;
     if (t.first) {
@@ -124,7 +127,7 @@ CHOCO_DEV void sgd_elem(const SgdTensor& t, int64_t i, int64_t j) {
   if (t.wr_b) st1<DT>(t.buf, j, nb);
   if (t.wr_p) st1<DT>(t.p, j, out);
   if (t.wr_g) st1<DT>(t.g, j, out);
-  if (t.flat) t.flat[i] = out;
+  if (t.flat) t.flat[i] = t.add_flat ? t.flat[i] + out : out;
 }
 
 // a group of 8 elements as loaded: two float4 (fp32) or one 16-byte vector of halves
@@ -179,7 +182,7 @@ CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, bo
   const int64_t g0 = a >> 3, g1 = (b - 1) >> 3;  // groups at absolute flat offsets, inclusive
   for (int64_t gb = g0; gb <= g1; gb += (int64_t)kPbThreads * kSgdU) {
     bool full[kSgdU];
-    Raw8 rp[kSgdU], rg[kSgdU], rb[kSgdU];
+    Raw8 rp[kSgdU], rg[kSgdU], rb[kSgdU], rf[kSgdU];
     // every load of the thread's kSgdU groups is issued before the first store
 #pragma unroll
     for (int u = 0; u < kSgdU; ++u) {
@@ -189,6 +192,7 @@ CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, bo
         if (t.rd_p) ld8<DT>(rp[u], t.p, e - o0);
         if (t.rd_g) ld8<DT>(rg[u], t.g, e - o0);
         if (t.rd_b) ld8<DT>(rb[u], t.buf, e - o0);
+        if (t.add_flat) ld8<CHOCO_DT_F32>(rf[u], t.flat, e);
       }
     }
 #pragma unroll
@@ -205,6 +209,12 @@ CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, bo
         if (t.wr_b) st8<DT>(t.buf, e - o0, nb);
         if (t.wr_p) st8<DT>(t.p, e - o0, out);
         if (t.wr_g) st8<DT>(t.g, e - o0, out);
+        if (t.add_flat) {
+          float f[8];
+          widen8<CHOCO_DT_F32>(rf[u], f);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) out[k] = f[k] + out[k];
+        }
         if (t.flat) st8<CHOCO_DT_F32>(t.flat, e, out);
       } else {
         // a group cut by the tensor's start or end (or past the span): its own elements only
@@ -215,8 +225,12 @@ CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, bo
   }
 }
 
+// EXT: the instantiation choco_params_sgd_clip launches (clip coefficients from norms[s] when
+// norms != nullptr, ADD_FLAT); choco_params_sgd's own has neither compiled in.
+template <bool EXT>
 __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb, float* flat, int64_t tile0,
-                                                               int32_t flat16, int32_t mode) {
+                                                               int32_t flat16, int32_t mode, const float* norms,
+                                                               float thr) {
   const int nt = tb.nt;
   const int64_t tile = tile0 + blockIdx.x;
   const int64_t tlo = i64max(tile * kPbTile, tb.off[0]);
@@ -245,6 +259,15 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
     t.nesterov = (fl & CHOCO_SGD_F_NESTEROV) != 0;
     t.first = (fl & CHOCO_SGD_F_FIRST) != 0;
     t.grad_mode = grad_mode;
+    t.clip = EXT && norms != nullptr && !t.pack_only;
+    t.add_flat = EXT && (mode & CHOCO_SGD_MODE_ADD_FLAT) != 0;
+    t.c = 1.0f;
+    if (t.clip) {
+      // threshold / grad_norm as torch computes it: grad_norm.reciprocal() * threshold, after an
+      // fp32 comparison (a NaN norm compares false; an inf norm gives 0)
+      const float nrm = norms[s];
+      if (nrm >= thr) t.c = __fmul_rn(1.0f / nrm, thr);
+    }
     t.rd_p = t.pack_only || t.has_wd || !grad_mode;
     t.rd_g = !t.pack_only;
     t.rd_b = !t.pack_only && t.has_mom && !t.first;
@@ -282,6 +305,9 @@ struct SgdArgs {
   float* flat;
   int64_t n;
   int32_t mode;
+  bool ext;              // choco_params_sgd_clip: the ADD_FLAT bit and the two arguments below
+  const float* norms;    // device, nseg per-tensor norms; nullptr: no clipping
+  double clip_threshold;
 };
 
 static bool elem_aligned(const void* p, uintptr_t esz) { return (reinterpret_cast<uintptr_t>(p) & (esz - 1)) == 0; }
@@ -293,8 +319,17 @@ static int sgd_check(const SgdArgs& a) {
   CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
   CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
   constexpr int32_t kModes = CHOCO_SGD_MODE_GRAD | CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS;
-  CHOCO_REQUIRE((a.mode & ~kModes) == 0, "unknown mode bits 0x%x", (unsigned)a.mode);
+  CHOCO_REQUIRE((a.mode & ~(kModes | (a.ext ? CHOCO_SGD_MODE_ADD_FLAT : 0))) == 0, "unknown mode bits 0x%x",
+                (unsigned)a.mode);
   const bool grad_mode = (a.mode & CHOCO_SGD_MODE_GRAD) != 0;
+  if (a.mode & CHOCO_SGD_MODE_ADD_FLAT)
+    CHOCO_REQUIRE(grad_mode && a.flat, "ADD_FLAT needs grad mode and a flat buffer");
+  if (a.norms) {
+    CHOCO_REQUIRE(aligned4(a.norms), "norms must be 4-byte aligned");
+    // tested as the kernel uses it: a positive double below fp32's range would clip against 0
+    CHOCO_REQUIRE(a.clip_threshold <= 3.4028234663852886e38 && (float)a.clip_threshold > 0.0f,
+                  "the clip threshold must be finite and > 0 as an fp32 value, got %g", a.clip_threshold);
+  }
   CHOCO_REQUIRE(!(grad_mode && (a.mode & CHOCO_SGD_MODE_WRITE_PARAMS)), "grad mode does not write the params");
   CHOCO_REQUIRE(!(!grad_mode && (a.mode & CHOCO_SGD_MODE_WRITE_GRADS)), "apply mode does not write the grads");
   CHOCO_REQUIRE(a.flat || (a.mode & (CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS)),
@@ -363,9 +398,306 @@ static int sgd_run(const SgdArgs& a, hipStream_t st) {
     // the tiles the chunk [off[0], off[nt]) touches; an empty chunk still takes its launch
     const int64_t tile0 = tb.off[0] / kPbTile;
     const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
-    CHOCO_TRY(CHOCO_LAUNCH("param_sgd_kernel", "param_sgd_kernel", param_sgd_kernel, dim3((unsigned)tiles),
-                           dim3(kPbThreads), st, tb, a.flat, tile0, flat16, a.mode));
+    const float* norms = a.norms ? a.norms + s0 : nullptr;
+    const float thr = (float)a.clip_threshold;
+    if (a.ext)
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_kernel", "param_sgd_kernel<clip>", param_sgd_kernel<true>,
+                             dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.flat, tile0, flat16, a.mode, norms,
+                             thr));
+    else
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_kernel", "param_sgd_kernel", param_sgd_kernel<false>, dim3((unsigned)tiles),
+                             dim3(kPbThreads), st, tb, a.flat, tile0, flat16, a.mode, norms, thr));
   }
+  return CHOCO_OK;
+}
+
+// ------------------------------------------------------------------ per-tensor gradient norms
+// ||d_s||_2 of every tensor, d = g or rnd(fma(wd, p, g)) (the first line of sgd_math): what
+// DGC._clip_gradient takes of d_p after the weight decay (dl_code/pcode/optim/dgc.py:254-265,
+// :304-310).  Same shape as the update: 8192-element tiles at absolute flat offsets, the chunk's
+// table in the kernel arguments, the same uniform search, 16-byte loads where p and g are
+// congruent with the group grid.  Squares and sums are fp64 (the square of an fp32 value is
+// exact there and the sum cannot overflow).  No atomics: every (tile, tensor) pair stores ONE
+// fp64 partial at slot tile + s -- the pairs are strictly ordered, so the slot is unique and a
+// tensor's slots are contiguous -- and the finish kernel adds a tensor's slots in ascending
+// order.  Every slot and meta word the finish reads is written by the same call.  Spans of up to
+// kNormWaveMax elements are reduced by ONE wave of the workgroup, the waves taking them in turn,
+// with no barrier (a tile of the 3000 x 100 layout holds ~80 tensors); longer spans by the
+// whole workgroup through LDS.
+constexpr int kNormCap = 112;             // tensors per launch
+constexpr int kNormU = 2;                 // 8-element groups in flight per thread
+constexpr int64_t kNormWaveMax = 1024;
+#ifndef CHOCO_SQNORM_NT
+#define CHOCO_SQNORM_NT 0                 // 1: non-temporal loads.  Default-policy loads leave p and g in the
+                                          // Infinity Cache for the update that follows
+#endif
+
+struct NormTable {
+  const void* p[kNormCap];
+  const void* g[kNormCap];
+  int64_t off[kNormCap + 1];
+  float wd[kNormCap];
+  uint8_t dt[kNormCap];
+  uint8_t fl[kNormCap];  // CHOCO_SGD_F_NOGRAD | kSgdHasWd
+  int32_t nt;
+};
+static_assert(sizeof(NormTable) + 32 <= 4096 - 256, "NormTable must fit in the kernel arguments");
+
+template <int DT>
+CHOCO_DEV void ld8n(Raw8& r, const void* base, int64_t j) {
+  if (CHOCO_SQNORM_NT) {
+    ld8<DT>(r, base, j);
+  } else if (DT == CHOCO_DT_F32) {
+    const float4* s = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + j);
+    r.lo = s[0];
+    r.hi = s[1];
+  } else {
+    r.h = *reinterpret_cast<const choco_u16x8*>(reinterpret_cast<const unsigned short*>(base) + j);
+  }
+}
+
+template <int DT>
+CHOCO_DEV double norm_sq(bool has_wd, float wd, float p, float g) {
+  float d = g;
+  if (has_wd) d = rnd<DT>(fmaf(wd, p, d));
+  return (double)d * (double)d;
+}
+
+template <int DT>
+CHOCO_DEV double norm_elem(const void* p, const void* g, bool has_wd, float wd, int64_t j) {
+  return norm_sq<DT>(has_wd, wd, has_wd ? ld1<DT>(p, j) : 0.0f, ld1<DT>(g, j));
+}
+
+// this thread's share of flat elements [a, b) of a tensor at flat offset o0, `stride` threads
+// (a wave or the workgroup) taking it elementwise, `me` this thread's place among them
+template <int DT>
+CHOCO_DEV double norm_scalar(const void* p, const void* g, bool has_wd, float wd, int64_t o0, int64_t a, int64_t b,
+                             int me, int stride) {
+  double acc = 0.0;
+  for (int64_t i = a + me; i < b; i += stride) acc += norm_elem<DT>(p, g, has_wd, wd, i - o0);
+  return acc;
+}
+
+// ... the workgroup taking whole groups as 16-byte vectors
+template <int DT>
+CHOCO_DEV double norm_vector(const void* p, const void* g, bool has_wd, float wd, int64_t o0, int64_t a, int64_t b) {
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  const int64_t g0 = a >> 3, g1 = (b - 1) >> 3;
+  for (int64_t gb = g0; gb <= g1; gb += (int64_t)kPbThreads * kNormU) {
+    bool full[kNormU];
+    Raw8 rp[kNormU], rg[kNormU];
+#pragma unroll
+    for (int u = 0; u < kNormU; ++u) {
+      const int64_t e = (gb + u * kPbThreads + tid) * kPbGroup;
+      full[u] = e >= a && e + kPbGroup <= b;
+      if (full[u]) {
+        if (has_wd) ld8n<DT>(rp[u], p, e - o0);
+        ld8n<DT>(rg[u], g, e - o0);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kNormU; ++u) {
+      const int64_t e = (gb + u * kPbThreads + tid) * kPbGroup;
+      if (full[u]) {
+        float pv[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gv[8];
+        if (has_wd) widen8<DT>(rp[u], pv);
+        widen8<DT>(rg[u], gv);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc += norm_sq<DT>(has_wd, wd, pv[k], gv[k]);
+      } else {
+        const int64_t ea = e > a ? e : a, eb = e + kPbGroup < b ? e + kPbGroup : b;
+        for (int64_t i = ea; i < eb; ++i) acc += norm_elem<DT>(p, g, has_wd, wd, i - o0);
+      }
+    }
+  }
+  return acc;
+}
+
+// meta: two words per tensor of the chunk, {first slot, slots | dtype << 24}
+__global__ __launch_bounds__(kPbThreads) void param_sqnorm_kernel(const NormTable tb, double* slots, int32_t* meta,
+                                                                  int64_t tile0, int32_t seg0) {
+  __shared__ double red[kPbThreads / 64];
+  const int nt = tb.nt;
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0) {
+    for (int s = 0; s < nt; ++s) {  // s is uniform: the table is read with scalar loads
+      const int64_t o0 = tb.off[s], o1 = tb.off[s + 1];
+      const bool any = o1 > o0 && !(tb.fl[s] & CHOCO_SGD_F_NOGRAD);
+      const int32_t cnt = any ? (int32_t)((o1 - 1) / kPbTile - o0 / kPbTile + 1) : 0;
+      if (tid == (s & (kPbThreads - 1))) {
+        meta[2 * s] = (int32_t)(o0 / kPbTile) + seg0 + s;
+        meta[2 * s + 1] = cnt | ((int32_t)tb.dt[s] << 24);
+      }
+    }
+  }
+  const int64_t tile = tile0 + blockIdx.x;
+  const int64_t tlo = i64max(tile * kPbTile, tb.off[0]);
+  const int64_t thi = i64min((tile + 1) * kPbTile, tb.off[nt]);
+  if (tlo >= thi) return;
+  int lo = 1, hi = nt;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (tb.off[mid] > tlo) hi = mid; else lo = mid + 1;
+  }
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  int nshort = 0;
+  for (int s = lo - 1; s < nt; ++s) {
+    const int64_t o0 = tb.off[s];
+    if (o0 >= thi) break;
+    const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);
+    const uint32_t fl = tb.fl[s];
+    if (a >= b || (fl & CHOCO_SGD_F_NOGRAD)) continue;
+    const int dt = tb.dt[s];
+    const bool has_wd = (fl & kSgdHasWd) != 0;
+    const float wd = tb.wd[s];
+    const void* p = tb.p[s];
+    const void* g = tb.g[s];
+    double* slot = slots + (tile + seg0 + s);
+    if (b - a <= kNormWaveMax) {
+      const bool mine = (nshort & 3) == wave;
+      ++nshort;
+      if (!mine) continue;
+      double acc;
+      if (dt == CHOCO_DT_F32) acc = norm_scalar<CHOCO_DT_F32>(p, g, has_wd, wd, o0, a, b, lane, 64);
+      else if (dt == CHOCO_DT_BF16) acc = norm_scalar<CHOCO_DT_BF16>(p, g, has_wd, wd, o0, a, b, lane, 64);
+      else acc = norm_scalar<CHOCO_DT_F16>(p, g, has_wd, wd, o0, a, b, lane, 64);
+      acc = wave_sum(acc);
+      if (lane == 0) *slot = acc;
+      continue;
+    }
+    const uintptr_t esz = dt == CHOCO_DT_F32 ? 4u : 2u, back = esz * (uintptr_t)o0;
+    uintptr_t mis = reinterpret_cast<uintptr_t>(g) - back;
+    if (has_wd) mis |= reinterpret_cast<uintptr_t>(p) - back;
+    const bool vec = (mis & 15u) == 0;
+    double acc;
+    if (dt == CHOCO_DT_F32)
+      acc = vec ? norm_vector<CHOCO_DT_F32>(p, g, has_wd, wd, o0, a, b)
+                : norm_scalar<CHOCO_DT_F32>(p, g, has_wd, wd, o0, a, b, tid, kPbThreads);
+    else if (dt == CHOCO_DT_BF16)
+      acc = vec ? norm_vector<CHOCO_DT_BF16>(p, g, has_wd, wd, o0, a, b)
+                : norm_scalar<CHOCO_DT_BF16>(p, g, has_wd, wd, o0, a, b, tid, kPbThreads);
+    else
+      acc = vec ? norm_vector<CHOCO_DT_F16>(p, g, has_wd, wd, o0, a, b)
+                : norm_scalar<CHOCO_DT_F16>(p, g, has_wd, wd, o0, a, b, tid, kPbThreads);
+    acc = wave_sum(acc);
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (tid == 0) *slot = ((red[0] + red[1]) + red[2]) + red[3];
+    __syncthreads();  // red is reused by the next long span
+  }
+}
+
+// one wave per tensor: its slots added in ascending order (64 at a time are loaded by the lanes
+// side by side, then added one after the other, so the order does not depend on the lane count),
+// sqrt in fp64, rounded to fp32 and, for a 16-bit tensor, again to its dtype (grad.norm()
+// returns the gradient's dtype)
+constexpr int kNormFinishWaves = kPbThreads / 64;
+__global__ __launch_bounds__(kPbThreads) void param_sqnorm_finish_kernel(const double* slots, const int32_t* meta,
+                                                                         float* norms, int32_t nseg) {
+  const int lane = threadIdx.x & 63;
+  const int s = blockIdx.x * kNormFinishWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (s >= nseg) return;
+  const int32_t slot0 = meta[2 * s], cd = meta[2 * s + 1];
+  const int32_t cnt = cd & 0xffffff, dt = cd >> 24;
+  double acc = 0.0;
+  for (int32_t base = 0; base < cnt; base += 64) {
+    const int32_t i = base + lane;
+    const double v = i < cnt ? slots[slot0 + i] : 0.0;
+    const int32_t m = cnt - base < 64 ? cnt - base : 64;
+    for (int32_t l = 0; l < m; ++l) acc += __shfl(v, l);
+  }
+  float r = (float)sqrt(acc);
+  if (dt == CHOCO_DT_BF16) r = rnd<CHOCO_DT_BF16>(r);
+  else if (dt == CHOCO_DT_F16) r = rnd<CHOCO_DT_F16>(r);
+  if (lane == 0) norms[s] = r;
+}
+
+static int norm_launches(int32_t nseg) { return nseg <= 0 ? 0 : (nseg + kNormCap - 1) / kNormCap + 1; }
+static size_t norm_slots(int32_t nseg, int64_t n) { return (size_t)(n / kPbTile + 1) + (size_t)nseg; }
+static size_t norm_ws_bytes(int32_t nseg, int64_t n) {
+  if (nseg <= 0 || n < 0) return 0;
+  return align_up(norm_slots(nseg, n) * sizeof(double) + (size_t)nseg * 2 * sizeof(int32_t), 256);
+}
+
+struct NormArgs {
+  const void* const* params;
+  const void* const* grads;
+  const int64_t* lens;
+  const int32_t* dtypes;
+  const double* wd;
+  const int32_t* flags;
+  int32_t nseg;
+  int64_t n;
+  float* norms;
+  void* ws;
+  size_t ws_bytes;
+};
+
+static int norm_check(const NormArgs& a) {
+  CHOCO_REQUIRE(a.params && a.grads && a.lens && a.dtypes && a.wd && a.flags, "null table argument");
+  CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
+  CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
+  CHOCO_REQUIRE(a.norms && aligned4(a.norms), "norms must be a 4-byte aligned device pointer");
+  CHOCO_REQUIRE(a.ws && (reinterpret_cast<uintptr_t>(a.ws) & 7u) == 0, "the workspace must be 8-byte aligned");
+  if (a.ws_bytes < norm_ws_bytes(a.nseg, a.n))
+    return fail(CHOCO_ERR_WORKSPACE, "workspace too small: %zu bytes, need %zu", a.ws_bytes,
+                norm_ws_bytes(a.nseg, a.n));
+  int64_t sum = 0;
+  for (int32_t s = 0; s < a.nseg; ++s) {
+    const int i = (int)s;
+    CHOCO_REQUIRE(a.lens[s] >= 0, "tensor %d: negative length", i);
+    CHOCO_REQUIRE(a.dtypes[s] >= CHOCO_DT_F32 && a.dtypes[s] <= CHOCO_DT_F16, "tensor %d: unknown dtype code %d", i,
+                  (int)a.dtypes[s]);
+    CHOCO_REQUIRE(a.lens[s] <= a.n - sum, "the lengths add up to more than n = %lld", (long long)a.n);
+    sum += a.lens[s];
+    constexpr int32_t kFlags = CHOCO_SGD_F_NESTEROV | CHOCO_SGD_F_FIRST | CHOCO_SGD_F_NOGRAD;
+    CHOCO_REQUIRE((a.flags[s] & ~kFlags) == 0, "tensor %d: unknown flag bits 0x%x", i, (unsigned)a.flags[s]);
+    const uintptr_t esz = a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u;
+    CHOCO_REQUIRE(elem_aligned(a.params[s], esz) && elem_aligned(a.grads[s], esz),
+                  "tensor %d: pointer not aligned to its element size", i);
+    if (a.lens[s] == 0 || (a.flags[s] & CHOCO_SGD_F_NOGRAD)) continue;
+    CHOCO_REQUIRE(a.grads[s], "tensor %d: null grad pointer without the no-grad flag", i);
+    CHOCO_REQUIRE(a.params[s] || a.wd[s] == 0.0, "tensor %d: null param pointer with weight decay != 0", i);
+  }
+  CHOCO_REQUIRE(sum == a.n, "the lengths add up to %lld, n is %lld", (long long)sum, (long long)a.n);
+  return CHOCO_OK;
+}
+
+static int norm_run(const NormArgs& a, hipStream_t st) {
+  const int rc = norm_check(a);
+  if (rc) return rc;
+  double* slots = reinterpret_cast<double*>(a.ws);
+  int32_t* meta = reinterpret_cast<int32_t*>(slots + norm_slots(a.nseg, a.n));
+  NormTable tb;
+  int64_t base = 0;
+  for (int32_t s0 = 0; s0 < a.nseg; s0 += kNormCap) {
+    const int nt = std::min<int32_t>(kNormCap, a.nseg - s0);
+    tb.nt = nt;
+    tb.off[0] = base;
+    for (int i = 0; i < kNormCap; ++i) {
+      const bool in = i < nt;
+      const int32_t s = s0 + i;
+      const bool upd = in && !(a.flags[s] & CHOCO_SGD_F_NOGRAD);
+      tb.p[i] = upd ? a.params[s] : nullptr;
+      tb.g[i] = upd ? a.grads[s] : nullptr;
+      tb.wd[i] = upd ? (float)a.wd[s] : 0.0f;
+      tb.dt[i] = in ? (uint8_t)a.dtypes[s] : (uint8_t)0;
+      uint32_t fl = in ? (uint32_t)(a.flags[s] & CHOCO_SGD_F_NOGRAD) : 0u;
+      if (upd && a.wd[s] != 0.0) fl |= kSgdHasWd;
+      tb.fl[i] = (uint8_t)fl;
+      base += in ? a.lens[s] : 0;
+      tb.off[i + 1] = base;
+    }
+    const int64_t tile0 = tb.off[0] / kPbTile;
+    const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
+    CHOCO_TRY(CHOCO_LAUNCH("param_sqnorm_kernel", "param_sqnorm_kernel", param_sqnorm_kernel, dim3((unsigned)tiles),
+                           dim3(kPbThreads), st, tb, slots, meta + 2 * (size_t)s0, tile0, s0));
+  }
+  const unsigned blocks = (unsigned)((a.nseg + kNormFinishWaves - 1) / kNormFinishWaves);
+  CHOCO_TRY(CHOCO_LAUNCH("param_sqnorm_finish_kernel", "param_sqnorm_finish_kernel", param_sqnorm_finish_kernel,
+                         dim3(blocks), dim3(kPbThreads), st, (const double*)slots, (const int32_t*)meta, a.norms,
+                         a.nseg));
   return CHOCO_OK;
 }
 
@@ -379,6 +711,27 @@ CHOCO_API int choco_params_sgd(void* const* params, const void* const* grads, vo
                                const int32_t* dtypes, const double* lr, const double* weight_decay,
                                const double* momentum, const double* dampening, const int32_t* flags, int32_t nseg,
                                float* flat, int64_t n, int32_t mode, void* stream) {
-  const SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, flat, n, mode};
+  const SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, flat, n, mode,
+                  false, nullptr, 0.0};
   return sgd_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_sgd_clip(void* const* params, const void* const* grads, void* const* bufs,
+                                    const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                    const double* weight_decay, const double* momentum, const double* dampening,
+                                    const int32_t* flags, int32_t nseg, float* flat, int64_t n, int32_t mode,
+                                    const float* norms, double clip_threshold, void* stream) {
+  const SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, flat, n, mode,
+                  true, norms, clip_threshold};
+  return sgd_run(a, as_stream(stream));
+}
+
+CHOCO_API size_t choco_params_sqnorm_workspace_size(int32_t nseg, int64_t n) { return norm_ws_bytes(nseg, n); }
+CHOCO_API int choco_params_sqnorm_launches(int32_t nseg) { return norm_launches(nseg); }
+
+CHOCO_API int choco_params_sqnorm(const void* const* params, const void* const* grads, const int64_t* lens,
+                                  const int32_t* dtypes, const double* weight_decay, const int32_t* flags, int32_t nseg,
+                                  int64_t n, float* norms, void* ws, size_t ws_bytes, void* stream) {
+  const NormArgs a{params, grads, lens, dtypes, weight_decay, flags, nseg, n, norms, ws, ws_bytes};
+  return norm_run(a, as_stream(stream));
 }

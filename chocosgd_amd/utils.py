@@ -62,13 +62,24 @@ def _sgd_plan(params):
 def _sgd_batched(entries, state, apply_grad_to_model, flat, write):
     """One batched launch (per chunk) for `entries`, a list of (group, param) in flat order.
     Returns False, with nothing changed, where a tensor cannot take it."""
-    if not entries:
+    plan = _sgd_fill(entries, state, apply_grad_to_model, flat)
+    if plan is None:
         return False
+    plan.run(flat, grad_mode=not apply_grad_to_model, write=write)
+    return True
+
+
+def _sgd_fill(entries, state, apply_grad_to_model, flat):
+    """The plan of `entries` with this step's pointers, flags and hyperparameters written (and
+    missing momentum buffers created), ready to run; None, with nothing changed, where a tensor
+    cannot take the batched kernels."""
+    if not entries:
+        return None
     params = [p for _, p in entries]
     plan = _sgd_plan(params)
     if plan is None or (flat is not None and (flat.dtype != torch.float32 or flat.device != plan.device
                                               or flat.numel() != plan.n or not flat.is_contiguous())):
-        return False
+        return None
     pp, gp, bp, flags, seen = plan.param_ptrs, plan.grad_ptrs, plan.buf_ptrs, plan.flags, plan.seen
     created = []
     ok = True
@@ -105,9 +116,8 @@ def _sgd_batched(entries, state, apply_grad_to_model, flat, write):
     if not ok:
         for param_state in created:
             del param_state["momentum_buffer"]
-        return False
-    plan.run(flat, grad_mode=not apply_grad_to_model, write=write)
-    return True
+        return None
+    return plan
 
 
 def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None):

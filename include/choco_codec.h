@@ -515,6 +515,78 @@ int choco_params_sgd(void* const* params, const void* const* grads, void* const*
                      const int32_t* flags, int32_t nseg, float* flat, int64_t n, int32_t mode,
                      void* stream);
 
+/* ------------------------------------------- DGC's optimizer half
+ * DGC._apply_gradient (pcode/optim/dgc.py:279-324) is apply_gradient with one more
+ * line: after the weight decay and before the momentum, each tensor's d_p is clipped by
+ * its own L2 norm (_clip_gradient, dgc.py:254-265, called at :308-310).  _compress then
+ * adds d_p to the error-feedback memory (:157) and, with mask_momentum, multiplies the
+ * momentum buffers by 1 - mask at the selected positions (:174-182).  Three entry
+ * points, each one launch per chunk of tensors, with the tables of choco_params_sgd.
+ *
+ * choco_params_sqnorm (dgc.py:256, grad.norm(p=2) of the d_p of :302-306):
+ *   norms[s] (DEVICE, fp32, nseg of them) = || d_s ||_2 with d = g, or
+ *   d = fma((float)wd, p, g) when weight_decay[s] != 0, narrowed for a 16-bit tensor as
+ *   choco_params_sgd narrows that line.  NOGRAD and zero-length tensors get 0.  Squares
+ *   and sums are fp64 (exact squares, no overflow); the result is sqrt in fp64, rounded
+ *   to fp32 and, for a 16-bit tensor, again to that dtype (grad.norm() returns the
+ *   gradient's dtype).  The summation order is fixed -- no floating-point atomics: every
+ *   (8192-element tile, tensor) pair stores one fp64 partial in the workspace and a
+ *   finish launch adds a tensor's partials in ascending order -- so two calls on the
+ *   same data give the same bits.  The workspace (choco_params_sqnorm_workspace_size
+ *   bytes, 8-byte aligned) needs no initialisation: everything read from it is written
+ *   by the same call.  The flags are those of choco_params_sgd (only NOGRAD matters).
+ *   Launches: choco_params_sqnorm_launches(nseg), of "param_sqnorm_kernel" per chunk and
+ *   one "param_sqnorm_finish_kernel".  Returns CHOCO_ERR_WORKSPACE for a short workspace.
+ *
+ * choco_params_sgd_clip (dgc.py:279-324): choco_params_sgd with, when norms != NULL,
+ *   for every tensor that has a gradient, between the weight decay and the momentum
+ *       thr = (float)clip_threshold
+ *       c   = norms[s] >= thr ? (1.0f / norms[s]) * thr : 1.0f
+ *       d   = c * d
+ *   -- torch's `threshold / grad_norm * grad` (dgc.py:263-264): an fp32 comparison, a
+ *   correctly rounded reciprocal times the threshold, one fp32 multiply per element
+ *   (narrowed for a 16-bit tensor).  A NaN norm compares false (unchanged); an inf norm
+ *   gives c = 0.  clip_threshold is clip_grad_val / sqrt(n_nodes), computed by the host
+ *   in double (dgc.py:258-262); with norms != NULL it must be finite and > 0 as the
+ *   fp32 value the kernel compares with.
+ *   CHOCO_SGD_MODE_ADD_FLAT (grad mode only, flat != NULL): flat[i] = flat[i] + d, an
+ *   fp32 add -- `_grad = grad + memory` (dgc.py:157) with the error-feedback memory as
+ *   the flat buffer.  choco_params_sgd itself rejects the bit.
+ *
+ * choco_params_mask (dgc.py:174-182): values[k] / indices[k] (DEVICE; global, ascending)
+ *   are a segmented selection with k_per_seg[s] (HOST) slots for tensor s; lens, dtypes:
+ *   the layout; bufs[s] (HOST table of DEVICE pointers, NULL entries allowed): the
+ *   momentum buffer of tensor s, of dtype dtypes[s].  For every slot j of tensor s whose
+ *   index i lies in the tensor's flat range:
+ *       bufs[s][i - off_s] = buf * 0.0f                  buf.mul_(1 - mask): -3 -> -0,
+ *                                                        inf / NaN -> NaN
+ *       memory[i] = values[j] + (-values[j])             when memory != NULL (DEVICE, n)
+ *   the latter being what choco_sparse_accumulate with -values leaves.  Other indices
+ *   are skipped.  Only selected elements are written.  Launches:
+ *   choco_params_mask_launches(nseg) of "param_mask_kernel".
+ *
+ * All three check every argument before the first launch without a HIP call. */
+#define CHOCO_SGD_MODE_ADD_FLAT 8
+size_t choco_params_sqnorm_workspace_size(int32_t nseg, int64_t n);
+int choco_params_sqnorm_launches(int32_t nseg);
+/* pcode/optim/dgc.py:254-256, :302-306 */
+int choco_params_sqnorm(const void* const* params, const void* const* grads, const int64_t* lens,
+                        const int32_t* dtypes, const double* weight_decay, const int32_t* flags,
+                        int32_t nseg, int64_t n, float* norms, void* ws, size_t ws_bytes,
+                        void* stream);
+/* pcode/optim/dgc.py:279-324, :157 */
+int choco_params_sgd_clip(void* const* params, const void* const* grads, void* const* bufs,
+                          const int64_t* lens, const int32_t* dtypes, const double* lr,
+                          const double* weight_decay, const double* momentum,
+                          const double* dampening, const int32_t* flags, int32_t nseg, float* flat,
+                          int64_t n, int32_t mode, const float* norms, double clip_threshold,
+                          void* stream);
+int choco_params_mask_launches(int32_t nseg);
+/* pcode/optim/dgc.py:174-182 */
+int choco_params_mask(void* const* bufs, const int64_t* lens, const int32_t* dtypes,
+                      const int64_t* k_per_seg, int32_t nseg, const float* values,
+                      const int32_t* indices, int64_t k, float* memory, int64_t n, void* stream);
+
 /* ------------------------------------------- fused gossip step + compress
  * ParallelCHOCO_V.step's update_params_from_neighbor -> compress sequence
  * (pcode/optim/parallel_choco_v.py:116-142 -> :229-240, optim/utils.py:67-72) in

@@ -13,6 +13,8 @@ VARIANTS = {
     "stamps": ["CHOCO_STAMPS=1"],
     # every bounded wait of the exact fallback gives up at once: tools/status_probe.py
     "poll1": ["CHOCO_POLL_BUDGET=1"],
+    # the per-tensor norm pass with non-temporal loads: tools/dgc_step_probe.py --norm-ab
+    "sqnorm_nt": ["CHOCO_SQNORM_NT=1"],
 }
 
 
