@@ -1130,6 +1130,78 @@ class ParamSgdPlan:
                                           _ptr(flat), self.n, mode, _stream(self.device)), "choco_params_sgd")
 
 
+    def mix(self, srcs, weights, lr=0.0, mode=0, ext_a=0.0, ext_b=0.0, flat_out=None, x_out=None):
+        """One choco_params_mix over the plan's parameter and gradient pointers as they stand
+        (params_mix describes the arguments)."""
+        _mix_call(srcs, weights, self.param_ptrs, self.grad_ptrs, self.lens, self.dts, self.nseg, self.n, self.device,
+                  lr, mode, ext_a, ext_b, flat_out, x_out)
+
+
+# ----------------------------------------------------------------------------- neighbour-weighted mix
+MIX_GRAD_SUB, MIX_GRAD_FMA, MIX_WRITE_PARAMS, MIX_EXTRAPOLATE = 1, 2, 4, 8  # CHOCO_MIX_*
+
+
+def params_mix_launches(nseg, nsrc):
+    """Launches one params_mix of `nsrc` sources over `nseg` tensors takes."""
+    return int(lib().choco_params_mix_launches(int(nseg), int(nsrc)))
+
+
+def _mix_call(srcs, weights, param_ptrs, grad_ptrs, lens, dts, nseg, n, dev, lr, mode, ext_a, ext_b, flat_out, x_out):
+    srcs = list(srcs)
+    nsrc = len(srcs)
+    if len(weights) != nsrc:
+        raise RuntimeError(f"params_mix: {len(weights)} weights for {nsrc} sources")
+    named = [(f"source {r}", t) for r, t in enumerate(srcs)]
+    named += [(name, t) for name, t in (("flat_out", flat_out), ("x_out", x_out)) if t is not None]
+    for name, t in named:
+        _require(t, torch.float32, name)
+        if t.device != dev or t.numel() != n:
+            raise RuntimeError(f"{name} must hold {n} elements on {dev}")
+    src_ptrs = (ctypes.c_void_p * max(nsrc, 1))(*[t.data_ptr() for t in srcs])
+    w = (ctypes.c_double * max(nsrc, 1))(*[float(v) for v in weights])
+    _lib.check(lib().choco_params_mix(src_ptrs, w, nsrc, param_ptrs, grad_ptrs, lens, dts, nseg, float(lr),
+                                      float(ext_a), float(ext_b), int(mode), _ptr(flat_out), _ptr(x_out), n,
+                                      _stream(dev)), "choco_params_mix")
+
+
+def params_mix(srcs, weights, params=None, grads=None, lr=0.0, mode=0, ext_a=0.0, ext_b=0.0, flat_out=None,
+               x_out=None, plan=None):
+    """The neighbour-weighted model mix sum(src_r * w_r) with the tail one of the reference's
+    optimizers puts behind it, one batched launch per chunk of tensors (include/choco_codec.h,
+    choco_params_mix): m = 0 + src_0 * w_0, m += src_r * w_r in the given order (srcs: flat fp32
+    tensors of one size, 1 to 64 of them; weights: Python floats), then
+        MIX_GRAD_SUB: m -= lr * grads (two roundings, dcd_psgd.py:124) or
+        MIX_GRAD_FMA: m.add_(grads, alpha=-lr) (fused, ecd_psgd.py:131-133);
+        MIX_WRITE_PARAMS: params = m (the unpack); MIX_EXTRAPOLATE: flat_out = ext_a * old
+        params + ext_b * m in place of m; x_out = the old params, packed.
+    params / grads: lists of tensors laid out back to back in the flat buffers (None: the
+    sources are mixed as one flat tensor into flat_out).  Returns the plan (pass it back in to
+    reuse its tables)."""
+    srcs = list(srcs)
+    if not srcs:
+        raise RuntimeError("params_mix needs at least one source")
+    if params is None:
+        if grads is not None:
+            raise RuntimeError("params_mix: grads without params")
+        n = srcs[0].numel()
+        lens, dts = (ctypes.c_int64 * 1)(n), (ctypes.c_int32 * 1)(0)
+        _mix_call(srcs, weights, None, None, lens, dts, 1, n, srcs[0].device, lr, mode, ext_a, ext_b, flat_out, x_out)
+        return None
+    params = list(params)
+    if plan is None:
+        plan = ParamSgdPlan(params)
+    elif not plan.holds(params):
+        raise RuntimeError("the plan was built for another parameter list")
+    grads = _per_tensor(grads, plan.nseg, "grads")
+    for i, (p, g) in enumerate(zip(params, grads)):
+        if g is not None and not plan.fits(i, g):
+            raise RuntimeError(f"grad {i} must match its parameter's dtype, device and size, and be contiguous")
+        plan.param_ptrs[i] = p.data_ptr()
+        plan.grad_ptrs[i] = g.data_ptr() if g is not None else None
+    plan.mix(srcs, weights, lr, mode, ext_a, ext_b, flat_out, x_out)
+    return plan
+
+
 def _per_tensor(v, nseg, name):
     if isinstance(v, (list, tuple)):
         if len(v) != nseg:

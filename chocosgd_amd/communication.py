@@ -15,6 +15,8 @@ unlike the reference nothing is re-cast to the default float dtype.
 import torch
 import torch.distributed as dist
 
+from . import codec
+
 
 def recover_device(data, device=None):
     return data.to(device) if device is not None else data
@@ -74,13 +76,28 @@ class DecentralizedAggregation(object):
             if op == "avg":
                 return sum(local_data.values()) / (self.world_size + 1)
             if op == "weighted":
-                return sum(t * self.neighbors_info[r] for r, t in local_data.items())
+                return self._weighted(local_data)
             if op == "get_raw_sync_data":
                 return local_data
             raise NotImplementedError("op {} is not supported yet.".format(op))
         if op == "get_raw_sync_data":
             return reqs, local_data
         raise NotImplementedError("op {} is not supported yet.".format(op))
+
+    def _weighted(self, local_data):
+        """sum(t * w_r) in local_data's order (communication.py:271-277).  Contiguous fp32 ROCm
+        tensors take one codec.params_mix call, with the same bits as the expression; CPU
+        tensors and everything else keep the expression."""
+        tensors = list(local_data.values())
+        first = tensors[0]
+        if (first.is_cuda and first.numel() > 0 and len(tensors) <= 64
+                and all(t.dtype == torch.float32 and t.device == first.device and t.shape == first.shape
+                        and t.is_contiguous() for t in tensors)):
+            out = torch.empty_like(first)
+            codec.params_mix([t.view(-1) for t in tensors], [self.neighbors_info[r] for r in local_data],
+                             flat_out=out.view(-1))
+            return out
+        return sum(t * self.neighbors_info[r] for r, t in local_data.items())
 
     def complete_wait(self, reqs):
         for req in reqs:

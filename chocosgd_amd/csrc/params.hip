@@ -127,17 +127,10 @@ CHOCO_DEV void param_span(void* p, float* flat, int64_t o0, int64_t a, int64_t b
 template <bool PACK>
 CHOCO_DEV void param_tile(const ParamTable& tb, float* flat, int64_t tile0, int flat16) {
   const int nt = tb.nt;
-  const int64_t t = tile0 + blockIdx.x;
-  const int64_t tlo = i64max(t * kPbTile, tb.off[0]);
-  const int64_t thi = i64min((t + 1) * kPbTile, tb.off[nt]);
-  if (tlo >= thi) return;
-  // the first s in [1, nt] with off[s] > tlo (off[nt] >= thi > tlo): tensor s - 1 holds tlo
-  int lo = 1, hi = nt;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (tb.off[mid] > tlo) hi = mid; else lo = mid + 1;
-  }
-  for (int s = lo - 1; s < nt; ++s) {
+  int64_t tlo, thi;
+  const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
+  if (s0 < 0) return;
+  for (int s = s0; s < nt; ++s) {
     const int64_t o0 = tb.off[s];
     if (o0 >= thi) break;
     const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);

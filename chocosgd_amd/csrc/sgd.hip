@@ -105,17 +105,6 @@ CHOCO_DEV void sgd_math(const SgdTensor& t, float p, float g, float b, float& bu
   out = t.grad_mode ? d : rnd<DT>(fmaf(t.nlr, d, p));
 }
 
-template <int DT>
-CHOCO_DEV float ld1(const void* base, int64_t j) {
-  if (DT == CHOCO_DT_F32) return reinterpret_cast<const float*>(base)[j];
-  return widen16<DT>(reinterpret_cast<const unsigned short*>(base)[j]);
-}
-template <int DT>
-CHOCO_DEV void st1(void* base, int64_t j, float v) {
-  if (DT == CHOCO_DT_F32) reinterpret_cast<float*>(base)[j] = v;
-  else reinterpret_cast<unsigned short*>(base)[j] = narrow16<DT>(v);
-}
-
 // flat index i, element j of the tensor
 template <int DT>
 CHOCO_DEV void sgd_elem(const SgdTensor& t, int64_t i, int64_t j) {
@@ -128,46 +117,6 @@ CHOCO_DEV void sgd_elem(const SgdTensor& t, int64_t i, int64_t j) {
   if (t.wr_p) st1<DT>(t.p, j, out);
   if (t.wr_g) st1<DT>(t.g, j, out);
   if (t.flat) t.flat[i] = t.add_flat ? t.flat[i] + out : out;
-}
-
-// a group of 8 elements as loaded: two float4 (fp32) or one 16-byte vector of halves
-struct Raw8 {
-  float4 lo, hi;
-  choco_u16x8 h;
-};
-template <int DT>
-CHOCO_DEV void ld8(Raw8& r, const void* base, int64_t j) {
-  if (DT == CHOCO_DT_F32) {
-    const float* s = reinterpret_cast<const float*>(base) + j;
-    r.lo = ld_nt4(s);
-    r.hi = ld_nt4(s + 4);
-  } else {
-    r.h = __builtin_nontemporal_load(
-        reinterpret_cast<const choco_u16x8*>(reinterpret_cast<const unsigned short*>(base) + j));
-  }
-}
-template <int DT>
-CHOCO_DEV void widen8(const Raw8& r, float (&v)[8]) {
-  if (DT == CHOCO_DT_F32) {
-    v[0] = r.lo.x; v[1] = r.lo.y; v[2] = r.lo.z; v[3] = r.lo.w;
-    v[4] = r.hi.x; v[5] = r.hi.y; v[6] = r.hi.z; v[7] = r.hi.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = widen16<DT>(r.h[k]);
-  }
-}
-template <int DT>
-CHOCO_DEV void st8(void* base, int64_t j, const float (&v)[8]) {
-  if (DT == CHOCO_DT_F32) {
-    float* s = reinterpret_cast<float*>(base) + j;
-    st_nt4(s, make_float4(v[0], v[1], v[2], v[3]));
-    st_nt4(s + 4, make_float4(v[4], v[5], v[6], v[7]));
-  } else {
-    choco_u16x8 o;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o[k] = narrow16<DT>(v[k]);
-    __builtin_nontemporal_store(o, reinterpret_cast<choco_u16x8*>(reinterpret_cast<unsigned short*>(base) + j));
-  }
 }
 
 // Flat elements [a, b) of a tensor at flat offset o0, a < b inside this workgroup's tile.
@@ -232,18 +181,11 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
                                                                int32_t flat16, int32_t mode, const float* norms,
                                                                float thr) {
   const int nt = tb.nt;
-  const int64_t tile = tile0 + blockIdx.x;
-  const int64_t tlo = i64max(tile * kPbTile, tb.off[0]);
-  const int64_t thi = i64min((tile + 1) * kPbTile, tb.off[nt]);
-  if (tlo >= thi) return;
-  // the first s in [1, nt] with off[s] > tlo (off[nt] >= thi > tlo): tensor s - 1 holds tlo
-  int lo = 1, hi = nt;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (tb.off[mid] > tlo) hi = mid; else lo = mid + 1;
-  }
+  int64_t tlo, thi;
+  const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
+  if (s0 < 0) return;
   const bool grad_mode = (mode & CHOCO_SGD_MODE_GRAD) != 0;
-  for (int s = lo - 1; s < nt; ++s) {
+  for (int s = s0; s < nt; ++s) {
     const int64_t o0 = tb.off[s];
     if (o0 >= thi) break;
     const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);
@@ -532,17 +474,12 @@ __global__ __launch_bounds__(kPbThreads) void param_sqnorm_kernel(const NormTabl
     }
   }
   const int64_t tile = tile0 + blockIdx.x;
-  const int64_t tlo = i64max(tile * kPbTile, tb.off[0]);
-  const int64_t thi = i64min((tile + 1) * kPbTile, tb.off[nt]);
-  if (tlo >= thi) return;
-  int lo = 1, hi = nt;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (tb.off[mid] > tlo) hi = mid; else lo = mid + 1;
-  }
+  int64_t tlo, thi;
+  const int s0 = tile_first_tensor(tb.off, nt, tile, tlo, thi);
+  if (s0 < 0) return;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   int nshort = 0;
-  for (int s = lo - 1; s < nt; ++s) {
+  for (int s = s0; s < nt; ++s) {
     const int64_t o0 = tb.off[s];
     if (o0 >= thi) break;
     const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);

@@ -12,10 +12,15 @@ compress over the flat buffers and this codec's packed wire; the receiver is
 the fused accumulate with weight 1 (x[idx] + 1.0f * v = x[idx] + v bit for bit;
 the sign receiver uses torch's add_(u, alpha) rounding, dcd_psgd.py:446).  The
 exchange keeps the reference's blocking `_agg(..., force_wait=True)` call.
+
+`fused_step(...)` is `DCD_PSGD.step` end to end (dcd_psgd.py:96-144): the batched
+apply_gradient, one neighbour-mix launch for the half params and the packed
+params (codec.params_mix), then compress / sync / uncompress and the unpack;
+`step_loop(...)` is the same step as one torch op per line (CPU tensors).
 """
 import torch
 
-from . import codec
+from . import codec, utils
 from .communication import recover_device
 from .parallel_choco import _Layout, _hdr_words, _seg_lens
 from .sparsification import _draw_seed, get_n_bits
@@ -41,6 +46,62 @@ class DCDCompressor(object):
 
     def uncompress(self, *args, **kargs):
         return self.compressor_fn.uncompress(*args, **kargs)
+
+
+def _own_rank(compressor):
+    return getattr(compressor, "compressor_fn", compressor).aggregator_fn.rank
+
+
+def _finish(compressor, sync_buffer, neighbor_hat_params, params):
+    """compress, sync, uncompress, and the local model taken from this rank's own replica
+    (dcd_psgd.py:127-144)."""
+    compressor.compress(sync_buffer)
+    compressor.sync(sync_buffer)
+    compressor.uncompress(sync_buffer, neighbor_hat_params)
+    return neighbor_hat_params[_own_rank(compressor)]
+
+
+def step_loop(compressor, param_groups, param_names, state, shapes, neighbor_hat_params, neighbors_info):
+    """DCD_PSGD.step (dcd_psgd.py:96-144) as the reference's op sequence, one torch op per line:
+    the path CPU tensors, and anything the batched kernels do not take, keep."""
+    entries = utils.step_entries(param_groups, param_names, "dcd.step_loop", need_grads=True)
+    utils.apply_gradient_loop(param_groups, state, False)
+    params = [p for _, p in entries]
+    sizes = [p.size() for p in params]
+    flatten_params = TensorBuffer([p.data for p in params], dtype=torch.float32)
+    flatten_grads = TensorBuffer([p.grad.data for p in params], dtype=torch.float32)
+    half = (utils.weighted_sum([h.buffer for h in neighbor_hat_params.values()],
+                               [neighbors_info[r] for r in neighbor_hat_params])
+            - param_groups[0]["lr"] * flatten_grads.buffer)
+    sync_buffer = {"original_shapes": shapes, "flatten_half_params": TensorBuffer.from_flat(half, sizes),
+                   "flatten_params": flatten_params}
+    own = _finish(compressor, sync_buffer, neighbor_hat_params, params)
+    flatten_params.buffer = own.buffer.clone()
+    flatten_params.unpack(params)
+    return sync_buffer["n_bits"]
+
+
+def fused_step(compressor, param_groups, param_names, state, shapes, neighbor_hat_params, neighbors_info):
+    """DCD_PSGD.step end to end (dcd_psgd.py:96-144): the batched
+    apply_gradient(apply_grad_to_model=False); ONE mix launch for :104-125, which writes the
+    half params sum(hat_r * w_r) - lr * d_p and packs the params beside them (the two inputs of
+    the compressor); this module's compress / sync / uncompress; and the batched unpack
+    straight from this rank's own replica (the reference clones it first).  lr is
+    param_groups[0]["lr"], as in the reference.  Returns n_bits.  Tensors the kernels do not
+    take run step_loop."""
+    entries = utils.step_entries(param_groups, param_names, "dcd.fused_step", need_grads=True)
+    plan = utils.grad_step_plan(entries, state, neighbor_hat_params)
+    if plan is None:
+        return step_loop(compressor, param_groups, param_names, state, shapes, neighbor_hat_params, neighbors_info)
+    params = [p for _, p in entries]
+    sizes = [p.size() for p in params]
+    half, packed = (torch.empty(plan.n, dtype=torch.float32, device=plan.device) for _ in range(2))
+    plan.mix([h.buffer for h in neighbor_hat_params.values()], [neighbors_info[r] for r in neighbor_hat_params],
+             lr=param_groups[0]["lr"], mode=codec.MIX_GRAD_SUB, flat_out=half, x_out=packed)
+    sync_buffer = {"original_shapes": shapes, "flatten_half_params": TensorBuffer.from_flat(half, sizes),
+                   "flatten_params": TensorBuffer.from_flat(packed, sizes)}
+    _finish(compressor, sync_buffer, neighbor_hat_params, params).unpack(params)
+    return sync_buffer["n_bits"]
 
 
 class _ConsumerBase(object):

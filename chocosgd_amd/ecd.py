@@ -9,10 +9,15 @@ message: hat <- (1 - 2/t) hat + (2/t) q  (t = local_index), in the reference's
 rounding (mul, then torch's fused add with alpha; the sign receiver folds 2/t
 into the per-tensor scale first, ecd_psgd.py:448-454).  Receivers are the
 *_extrapolate kernels of include/choco_codec.h.
+
+`fused_step(...)` is `ECD_PSGD.step` end to end (ecd_psgd.py:99-157): the batched
+apply_gradient, one neighbour-mix launch for the updated params and the
+extrapolated model (codec.params_mix), then compress / sync / uncompress;
+`step_loop(...)` is the same step as one torch op per line (CPU tensors).
 """
 import torch
 
-from . import codec
+from . import codec, utils
 from .communication import recover_device
 from .dcd import _ConsumerBase
 from .tensor_buffer import TensorBuffer
@@ -37,6 +42,53 @@ class ECDCompressor(object):
 
     def uncompress(self, *args, **kargs):
         return self.compressor_fn.uncompress(*args, **kargs)
+
+
+def _finish(compressor, sync_buffer, neighbor_hat_params, local_index):
+    compressor.compress(sync_buffer)
+    compressor.sync(sync_buffer)
+    compressor.uncompress(sync_buffer, neighbor_hat_params, local_index)
+    return sync_buffer["n_bits"]
+
+
+def step_loop(compressor, param_groups, param_names, state, shapes, neighbor_hat_params, neighbors_info, local_index):
+    """ECD_PSGD.step (ecd_psgd.py:99-157) as the reference's op sequence, one torch op per line:
+    the path CPU tensors, and anything the batched kernels do not take, keep."""
+    entries = utils.step_entries(param_groups, param_names, "ecd.step_loop", need_grads=True)
+    utils.apply_gradient_loop(param_groups, state, False)
+    params = [p for _, p in entries]
+    flatten_params = TensorBuffer([p.data for p in params], dtype=torch.float32)
+    flatten_grads = TensorBuffer([p.grad.data for p in params], dtype=torch.float32)
+    updated = TensorBuffer.from_flat(
+        utils.weighted_sum([h.buffer for h in neighbor_hat_params.values()],
+                           [neighbors_info[r] for r in neighbor_hat_params]), [p.size() for p in params])
+    updated.buffer.add_(flatten_grads.buffer, alpha=-param_groups[0]["lr"])
+    updated.unpack(params)
+    updated.buffer = (1 - 0.5 * local_index) * flatten_params.buffer + 0.5 * local_index * updated.buffer
+    sync_buffer = {"original_shapes": shapes, "flatten_updated_params": updated}
+    return _finish(compressor, sync_buffer, neighbor_hat_params, local_index)
+
+
+def fused_step(compressor, param_groups, param_names, state, shapes, neighbor_hat_params, neighbors_info, local_index):
+    """ECD_PSGD.step end to end (ecd_psgd.py:99-157): the batched
+    apply_gradient(apply_grad_to_model=False); ONE mix launch for :107-140, which writes the
+    updated model sum(hat_r * w_r) + (-lr) * d_p (fused, as add_(alpha=)) into the params and
+    the extrapolated model (1 - 0.5 t) * old params + 0.5 t * updated, t = local_index, into
+    the buffer the compressor takes; this module's compress / sync / uncompress.  lr is
+    param_groups[0]["lr"], as in the reference.  Returns n_bits.  Tensors the kernels do not
+    take run step_loop."""
+    entries = utils.step_entries(param_groups, param_names, "ecd.fused_step", need_grads=True)
+    plan = utils.grad_step_plan(entries, state, neighbor_hat_params)
+    if plan is None:
+        return step_loop(compressor, param_groups, param_names, state, shapes, neighbor_hat_params, neighbors_info,
+                         local_index)
+    updated = torch.empty(plan.n, dtype=torch.float32, device=plan.device)
+    plan.mix([h.buffer for h in neighbor_hat_params.values()], [neighbors_info[r] for r in neighbor_hat_params],
+             lr=param_groups[0]["lr"], mode=codec.MIX_GRAD_FMA | codec.MIX_WRITE_PARAMS | codec.MIX_EXTRAPOLATE,
+             ext_a=1 - 0.5 * local_index, ext_b=0.5 * local_index, flat_out=updated)
+    sync_buffer = {"original_shapes": shapes,
+                   "flatten_updated_params": TensorBuffer.from_flat(updated, [p.size() for _, p in entries])}
+    return _finish(compressor, sync_buffer, neighbor_hat_params, local_index)
 
 
 def _coeffs(local_index):

@@ -3,6 +3,7 @@ CHOCO half)."""
 import torch
 
 from . import codec
+from .sparsification import get_n_bits
 from .tensor_buffer import TensorBuffer, flatten
 
 
@@ -221,16 +222,91 @@ def _sgd_packed(param_groups, param_names, state):
     """fused_step(state=...): apply_gradient and the pack of the new params in one launch.
     Returns the flat TensorBuffer, or None after the per-tensor loop has updated the params
     (tensors the batched kernel does not take: recover_params packs them as before)."""
-    if len(param_names) != len(param_groups) or any(len(g["params"]) != 1 for g in param_groups) \
-            or sorted(idx for idx, _ in param_names) != list(range(len(param_groups))):
-        raise RuntimeError("fused_step(state=...) needs one parameter per group, each named once in param_names")
-    entries = [(param_groups[idx], param_groups[idx]["params"][0]) for idx, _ in param_names]
+    entries = step_entries(param_groups, param_names, "fused_step(state=...)")
     dev = entries[0][1].device
     flat = torch.empty(sum(p.numel() for _, p in entries), dtype=torch.float32, device=dev)
     if dev.type == "cuda" and _sgd_batched(entries, state, True, flat, write=False):
         return TensorBuffer.from_flat(flat, [p.size() for _, p in entries])
     apply_gradient_loop(param_groups, state, True)
     return None
+
+
+def step_entries(param_groups, param_names, what, need_grads=False):
+    """[(group, param)] in param_names' order for a step that runs apply_gradient itself: every
+    group must hold one parameter, named once in param_names, as the reference's groups do.
+    need_grads: a parameter without a gradient raises (the flat gradient buffer the reference
+    builds with get_data(is_get_grad=True) has no slot for it)."""
+    if len(param_names) != len(param_groups) or any(len(g["params"]) != 1 for g in param_groups) \
+            or sorted(idx for idx, _ in param_names) != list(range(len(param_groups))):
+        raise RuntimeError(f"{what} needs one parameter per group, each named once in param_names")
+    entries = [(param_groups[idx], param_groups[idx]["params"][0]) for idx, _ in param_names]
+    if need_grads:
+        for idx, name in param_names:
+            if param_groups[idx]["params"][0].grad is None:
+                raise RuntimeError(f"{what}: parameter {name!r} has no gradient")
+    return entries
+
+
+def mix_sources(buffers, n, device):
+    """Whether codec.params_mix takes `buffers` (flat tensors) as its sources for a layout of n
+    elements on `device`."""
+    return (device.type == "cuda" and 1 <= len(buffers) <= 64
+            and all(b.is_cuda and b.device == device and b.dtype == torch.float32 and b.numel() == n
+                    and b.is_contiguous() for b in buffers))
+
+
+def grad_step_plan(entries, state, neighbor_hat_params):
+    """The first line of DCD_PSGD.step / ECD_PSGD.step, apply_gradient(apply_grad_to_model=False),
+    as the batched launch where the mix kernel can follow it: returns the plan whose tables the
+    mix reuses, or None, with nothing changed, where the kernels do not take the tensors (CPU
+    tensors, other dtypes, replicas that are not flat fp32 buffers of the model's size)."""
+    params = [p for _, p in entries]
+    hats = [h.buffer for h in neighbor_hat_params.values()]
+    if not mix_sources(hats, sum(p.numel() for p in params), params[0].device):
+        return None
+    plan = _sgd_fill(entries, state, False, None)
+    if plan is not None:
+        plan.run(None, grad_mode=True, write=True)
+    return plan
+
+
+def weighted_sum(buffers, weights):
+    """sum([b * w for ...]): the reference's own expression, one torch op per term."""
+    return sum([b * w for b, w in zip(buffers, weights)])
+
+
+def dpsgd_step_loop(param_groups, param_names, state, aggregator):
+    """dpsgd_step as the reference's op sequence (sgd.py:94-121), one torch op per line: the path
+    CPU tensors, and anything the batched kernels do not take, keep."""
+    apply_gradient_loop(param_groups, state, True)
+    params, flatten_params = recover_params(param_groups, param_names, get_hat_params=False)
+    flatten_params.buffer = aggregator._agg(flatten_params.buffer, op="weighted")
+    flatten_params.unpack(params)
+    return get_n_bits(flatten_params.buffer)
+
+
+def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info):
+    """The decentralized branch of SGD.step (sgd.py:94-121), plain D-PSGD: apply_gradient fused
+    with the pack of the new params (one launch; the params themselves are not written yet),
+    the exchange of the flat fp32 buffer (_agg(op="get_raw_sync_data")), and ONE mix launch
+    that writes sum(x_r * w_r) straight into the params (communication.py:271-277 and the
+    unpack of sgd.py:118).  Returns n_bits.  Tensors the kernels do not take run
+    dpsgd_step_loop."""
+    entries = step_entries(param_groups, param_names, "dpsgd_step")
+    params = [p for _, p in entries]
+    dev = params[0].device
+    flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
+    plan = _sgd_fill(entries, state, True, flat)
+    if plan is None:
+        return dpsgd_step_loop(param_groups, param_names, state, aggregator)
+    plan.run(flat, grad_mode=False, write=False)
+    local_data = aggregator._agg(flat, op="get_raw_sync_data")
+    srcs = list(local_data.values())
+    weights = [neighbors_info[r] for r in local_data]
+    # the running sum of more than one launch's sources needs a flat buffer of its own
+    run = torch.empty_like(flat) if len(srcs) > 8 else None
+    plan.mix(srcs, weights, mode=codec.MIX_WRITE_PARAMS, flat_out=run)
+    return get_n_bits(flat)
 
 
 def update_params_from_neighbor(neighbor_hat_params, flatten_params, consensus_stepsize, self_rank):

@@ -587,6 +587,61 @@ int choco_params_mask(void* const* bufs, const int64_t* lens, const int32_t* dty
                       const int64_t* k_per_seg, int32_t nseg, const float* values,
                       const int32_t* indices, int64_t k, float* memory, int64_t n, void* stream);
 
+/* ------------------------------------------- neighbour-weighted model mix
+ * The dense line three decentralized optimizers of the reference share,
+ *     sum([hat_r.buffer * neighbors_info[r] for r, hat_r in ...])
+ * with what follows it in each, as ONE launch per chunk of tensors:
+ *   DCD-PSGD (pcode/optim/dcd_psgd.py:114-125): `- lr * flatten_grads.buffer`, two
+ *     roundings; the params are packed beside it for the compressor.
+ *       mode GRAD_SUB, flat_out = half params, x_out = packed params
+ *   ECD-PSGD (pcode/optim/ecd_psgd.py:118-140): `.add_(grads, alpha=-lr)` (fused),
+ *     unpack(params), then (1 - 0.5 t) * old params + 0.5 t * updated.
+ *       mode GRAD_FMA | WRITE_PARAMS | EXTRAPOLATE, flat_out = the extrapolated model
+ *   D-PSGD (pcode/optim/sgd.py:94-121, _agg(op="weighted") of
+ *     pcode/utils/communication.py:271-277), then unpack(params).
+ *       mode WRITE_PARAMS (and / or flat_out)
+ * srcs[r] (HOST table of nsrc DEVICE pointers): flat fp32 buffers of n elements;
+ * weights[r] (HOST doubles) are used as (float)weights[r].  The tensor tables are those
+ * of choco_params_sgd: tensor s holds lens[s] elements of dtype dtypes[s] in params[s] and
+ * grads[s] and owns flat elements [sum(lens[0..s)), + lens[s]).  Per element (flat index
+ * i, element j of tensor s), every line one reference op with one rounding:
+ *     m = 0.0f + rn(src[0][i] * w[0])          Python's sum() starts at int 0: -0 -> +0
+ *     m = rn(m + rn(src[r][i] * w[r]))         r = 1 .. nsrc - 1, in the given order
+ *     GRAD_SUB:     m = rn(m - rn((float)lr * g))       g = grads[s][j] widened
+ *     GRAD_FMA:     m = fmaf((float)(-lr), g, m)
+ *     WRITE_PARAMS: params[s][j] = m narrowed round-to-nearest-even (the unpack)
+ *     EXTRAPOLATE:  x = old params[s][j] widened, read before the store above
+ *                   z = rn(rn((float)ext_a * x) + rn((float)ext_b * m))   the un-narrowed m
+ *     flat_out[i] = EXTRAPOLATE ? z : m        (if not NULL)
+ *     x_out[i]    = old params[s][j] widened   (if not NULL)
+ * A zero weight is multiplied, not skipped (inf * 0 = NaN); NaN and inf propagate.
+ * flat_out and x_out must not overlap a source or each other: NOT checked.  Each thread
+ * reads params before it writes them.  nsrc may be 1 .. 64: more than 8 sources run as
+ * successive launches of 8 whose earlier ones leave the running sum in flat_out (then
+ * required) and whose last one applies the tail -- the same bits as one sum.  `params`
+ * may be NULL when neither the mode nor x_out touches them, `grads` without a GRAD bit;
+ * lens = {n}, nseg = 1 is a flat buffer.  Only the bytes of the layout's own elements are
+ * written; pointers need their element's alignment only.  Every argument is checked
+ * before the first launch without a HIP call -- null srcs / weights / lens / dtypes
+ * tables, nsrc outside 1..64, a NULL source, nseg <= 0, negative lengths or lengths that
+ * do not sum to n, unknown dtype or mode bits, both GRAD bits, a GRAD bit with a NULL
+ * grads table or grad, EXTRAPOLATE / WRITE_PARAMS / x_out with a NULL params table or
+ * param, nothing to write, EXTRAPOLATE or nsrc > 8 with flat_out == NULL, misaligned
+ * pointers, a non-finite lr with a GRAD bit -- and a bad one returns CHOCO_ERR_INVALID
+ * and launches nothing.  A call takes choco_params_mix_launches(nseg, nsrc) launches of
+ * "param_mix_kernel" (0 for arguments the call would refuse). */
+#define CHOCO_MIX_GRAD_SUB 1
+#define CHOCO_MIX_GRAD_FMA 2
+#define CHOCO_MIX_WRITE_PARAMS 4
+#define CHOCO_MIX_EXTRAPOLATE 8
+int choco_params_mix_launches(int32_t nseg, int32_t nsrc);
+/* pcode/optim/dcd_psgd.py:114-125, ecd_psgd.py:118-140, sgd.py:94-121 */
+int choco_params_mix(const float* const* srcs, const double* weights, int32_t nsrc,
+                     void* const* params, const void* const* grads,
+                     const int64_t* lens, const int32_t* dtypes, int32_t nseg,
+                     double lr, double ext_a, double ext_b, int32_t mode,
+                     float* flat_out, float* x_out, int64_t n, void* stream);
+
 /* ------------------------------------------- fused gossip step + compress
  * ParallelCHOCO_V.step's update_params_from_neighbor -> compress sequence
  * (pcode/optim/parallel_choco_v.py:116-142 -> :229-240, optim/utils.py:67-72) in
