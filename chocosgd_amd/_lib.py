@@ -70,6 +70,7 @@ SIGNATURES = {
                                                    _vp, _vp]),
     "choco_sparse_extrapolate": (_c_i32, [_vp, _vp, _c_i64, _vp, _c_i64, _c_f32, _c_f32, _vp, _vp]),
     "choco_sign_local_decode": (_c_i32, [_vp, _c_i64, _vp, _c_i32, _vp, _vp, _vp]),
+    "choco_sign_local_residual": (_c_i32, [_vp, _c_i64, _vp, _c_i32, _vp, _vp, _vp, _vp]),
     "choco_qsgd_packed_bytes": (_c_i64, [_c_i64, _c_i32]),
     "choco_qsgd_workspace_size": (_c_sz, [_c_i32]),
     "choco_qsgd_compress": (_c_i32, [_vp, _vp, _c_i64, _vp, _c_i32, _c_i32, _c_i32, _vp, _vp, _c_u64, _c_u64,
@@ -102,6 +103,8 @@ SIGNATURES = {
     "choco_params_mix_launches": (_c_i32, [_c_i32, _c_i32]),
     "choco_params_mix": (_c_i32, [_pp, _p_f64, _c_i32, _pp, _pp, _p_i64, _p_i32, _c_i32, _c_f64, _c_f64, _c_f64,
                                   _c_i32, _vp, _vp, _c_i64, _vp]),
+    "choco_params_ef_launches": (_c_i32, [_c_i32]),
+    "choco_params_ef": (_c_i32, [_pp, _p_i64, _p_i32, _c_i32, _vp, _c_i64, _c_i32, _c_f64, _c_f64, _vp]),
     "choco_gossip_topk_compress": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
     "choco_gossip_topk_compress_accumulate": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i64, _vp, _vp, _c_i32,
                                                        _c_f32, _vp, _c_sz, _vp]),

@@ -777,6 +777,26 @@ def sign_local_decode(x, norms, seg_off=None, nseg=1):
     return out
 
 
+def sign_local_residual(x, norms, seg_off=None, nseg=1, local_out=None, resid_out=None):
+    """The error feedback of a sign message in one pass: resid_out = x - u with u =
+    sign_local_decode's value, and local_out = u when given (deep_squeeze.py:416-422 with :115;
+    ef_sign_sgd.py:153 with :104-106).  resid_out may be x itself (in place; None: a new
+    tensor); local_out may alias neither.  Returns resid_out."""
+    _require(x, torch.float32, "x")
+    _require(norms, torch.float32, "norms")
+    if resid_out is None:
+        resid_out = torch.empty_like(x)
+    for name, t in (("local_out", local_out), ("resid_out", resid_out)):
+        if t is not None:
+            _require(t, torch.float32, name)
+            if t.device != x.device or t.numel() != x.numel():
+                raise RuntimeError(f"{name} must hold {x.numel()} elements on {x.device}")
+    _lib.check(lib().choco_sign_local_residual(_ptr(x), x.numel(), _ptr(seg_off), int(nseg), _ptr(norms),
+                                               _ptr(local_out), _ptr(resid_out), _stream(x.device)),
+               "choco_sign_local_residual")
+    return resid_out
+
+
 # ----------------------------------------------------------------------------- QSGD
 def qsgd_packed_bytes(n, q):
     return int(lib().choco_qsgd_packed_bytes(int(n), int(q)))
@@ -1136,6 +1156,11 @@ class ParamSgdPlan:
         _mix_call(srcs, weights, self.param_ptrs, self.grad_ptrs, self.lens, self.dts, self.nseg, self.n, self.device,
                   lr, mode, ext_a, ext_b, flat_out, x_out)
 
+    def ef(self, flat, mode, lr=0.0, divisor=1.0):
+        """One choco_params_ef over the plan's parameter pointers as they stand (params_ef
+        describes the arguments)."""
+        _ef_call(self.param_ptrs, self.lens, self.dts, self.nseg, self.n, self.device, flat, mode, lr, divisor)
+
 
 # ----------------------------------------------------------------------------- neighbour-weighted mix
 MIX_GRAD_SUB, MIX_GRAD_FMA, MIX_WRITE_PARAMS, MIX_EXTRAPOLATE = 1, 2, 4, 8  # CHOCO_MIX_*
@@ -1199,6 +1224,47 @@ def params_mix(srcs, weights, params=None, grads=None, lr=0.0, mode=0, ext_a=0.0
         plan.param_ptrs[i] = p.data_ptr()
         plan.grad_ptrs[i] = g.data_ptr() if g is not None else None
     plan.mix(srcs, weights, lr, mode, ext_a, ext_b, flat_out, x_out)
+    return plan
+
+
+# ----------------------------------------------------------------------------- error-feedback lines
+EF_ACCUM, EF_APPLY, EF_DIV, EF_SCALE = 1, 2, 4, 8  # CHOCO_EF_*
+
+
+def params_ef_launches(nseg):
+    """Launches one params_ef over `nseg` tensors takes."""
+    return int(lib().choco_params_ef_launches(int(nseg)))
+
+
+def _ef_call(param_ptrs, lens, dts, nseg, n, dev, flat, mode, lr, divisor):
+    _require(flat, torch.float32, "flat")
+    if flat.device != dev or flat.numel() != n:
+        raise RuntimeError(f"flat must hold {n} elements on {dev}")
+    _lib.check(lib().choco_params_ef(param_ptrs, lens, dts, nseg, _ptr(flat), n, int(mode), float(lr), float(divisor),
+                                     _stream(dev)), "choco_params_ef")
+
+
+def params_ef(params, flat, mode, lr=0.0, divisor=1.0, plan=None):
+    """The dense lines around the compressors of the two error-feedback optimizers, straight
+    between the parameter tensors and a flat fp32 buffer, one batched launch per chunk of
+    tensors (include/choco_codec.h, choco_params_ef):
+        EF_ACCUM: flat += params (the pack and memory.buffer += params_tb.buffer,
+                  deep_squeeze.py:101-108); the params are read only.
+        EF_APPLY: params += flat, narrowed once (deep_squeeze.py:125-126), after
+            | EF_DIV:   flat /= divisor, a true division, written back (ef_sign_sgd.py:218)
+            | EF_SCALE: the addend is (-lr) * flat, not written back (ef_sign_sgd.py:119).
+    params: tensors laid out back to back in flat.  Returns the plan (pass it back in to reuse
+    its tables)."""
+    params = list(params)
+    if plan is None:
+        plan = ParamSgdPlan(params)
+    elif not plan.holds(params):
+        raise RuntimeError("the plan was built for another parameter list")
+    for i, p in enumerate(params):
+        if not p.is_contiguous():
+            raise RuntimeError(f"param {i} must be contiguous")
+        plan.param_ptrs[i] = p.data_ptr()
+    plan.ef(flat, mode, lr, divisor)
     return plan
 
 

@@ -1284,10 +1284,15 @@ __global__ __launch_bounds__(kSignThreads) void sign_recv_rows_kernel(PlaneMsgs 
 // per thread; the segment is found once per workgroup and walked per element only
 // when the workgroup straddles a boundary.
 constexpr int kLocalTile = kSignThreads * 4;
-__global__ __launch_bounds__(kSignThreads) void sign_local_kernel(const float* __restrict__ x, int64_t n,
-                                                                  const int64_t* __restrict__ seg_off, int nseg,
-                                                                  const float* __restrict__ norms,
-                                                                  float* __restrict__ out) {
+// u of one element: v = x[e] of a segment with `numel` elements and L1 norm `norm`
+CHOCO_DEV float sign_local_u(float norm, float v, int64_t numel) {
+  const float sg = v > 0.f ? 1.0f : (v < 0.f ? -1.0f : 0.0f);  // torch.sign: +-0 and NaN -> +0
+  return (norm * sg) / (float)numel;
+}
+// One workgroup's tile: out[e] = u (out not NULL), resid[e] = x[e] - u (resid not NULL; it may
+// be x itself: each thread reads an element before it writes it).
+CHOCO_DEV void sign_local_tile(const float* x, int64_t n, const int64_t* __restrict__ seg_off, int nseg,
+                               const float* __restrict__ norms, float* __restrict__ out, float* resid) {
   __shared__ int s_seg[2];
   const int64_t t0 = (int64_t)blockIdx.x * kLocalTile;
   const int64_t t1 = std::min<int64_t>(t0 + kLocalTile, n);
@@ -1308,9 +1313,25 @@ __global__ __launch_bounds__(kSignThreads) void sign_local_kernel(const float* _
       while (sgi + 1 < nseg && seg_off[sgi + 1] <= e) ++sgi;
     const int64_t numel = nseg > 1 ? seg_off[sgi + 1] - seg_off[sgi] : n;
     const float v = x[e];
-    const float sg = v > 0.f ? 1.0f : (v < 0.f ? -1.0f : 0.0f);  // torch.sign: +-0 and NaN -> +0
-    out[e] = (norms[sgi] * sg) / (float)numel;
+    const float u = sign_local_u(norms[sgi], v, numel);
+    if (out) out[e] = u;
+    if (resid) resid[e] = __fsub_rn(v, u);
   }
+}
+__global__ __launch_bounds__(kSignThreads) void sign_local_kernel(const float* __restrict__ x, int64_t n,
+                                                                  const int64_t* __restrict__ seg_off, int nseg,
+                                                                  const float* __restrict__ norms,
+                                                                  float* __restrict__ out) {
+  sign_local_tile(x, n, seg_off, nseg, norms, out, nullptr);
+}
+// The local copy with the error feedback that subtracts it in the same pass
+// (deep_squeeze.py:416-422 with :115; ef_sign_sgd.py:153 with :104-106):
+// resid[e] = rn(x[e] - u), local[e] = u where local is not NULL.  resid may be x.
+__global__ __launch_bounds__(kSignThreads) void sign_local_residual_kernel(const float* x, int64_t n,
+                                                                           const int64_t* __restrict__ seg_off,
+                                                                           int nseg, const float* __restrict__ norms,
+                                                                           float* __restrict__ local, float* resid) {
+  sign_local_tile(x, n, seg_off, nseg, norms, local, resid);
 }
 
 }  // namespace choco
@@ -1573,6 +1594,25 @@ CHOCO_API int choco_sign_local_decode(const float* x, int64_t n, const int64_t* 
   const unsigned grid = (unsigned)((n + kLocalTile - 1) / kLocalTile);
   return CHOCO_LAUNCH(nullptr, "sign_local_kernel", sign_local_kernel, dim3(grid), dim3(kSignThreads), st, x, n,
                       seg_off, nseg, norms, out);
+}
+
+CHOCO_API int choco_sign_local_residual(const float* x, int64_t n, const int64_t* seg_off, int32_t nseg,
+                                        const float* norms, float* local_out, float* resid_out, void* stream) {
+  hipStream_t st = as_stream(stream);
+  CHOCO_REQUIRE(x && norms && resid_out, "null pointer argument");
+  CHOCO_TRY(check_flat(n, seg_off, nseg));
+  CHOCO_REQUIRE(aligned4(x) && aligned4(norms) && aligned4(local_out) && aligned4(resid_out),
+                "x, norms, local_out and resid_out must be 4-byte aligned");
+  // local_out is written while x is still being read by other threads, and it holds another
+  // value than resid_out: a range test against both
+  CHOCO_REQUIRE(!local_out || ((local_out + n <= x || x + n <= local_out) &&
+                               (local_out + n <= resid_out || resid_out + n <= local_out)),
+                "local_out aliases (overlaps) x or resid_out");
+  CHOCO_REQUIRE(resid_out == x || resid_out + n <= x || x + n <= resid_out,
+                "resid_out overlaps x without being x itself");
+  const unsigned grid = (unsigned)((n + kLocalTile - 1) / kLocalTile);
+  return CHOCO_LAUNCH("sign_local_residual", "sign_local_residual_kernel", sign_local_residual_kernel, dim3(grid),
+                      dim3(kSignThreads), st, x, n, seg_off, nseg, norms, local_out, resid_out);
 }
 
 CHOCO_API int choco_sign_decompress_extrapolate(const int32_t* packed, const float* norms, int64_t n,

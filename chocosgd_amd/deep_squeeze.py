@@ -15,10 +15,17 @@ kernels (top-k: a scatter of the message into zeros with the accumulate kernel,
 QSGD: the quantize pass's dense decode, sign: choco_sign_local_decode with
 torch.sign's sign(0) = 0); the aggregate uses the receivers with the
 reference's two-rounding add_(c * u) (include/choco_codec.h).
+
+`fused_step(...)` is `DeepSqueeze.step` end to end (deep_squeeze.py:94-127): the batched
+apply_gradient, `memory += params` straight from the parameter tensors
+(codec.params_ef), `compress(sync_buffer, residual=True)` -- the message, then
+`memory -= local copy` in place with no local copy built --, sync / uncompress, and
+`params += aggregate` straight into the parameter tensors.  `step_loop(...)` is the same
+step as one torch op per line (CPU tensors).
 """
 import torch
 
-from . import codec
+from . import codec, utils
 from .communication import recover_device
 from .dcd import _ConsumerBase
 from .tensor_buffer import TensorBuffer
@@ -43,6 +50,48 @@ class DeepSqueezeCompressor(object):
 
     def uncompress(self, *args, **kargs):
         return self.compressor_fn.uncompress(*args, **kargs)
+
+
+def step_loop(compressor, param_groups, param_names, state, shapes, memory, neighbors_info):
+    """DeepSqueeze.step (deep_squeeze.py:94-127) as the reference's op sequence, one torch op per
+    line: the path CPU tensors, and anything the batched kernels do not take, keep."""
+    entries = utils.step_entries(param_groups, param_names, "deep_squeeze.step_loop")
+    utils.apply_gradient(param_groups, state, apply_grad_to_model=True)
+    params = [p for _, p in entries]
+    params_tb = TensorBuffer([p.data for p in params], dtype=torch.float32)
+    memory.buffer += params_tb.buffer
+    sync_buffer = {"original_shapes": shapes, "params_tb": memory}
+    local_compressed_params_tb = compressor.compress(sync_buffer)
+    memory.buffer = memory.buffer - local_compressed_params_tb.buffer
+    compressor.sync(sync_buffer)
+    aggregated_info_tb = compressor.uncompress(sync_buffer, neighbors_info)
+    params_tb.buffer += aggregated_info_tb.buffer
+    params_tb.unpack(params)
+    return sync_buffer["n_bits"]
+
+
+def fused_step(compressor, param_groups, param_names, state, shapes, memory, neighbors_info):
+    """DeepSqueeze.step end to end (deep_squeeze.py:94-127): the batched
+    apply_gradient(apply_grad_to_model=True) writes the params; ONE params_ef launch (per chunk)
+    adds them onto memory.buffer (:101-108, no flat copy of the params); the compressor builds
+    its message and subtracts its local copy from memory.buffer in place
+    (compress(residual=True), :110-115); sync and uncompress as they are; ONE params_ef launch
+    adds the aggregate onto the params (:125-126).  No pack, no unpack.  memory.buffer is
+    updated in place, where the reference rebinds it.  Returns n_bits.  Tensors the kernels do
+    not take run step_loop."""
+    entries = utils.step_entries(param_groups, param_names, "deep_squeeze.fused_step")
+    mem = memory.buffer
+    plan = utils._sgd_fill(entries, state, True, mem) if mem.is_cuda else None
+    if plan is None:
+        return step_loop(compressor, param_groups, param_names, state, shapes, memory, neighbors_info)
+    plan.run(None, grad_mode=False, write=True)
+    plan.ef(mem, codec.EF_ACCUM)
+    sync_buffer = {"original_shapes": shapes, "params_tb": memory}
+    compressor.compress(sync_buffer, residual=True)
+    compressor.sync(sync_buffer)
+    agg = compressor.uncompress(sync_buffer, neighbors_info)
+    plan.ef(agg.buffer, codec.EF_APPLY)
+    return sync_buffer["n_bits"]
 
 
 class _DeepSqueezeBase(_ConsumerBase):
@@ -83,9 +132,14 @@ class DeepSqueezeSparsificationCompressor(_DeepSqueezeBase):
             g = self._guards[dev] = codec.IndexGuard(dev)
         return g
 
-    def compress(self, sync_buffer):
+    def compress(self, sync_buffer, residual=False):
+        """residual: params_tb.buffer -= local copy in place, at the selected positions only
+        (m + (-v) is m - v bit for bit, m - 0 = m everywhere else); returns None."""
         tb, x, lay = self._inputs(sync_buffer)
         values, indices = self._sparse_message(sync_buffer, x, None, lay)
+        if residual:
+            codec.sparse_accumulate(values, indices, x, -1.0)
+            return None
         local = torch.zeros_like(x)
         codec.sparse_accumulate(values, indices, local, 1.0)  # local[idx] = v  (deep_squeeze.py:206-208)
         return self._like(tb, local)
@@ -113,9 +167,16 @@ class DeepSqueezeSparsificationCompressor(_DeepSqueezeBase):
 class DeepSqueezeQuantizationCompressor(_DeepSqueezeBase):
     """QSGD  (deep_squeeze.py:282-376)."""
 
-    def compress(self, sync_buffer):
+    def compress(self, sync_buffer, residual=False):
+        """residual: params_tb.buffer -= the dense decode in place; returns None."""
         tb, x, lay = self._inputs(sync_buffer)
         dense = self._qsgd_message(sync_buffer, x, None, lay, want_dense=True)
+        if residual:
+            if int(self.quantize_level) == 32:  # the message is a view of x: it keeps its own bytes
+                wire = sync_buffer["flatten_updates"]
+                wire.buffer = wire.buffer.clone()
+            x.sub_(dense)
+            return None
         return self._like(tb, dense.clone() if int(self.quantize_level) == 32 else dense)
 
     def sync(self, sync_buffer):
@@ -143,10 +204,15 @@ class DeepSqueezeSignCompressor(_DeepSqueezeBase):
     """sign + per-tensor L1 norm  (deep_squeeze.py:379-489); norms and signs travel in ONE
     message, `synced_param_norms` / `synced_signs` are views of it."""
 
-    def compress(self, sync_buffer):
+    def compress(self, sync_buffer, residual=False):
+        """residual: params_tb.buffer -= local copy in place, in the pass that decodes it
+        (codec.sign_local_residual); returns None."""
         tb, x, lay = self._inputs(sync_buffer)
         signs, norms = self._sign_message(sync_buffer, x, None, lay)
         sync_buffer["param_norms_tb"] = TensorBuffer.from_flat(norms, [() for _ in range(lay.nseg)])
+        if residual:
+            codec.sign_local_residual(x, norms, seg_off=lay.seg_off, nseg=lay.nseg, resid_out=x)
+            return None
         # (norm_s * torch.sign(x)) / numel_s  (deep_squeeze.py:416-422)
         local = codec.sign_local_decode(x, norms, seg_off=lay.seg_off, nseg=lay.nseg)
         return self._like(tb, local)

@@ -318,6 +318,19 @@ int choco_sign_decompress_extrapolate(const int32_t* packed, const float* norms,
 int choco_sign_local_decode(const float* x, int64_t n, const int64_t* seg_off, int32_t nseg,
                             const float* norms, float* out, void* stream);
 
+/* The local copy with the error feedback that subtracts it, in one pass
+ * (deep_squeeze.py:416-422 with :115; ef_sign_sgd.py:153 with :104-106): u is exactly
+ * choco_sign_local_decode's value (the same device function), then
+ *     resid_out[i] = rn(x[i] - u),   local_out[i] = u   (when local_out != NULL).
+ * resid_out may be x itself (each thread reads an element before it writes it); it must
+ * not overlap x otherwise, and local_out may overlap neither x nor resid_out: both are
+ * checked, with null x / norms / resid_out, n outside [1, 2^31 - 1), nseg < 1, nseg > 1
+ * without seg_off and pointers off 4-byte alignment, before the launch and without a
+ * HIP call. */
+int choco_sign_local_residual(const float* x, int64_t n, const int64_t* seg_off, int32_t nseg,
+                              const float* norms, float* local_out, float* resid_out,
+                              void* stream);
+
 /* --------------------------------------------------------------- QSGD
  * Replaces QuantizationCompressor.get_qsgd/compress (sparsification.py:87-98,114-120)
  * applied per segment (parallel_choco_v.py:375-397).  s = 2^q - 1 levels.
@@ -641,6 +654,48 @@ int choco_params_mix(const float* const* srcs, const double* weights, int32_t ns
                      const int64_t* lens, const int32_t* dtypes, int32_t nseg,
                      double lr, double ext_a, double ext_b, int32_t mode,
                      float* flat_out, float* x_out, int64_t n, void* stream);
+
+/* ------------------------------------------- error-feedback lines
+ * The dense lines around the compressors of the reference's two error-feedback
+ * optimizers, as ONE launch per chunk of tensors straight between the parameter tensors
+ * and a flat fp32 buffer (no pack, no unpack, no temporary):
+ *   DeepSqueeze (pcode/optim/deep_squeeze.py:101-108): the pack of the params and
+ *     `self.memory.buffer += params_tb.buffer`.
+ *       mode ACCUM, flat = memory.buffer
+ *   DeepSqueeze (pcode/optim/deep_squeeze.py:125-126): `params_tb.buffer += agg`, unpack.
+ *       mode APPLY, flat = the aggregate
+ *   EF-signSGD (pcode/optim/ef_sign_sgd.py:218, :113-122): `/= world_size * 1.0`, the pack
+ *     of the params, `.add_(-lr * sync_grads_tb.buffer)`, unpack.
+ *       mode APPLY | DIV | SCALE, flat = synced_grads
+ * The tensor tables are those of choco_params_sgd: tensor s holds lens[s] elements of
+ * dtype dtypes[s] in params[s] and owns flat elements [sum(lens[0..s)), + lens[s]).  Per
+ * element (flat index i, element j of tensor s, x = params[s][j] widened), every line one
+ * reference op with one rounding:
+ *     ACCUM:  flat[i] = rn(flat[i] + x)                    the params are read only
+ *     APPLY:  a = flat[i]
+ *       DIV:    a = rn(a / (float)divisor), flat[i] = a    a correctly rounded IEEE division,
+ *                                                          never a reciprocal multiply
+ *       SCALE:  a = rn((float)(-lr) * a)                   not written back
+ *             params[s][j] = rn(x + a) narrowed round-to-nearest-even: the add is an fp32
+ *             add on the widened param, the store narrows once
+ * NaN and inf propagate; (-0) + (+0) = +0.  Each thread reads before it writes.  Only the
+ * bytes of the layout's own elements are written; pointers need their element's alignment
+ * only (16-byte vectors are used where flat and a tensor's side allow them).  Every
+ * argument is checked before the first launch without a HIP call -- null params / lens /
+ * dtypes tables, nseg <= 0, negative lengths or lengths that do not sum to n, unknown
+ * dtype or mode bits, neither or both of ACCUM and APPLY, DIV or SCALE without APPLY,
+ * flat == NULL, a NULL param of a non-empty tensor, misaligned pointers, a divisor that is
+ * not finite or is zero (as a float) under DIV, a non-finite lr under SCALE -- and a bad
+ * one returns CHOCO_ERR_INVALID and launches nothing.  A call takes
+ * choco_params_ef_launches(nseg) launches of "param_ef_kernel" (0 for nseg <= 0). */
+#define CHOCO_EF_ACCUM 1
+#define CHOCO_EF_APPLY 2
+#define CHOCO_EF_DIV 4
+#define CHOCO_EF_SCALE 8
+int choco_params_ef_launches(int32_t nseg);
+/* pcode/optim/deep_squeeze.py:101-108, :125-126, ef_sign_sgd.py:113-122, :218 */
+int choco_params_ef(void* const* params, const int64_t* lens, const int32_t* dtypes, int32_t nseg,
+                    float* flat, int64_t n, int32_t mode, double lr, double divisor, void* stream);
 
 /* ------------------------------------------- fused gossip step + compress
  * ParallelCHOCO_V.step's update_params_from_neighbor -> compress sequence
