@@ -17,6 +17,26 @@ TOPK_STATUS_OFFSET = 0        # CHOCO_TOPK_STATUS_OFFSET
 TOPK_FALLBACKS_OFFSET = 4     # CHOCO_TOPK_FALLBACKS_OFFSET
 TOPK_COLD_LEFT_OFFSET = 8     # CHOCO_TOPK_COLD_LEFT_OFFSET
 TOPK_K2_SAMPLES_OFFSET = 16   # CHOCO_TOPK_K2_SAMPLES_OFFSET
+# the rest of the flat top-k control block (diagnostics): CHOCO_TOPK_DIAG_*
+TOPK_DIAG_BACKOFF_OFFSET = 12
+TOPK_DIAG_T_PREV_OFFSET = 20
+TOPK_DIAG_D_PREV_OFFSET = 24
+TOPK_DIAG_SH_LO_OFFSET = 28
+TOPK_DIAG_SH_HI_OFFSET = 32
+TOPK_DIAG_SH_NK_OFFSET = 36
+TOPK_DIAG_SH_HITS_OFFSET = 40
+TOPK_DIAG_D_CAND_OFFSET = 44
+TOPK_DIAG_D_TRUST_OFFSET = 48
+TOPK_DIAG_OVERFLOW_OFFSET = 64   # + 4 * parity
+TOPK_DIAG_BOUNDS_OFFSET = 128    # + TOPK_DIAG_BOUNDS_STRIDE * parity
+TOPK_DIAG_BOUNDS_STRIDE = 40
+TOPK_DIAG_BOUNDS_S_LO = 0
+TOPK_DIAG_BOUNDS_S_HI = 4
+TOPK_DIAG_BOUNDS_SHIFT = 8
+TOPK_DIAG_BOUNDS_M1024 = 12
+TOPK_DIAG_BOUNDS_N = 16          # int64
+TOPK_DIAG_BOUNDS_K = 24          # int64
+TOPK_DIAG_BOUNDS_VALID = 32
 TOPK_STATUS_POLL_TIMEOUT = 1  # CHOCO_TOPK_STATUS_POLL_TIMEOUT
 
 _c_i32, _c_i64, _c_u64, _c_f32, _c_f64 = (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,

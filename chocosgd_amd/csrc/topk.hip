@@ -117,7 +117,7 @@ struct TopkCtrl {
   uint32_t status;                               // sticky error bits (kStatus*), read by the host lazily
   uint32_t fallbacks;                            // calls that took the exact fallback (diagnostic counter)
   uint32_t cold_left;                            // warm-host calls still to sample their window in K2 (backoff)
-  uint32_t backoff;                              // cold run length after the next warm miss
+  uint32_t backoff;                              // the next warm miss doubles it and starts a cold run that long
   uint32_t k2_samples;                           // calls whose K2 took its window from its own sample (diagnostic)
   // drift tracking (K34, workgroup 0): the previous call's exact k-th key, the key drift
   // between the two calls before it, the window the previous call prepared for this one
@@ -139,6 +139,23 @@ static_assert(offsetof(TopkCtrl, status) == CHOCO_TOPK_STATUS_OFFSET, "status wo
 static_assert(offsetof(TopkCtrl, fallbacks) == CHOCO_TOPK_FALLBACKS_OFFSET, "fallback counter at the documented offset");
 static_assert(offsetof(TopkCtrl, cold_left) == CHOCO_TOPK_COLD_LEFT_OFFSET, "cold-run word at the documented offset");
 static_assert(offsetof(TopkCtrl, k2_samples) == CHOCO_TOPK_K2_SAMPLES_OFFSET, "K2 sample counter at the documented offset");
+static_assert(offsetof(TopkCtrl, backoff) == CHOCO_TOPK_DIAG_BACKOFF_OFFSET, "backoff at the documented offset");
+static_assert(offsetof(TopkCtrl, t_prev) == CHOCO_TOPK_DIAG_T_PREV_OFFSET, "t_prev at the documented offset");
+static_assert(offsetof(TopkCtrl, d_prev) == CHOCO_TOPK_DIAG_D_PREV_OFFSET, "d_prev at the documented offset");
+static_assert(offsetof(TopkCtrl, sh_lo) == CHOCO_TOPK_DIAG_SH_LO_OFFSET, "sh_lo at the documented offset");
+static_assert(offsetof(TopkCtrl, sh_hi) == CHOCO_TOPK_DIAG_SH_HI_OFFSET, "sh_hi at the documented offset");
+static_assert(offsetof(TopkCtrl, sh_nk) == CHOCO_TOPK_DIAG_SH_NK_OFFSET, "sh_nk at the documented offset");
+static_assert(offsetof(TopkCtrl, sh_hits) == CHOCO_TOPK_DIAG_SH_HITS_OFFSET, "sh_hits at the documented offset");
+static_assert(offsetof(TopkCtrl, d_cand) == CHOCO_TOPK_DIAG_D_CAND_OFFSET, "d_cand at the documented offset");
+static_assert(offsetof(TopkCtrl, d_trust) == CHOCO_TOPK_DIAG_D_TRUST_OFFSET, "d_trust at the documented offset");
+static_assert(offsetof(TopkCtrl, overflow) == CHOCO_TOPK_DIAG_OVERFLOW_OFFSET, "overflow words at the documented offset");
+static_assert(offsetof(TopkCtrl, bounds) == CHOCO_TOPK_DIAG_BOUNDS_OFFSET, "windows at the documented offset");
+static_assert(sizeof(TopkBounds) == CHOCO_TOPK_DIAG_BOUNDS_STRIDE, "one window per documented stride");
+static_assert(offsetof(TopkBounds, s_lo) == CHOCO_TOPK_DIAG_BOUNDS_S_LO && offsetof(TopkBounds, s_hi) == CHOCO_TOPK_DIAG_BOUNDS_S_HI &&
+                  offsetof(TopkBounds, shift) == CHOCO_TOPK_DIAG_BOUNDS_SHIFT &&
+                  offsetof(TopkBounds, m1024) == CHOCO_TOPK_DIAG_BOUNDS_M1024 && offsetof(TopkBounds, n) == CHOCO_TOPK_DIAG_BOUNDS_N &&
+                  offsetof(TopkBounds, k) == CHOCO_TOPK_DIAG_BOUNDS_K && offsetof(TopkBounds, valid) == CHOCO_TOPK_DIAG_BOUNDS_VALID,
+              "window fields at the documented offsets");
 constexpr uint32_t kNoCandKey = 0x7F800000u;   // window that admits only inf / NaN keys (invalid bounds)
 
 // The self-message part of CHOCOSparsificationCompressor.uncompress (parallel_choco_v.py:
@@ -1279,7 +1296,7 @@ CHOCO_DEV void wide_fallback(const Src<MODE, XH>& src, int64_t n, int64_t k, uin
 // floor where this call had k (1 + m) keys above, and its sure ceiling where it
 // had k (1 - m): if the next delta's distribution moved by less than m the next
 // call selects inside it.  m (in 1/1024 of k) is twice the miss of the edges
-// this call aimed at, decaying by half per call to kWarmM0.  Edges outside the
+// this call aimed at, decaying by half per call to the floor m0 (warm_m0).  Edges outside the
 // window are extrapolated from its density (G[0] - k keys over [s_lo, T]).
 // Wave 0 of one workgroup; ~0.3 us, after that workgroup's emission.
 // ----------------------------------------------------------------------------
@@ -1294,12 +1311,23 @@ CHOCO_DEV uint32_t nk_tag(int64_t n, int64_t k) {
 // (window_drift: choco_common.h)
 constexpr uint32_t kWarmM0 = 20;     // ~2 % of k (the bench's randn deltas drift ~0.1 %)
 constexpr uint32_t kWarmMMax = 512;  // 50 %
+// The margin's floor m0 for a given k (host; a kernel argument of K34).  Between two independent
+// draws of the same distribution the number of keys above a fixed key moves by ~sqrt(2 k)
+// (one binomial error in the draw that placed the edge, one in the draw that meets it), i.e.
+// by sqrt(2 / k) of k: 0.14 % at k = 1M, but 2.8 % at k = 2,621 (n = 262,147 at 1 %), more
+// than kWarmM0 -- there a stationary delta missed its carried window every few calls, and the
+// rule below, which raises m once an edge comes closer than m / 2, kept moving m.  The floor
+// is 8 sigma of that noise (4 sigma for the rule) where this exceeds kWarmM0: k < 335,545.
+static uint32_t warm_m0(int64_t k) {
+  const double m = ceil(1024.0 * 8.0 * sqrt(2.0 / (double)k));
+  return (uint32_t)std::min<double>((double)kWarmMMax, std::max<double>((double)kWarmM0, m));
+}
 CHOCO_DEV void next_window(const uint32_t* G, uint32_t s_lo, uint32_t s_hi, uint32_t shift, uint32_t m_prev,
-                           uint32_t T, int64_t n, int64_t k, int32_t drift, TopkBounds* __restrict__ out,
-                           uint32_t& w_lo, uint32_t& w_hi) {
+                           uint32_t T, int64_t n, int64_t k, int32_t drift, uint32_t m0,
+                           TopkBounds* __restrict__ out, uint32_t& w_lo, uint32_t& w_hi) {
   const int lane = lane_id();
   const double kd = (double)k;
-  uint32_t m = kWarmM0;
+  uint32_t m = m0;
   if (m_prev != 0u) {  // this call's window aimed at k (1 + m_prev) / k (1 - m_prev)
     // One-sided: only an edge that moved TOWARD the k-th key is a miss of the aim (fewer
     // candidates above the floor, more keys above the ceiling).  A window wider than
@@ -1310,7 +1338,7 @@ CHOCO_DEV void next_window(const uint32_t* G, uint32_t s_lo, uint32_t s_hi, uint
     const double e = fmax(fmax(kd * (1.0 + m_prev / 1024.0) - (double)G[0], 0.0),
                           fmax((double)G[kNMaybe] - kd * (1.0 - m_prev / 1024.0), 0.0));
     const double me = ceil(2.0 * e / kd * 1024.0);
-    m = (uint32_t)fmin((double)kWarmMMax, fmax(fmax((double)kWarmM0, me), (double)(m_prev / 2)));
+    m = (uint32_t)fmin((double)kWarmMMax, fmax(fmax((double)m0, me), (double)(m_prev / 2)));
   }
   const uint64_t lo_t = (uint64_t)k + (uint64_t)k * m / 1024u;
   const uint64_t hi_t = (uint64_t)k - std::min<uint64_t>((uint64_t)k, (uint64_t)k * m / 1024u);
@@ -1370,7 +1398,7 @@ __global__ __launch_bounds__(kK4Threads) void topk_finish_kernel(
     const uint32_t* __restrict__ cidx, float* __restrict__ out_val, int32_t* __restrict__ out_idx,
     int64_t idx_base, WideCtrl* __restrict__ wide, uint32_t* __restrict__ gcnt, uint32_t* __restrict__ thist,
     uint32_t par, uint32_t* __restrict__ status, uint32_t* __restrict__ host_status, const uint32_t* __restrict__ tinfo,
-    Fold fold, uint32_t* __restrict__ cold_host) {
+    Fold fold, uint32_t* __restrict__ cold_host, uint32_t m0) {
   __shared__ FinSmem fs;
   __shared__ ExactSmem es;
   __shared__ uint32_t s_tk;
@@ -1631,7 +1659,7 @@ __global__ __launch_bounds__(kK4Threads) void topk_finish_kernel(
       next_window(fs.G, s_lo, fs.ctl[1], shift, fs.ctl[4], T, n, k,
                   (trust = drift_trusted(T, fs.ctl[5], fs.ctl[13], fs.ctl[9] == nk) ? min(fs.ctl[14] + 1u, 15u) : 0u)
                           >= kDriftTrust ? window_drift(T, fs.ctl[5], fs.ctl[6], fs.ctl[9] == nk) : 0,
-                  &ctrl->bounds[par ^ 1u], nw_lo, nw_hi);
+                  m0, &ctrl->bounds[par ^ 1u], nw_lo, nw_hi);
   }
   // random-k windows come from the host each call: nothing for the next call to reuse
   if (MODE == kHash && b == 0 && tid == 0) ctrl->bounds[par ^ 1u].valid = 0u;
@@ -1817,7 +1845,7 @@ static int launch_topk(const float* x, const float* xh, int64_t n, int64_t k, ui
                       cval, cidx, out_val, out_idx, idx_base, reinterpret_cast<WideCtrl*>(base + L.off_wide),
                       reinterpret_cast<uint32_t*>(base + L.off_gcnt), reinterpret_cast<uint32_t*>(base + L.off_thist),
                       par, status.dev, status.host, reinterpret_cast<const uint32_t*>(base + L.off_tinfo), fold,
-                      cold_host);
+                      cold_host, warm_m0(k));
 }
 
 template <int MODE>

@@ -97,6 +97,46 @@ int choco_topk_host_status(const void* ws, int32_t clear, void* stream);
  * under the stream: the host then runs the separate sample kernel first). */
 #define CHOCO_TOPK_COLD_LEFT_OFFSET 8
 #define CHOCO_TOPK_K2_SAMPLES_OFFSET 16
+/* Flat workspaces only, diagnostics (byte offsets of uint32 words unless noted; read them
+ * after the call has completed, never written by the host): the rest of the warm-start
+ * controller's state, as the finish kernel of the last call left it.
+ *   BACKOFF   the length of the last cold run, as warm hits have halved it since (not below
+ *             64): the next warm miss doubles it (64 on a fresh workspace, at most 4096) and
+ *             starts a cold run of that many calls;
+ *   T_PREV    the last call's exact k-th key (|v| bits; 0 after a fallback), D_PREV its move
+ *             against the call before (int32 bits; 0 when there is none for this (n, k));
+ *   SH_LO / SH_HI / SH_NK  the window the last call prepared for the next one and a tag of
+ *             the (n, k) it was made for; SH_HITS the cold-run calls in a row whose k-th key
+ *             that carried window would have held (2 end the cold run early);
+ *   D_CAND    the drift the last call proposed (int32 bits), D_TRUST the calls in a row whose
+ *             proposed drift predicted the k-th key better than the previous key did (from 2
+ *             on the prepared window is moved by the drift);
+ *   OVERFLOW + 4 par  per call parity (call count on the workspace & 1): bit 0 a side list
+ *             overflowed, bit 1 the sample was degenerate; either means the exact fallback.
+ *             Call c's word stays as it was until call c + 1's stream kernel clears it;
+ *   BOUNDS + CHOCO_TOPK_DIAG_BOUNDS_STRIDE par  the window call c used (par = c & 1) and, at
+ *             the other parity, the one it prepared: uint32 S_LO, S_HI, SHIFT, M1024 (the
+ *             margin in 1/1024 of k; 0: a sampled or fallback window), int64 N, K and uint32
+ *             VALID at the CHOCO_TOPK_DIAG_BOUNDS_* offsets inside the entry. */
+#define CHOCO_TOPK_DIAG_BACKOFF_OFFSET 12
+#define CHOCO_TOPK_DIAG_T_PREV_OFFSET 20
+#define CHOCO_TOPK_DIAG_D_PREV_OFFSET 24
+#define CHOCO_TOPK_DIAG_SH_LO_OFFSET 28
+#define CHOCO_TOPK_DIAG_SH_HI_OFFSET 32
+#define CHOCO_TOPK_DIAG_SH_NK_OFFSET 36
+#define CHOCO_TOPK_DIAG_SH_HITS_OFFSET 40
+#define CHOCO_TOPK_DIAG_D_CAND_OFFSET 44
+#define CHOCO_TOPK_DIAG_D_TRUST_OFFSET 48
+#define CHOCO_TOPK_DIAG_OVERFLOW_OFFSET 64
+#define CHOCO_TOPK_DIAG_BOUNDS_OFFSET 128
+#define CHOCO_TOPK_DIAG_BOUNDS_STRIDE 40
+#define CHOCO_TOPK_DIAG_BOUNDS_S_LO 0
+#define CHOCO_TOPK_DIAG_BOUNDS_S_HI 4
+#define CHOCO_TOPK_DIAG_BOUNDS_SHIFT 8
+#define CHOCO_TOPK_DIAG_BOUNDS_M1024 12
+#define CHOCO_TOPK_DIAG_BOUNDS_N 16
+#define CHOCO_TOPK_DIAG_BOUNDS_K 24
+#define CHOCO_TOPK_DIAG_BOUNDS_VALID 32
 #define CHOCO_TOPK_STATUS_POLL_TIMEOUT 1
 int choco_topk_compress(const float* x, const float* xhat, int64_t n, int64_t k,
                         float* out_val, int32_t* out_idx,

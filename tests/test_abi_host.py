@@ -42,6 +42,18 @@ def test_exported_symbols_are_exactly_the_abi():
     assert exported == _header_symbols()
 
 
+def test_topk_workspace_offsets_mirror_the_header():
+    """Every CHOCO_TOPK_* word of the header (the control block's documented offsets, the
+    diagnostics included) has the same value in chocosgd_amd/_lib.py, and nothing else there
+    claims to be one.  (csrc/topk.hip static_asserts the header against the structs.)"""
+    from chocosgd_amd import _lib
+    defs = dict(re.findall(r"^#define CHOCO_(TOPK_[A-Z0-9_]+) (\d+)\s*$", open(HEADER).read(), re.M))
+    assert len(defs) == 24 and "TOPK_DIAG_BOUNDS_VALID" in defs and "TOPK_STATUS_OFFSET" in defs
+    for name, value in defs.items():
+        assert getattr(_lib, name) == int(value), name
+    assert {n for n in dir(_lib) if n.startswith("TOPK_")} == set(defs)
+
+
 def test_topk_k_rule_matches_reference_table(lib):
     for n, ratio, k in golden_json("k_table.json"):
         assert lib.choco_topk_k(n, ratio) == k, (n, ratio)
