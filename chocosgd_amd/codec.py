@@ -1149,6 +1149,25 @@ class ParamSgdPlan:
                                           self.weight_decay, self.momentum, self.dampening, self.flags, self.nseg,
                                           _ptr(flat), self.n, mode, _stream(self.device)), "choco_params_sgd")
 
+    def fits_master_buf(self, i, t):
+        """Whether tensor t can stand as the fp32 momentum buffer of parameter i in a master
+        update (the buffers are fp32 whatever the parameter's dtype)."""
+        return (t.dtype == torch.float32 and t.device == self.device and t.numel() == self.numels[i]
+                and t.is_contiguous())
+
+    def run_master(self, master, write=True):
+        """One choco_params_sgd_master over the tables as they stand: the update runs on
+        `master` (the persistent flat fp32 copy of the parameters, n elements) in place, with
+        fp32 momentum buffers behind `buf_ptrs` and the gradients in their parameters' dtype;
+        write -> the parameters receive the new master values narrowed to their dtype."""
+        _require(master, torch.float32, "master")
+        if master.device != self.device or master.numel() != self.n:
+            raise RuntimeError(f"master must hold {self.n} elements on {self.device}")
+        _lib.check(lib().choco_params_sgd_master(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts,
+                                                 self.lr, self.weight_decay, self.momentum, self.dampening,
+                                                 self.flags, self.nseg, _ptr(master), self.n,
+                                                 SGD_MODE_WRITE_PARAMS if write else 0, _stream(self.device)),
+                   "choco_params_sgd_master")
 
     def mix(self, srcs, weights, lr=0.0, mode=0, ext_a=0.0, ext_b=0.0, flat_out=None, x_out=None):
         """One choco_params_mix over the plan's parameter and gradient pointers as they stand
@@ -1283,6 +1302,33 @@ def params_sgd(params, grads, bufs, lr, weight_decay=0.0, momentum=0.0, dampenin
     the tensor is only packed into `flat`).  bufs[s]: the momentum buffer, written when
     momentum != 0 and read unless first[s].  The hyperparameters, `nesterov` and `first` are
     scalars or per-tensor lists.  Returns the plan (pass it back in to reuse its tables)."""
+    plan = _sgd_tables(params, grads, bufs, lr, weight_decay, momentum, dampening, nesterov, first, plan, False)
+    plan.run(flat, grad_mode, write)
+    return plan
+
+
+def params_sgd_master_launches(nseg):
+    """Launches one params_sgd_master of `nseg` tensors takes."""
+    return int(lib().choco_params_sgd_master_launches(int(nseg)))
+
+
+def params_sgd_master(params, grads, bufs, lr, weight_decay=0.0, momentum=0.0, dampening=0.0, nesterov=False,
+                      first=False, master=None, write=True, plan=None):
+    """apply_gradient on fp32 master weights (include/choco_codec.h, choco_params_sgd_master):
+    params_sgd's arguments, except that the update runs in place on `master` -- the persistent
+    flat fp32 copy of `params`, laid out back to back -- and bufs[s] is an fp32 tensor whatever
+    its parameter's dtype.  grads[s] has its parameter's dtype; None: the tensor is passed over.
+    write: the parameters receive the new master values narrowed to their dtype.  Returns the
+    plan (pass it back in to reuse its tables)."""
+    if master is None:
+        raise RuntimeError("params_sgd_master needs the master buffer")
+    plan = _sgd_tables(params, grads, bufs, lr, weight_decay, momentum, dampening, nesterov, first, plan, True)
+    plan.run_master(master, write)
+    return plan
+
+
+def _sgd_tables(params, grads, bufs, lr, weight_decay, momentum, dampening, nesterov, first, plan, master):
+    """The plan of `params` with one call's pointers, flags and hyperparameters written."""
     params = list(params)
     nseg = len(params)
     if plan is None:
@@ -1293,9 +1339,11 @@ def params_sgd(params, grads, bufs, lr, weight_decay=0.0, momentum=0.0, dampenin
                                                    (weight_decay, "weight_decay"), (momentum, "momentum"),
                                                    (dampening, "dampening"), (nesterov, "nesterov"), (first, "first"))]
     for i, (p, g, b, a, wd, mom, damp, nest, fst) in enumerate(zip(params, *cols)):
-        for t, nm in ((g, "grad"), (b, "buf")):
-            if t is not None and not plan.fits(i, t):
-                raise RuntimeError(f"{nm} {i} must match its parameter's dtype, device and size, and be contiguous")
+        if g is not None and not plan.fits(i, g):
+            raise RuntimeError(f"grad {i} must match its parameter's dtype, device and size, and be contiguous")
+        if b is not None and not (plan.fits_master_buf(i, b) if master else plan.fits(i, b)):
+            what = "be float32 and match its parameter's" if master else "match its parameter's dtype,"
+            raise RuntimeError(f"buf {i} must {what} device and size, and be contiguous")
         plan.param_ptrs[i] = p.data_ptr()
         plan.grad_ptrs[i] = g.data_ptr() if g is not None else None
         plan.buf_ptrs[i] = b.data_ptr() if b is not None else None
@@ -1303,7 +1351,6 @@ def params_sgd(params, grads, bufs, lr, weight_decay=0.0, momentum=0.0, dampenin
                          | (SGD_F_NOGRAD if g is None else 0))
         plan.lr[i], plan.weight_decay[i], plan.momentum[i], plan.dampening[i] = a, wd, mom, damp
         plan.seen[i] = None
-    plan.run(flat, grad_mode, write)
     return plan
 
 

@@ -230,6 +230,112 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
   }
 }
 
+// ------------------------------------------------------------------ fp32 master weights
+// The same update on a persistent flat fp32 copy of a bf16 / fp16 model (choco_params_sgd_master):
+// p is master[i], the momentum buffer is fp32 whatever the tensor's dtype, g is the tensor's own
+// gradient widened (exact), the arithmetic is sgd_math<CHOCO_DT_F32> -- nothing is narrowed
+// between the lines -- and the 16-bit parameter, where the mode writes it, is the new master value
+// narrowed once, as param_unpack_kernel would narrow it.  A NOGRAD tensor is passed over: neither
+// its master slice nor its parameter is read or written.  The launch has param_sgd_kernel's shape
+// (same table, tiles and search).  The sides of one tensor have different element sizes here: a
+// tensor takes the 16-byte path when master is 16-byte aligned and each side it touches is
+// congruent with the group grid at that side's own element size -- g and p at the tensor's, buf
+// at 4 bytes.
+
+// flat index i, element j of the tensor
+template <int DT>
+CHOCO_DEV void master_elem(const SgdTensor& t, float* master, int64_t i, int64_t j) {
+  const float p = master[i];
+  const float g = ld1<DT>(t.g, j);
+  const float b = t.rd_b ? ld1<CHOCO_DT_F32>(t.buf, j) : 0.0f;
+  float nb = 0.0f, out;
+  sgd_math<CHOCO_DT_F32>(t, p, g, b, nb, out);
+  if (DT != CHOCO_DT_F32) asm("" : "+v"(out));  // the narrowing below starts from the rounded fp32 (see rnd)
+  if (t.wr_b) st1<CHOCO_DT_F32>(t.buf, j, nb);
+  master[i] = out;
+  if (t.wr_p) st1<DT>(t.p, j, out);
+}
+
+// Flat elements [a, b) of a tensor at flat offset o0, a < b inside this workgroup's tile; one
+// 8-element group in flight per thread, every load issued before the first store.
+template <int DT>
+CHOCO_DEV void master_span(const SgdTensor& t, float* master, int64_t o0, int64_t a, int64_t b, bool vec) {
+  const int tid = threadIdx.x;
+  if (!vec) {
+    for (int64_t i = a + tid; i < b; i += kPbThreads) master_elem<DT>(t, master, i, i - o0);
+    return;
+  }
+  const int64_t g0 = a >> 3, g1 = (b - 1) >> 3;  // groups at absolute flat offsets, inclusive
+  for (int64_t gb = g0; gb <= g1; gb += kPbThreads) {
+    const int64_t e = (gb + tid) * kPbGroup;
+    if (e >= a && e + kPbGroup <= b) {
+      Raw8 rp, rg, rb;
+      ld8<CHOCO_DT_F32>(rp, master, e);
+      ld8<DT>(rg, t.g, e - o0);
+      if (t.rd_b) ld8<CHOCO_DT_F32>(rb, t.buf, e - o0);
+      float p[8], g[8], bi[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      float nb[8] = {0, 0, 0, 0, 0, 0, 0, 0}, out[8];
+      widen8<CHOCO_DT_F32>(rp, p);
+      widen8<DT>(rg, g);
+      if (t.rd_b) widen8<CHOCO_DT_F32>(rb, bi);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        sgd_math<CHOCO_DT_F32>(t, p[k], g[k], bi[k], nb[k], out[k]);
+        if (DT != CHOCO_DT_F32) asm("" : "+v"(out[k]));
+      }
+      if (t.wr_b) st8<CHOCO_DT_F32>(t.buf, e - o0, nb);
+      st8<CHOCO_DT_F32>(master, e, out);
+      if (t.wr_p) st8<DT>(t.p, e - o0, out);
+    } else {
+      // a group cut by the tensor's start or end (or past the span): its own elements only
+      const int64_t ea = e > a ? e : a, eb = e + kPbGroup < b ? e + kPbGroup : b;
+      for (int64_t i = ea; i < eb; ++i) master_elem<DT>(t, master, i, i - o0);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kPbThreads) void param_sgd_master_kernel(const SgdTable tb, float* master, int64_t tile0,
+                                                                      int32_t master16, int32_t mode) {
+  const int nt = tb.nt;
+  int64_t tlo, thi;
+  const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
+  if (s0 < 0) return;
+  for (int s = s0; s < nt; ++s) {
+    const int64_t o0 = tb.off[s];
+    if (o0 >= thi) break;
+    const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);
+    const uint32_t fl = tb.fl[s];
+    if (a >= b || (fl & CHOCO_SGD_F_NOGRAD)) continue;  // zero-length, or no gradient: passed over
+    const int dt = tb.dt[s];
+    SgdTensor t;
+    t.p = tb.p[s]; t.g = tb.g[s]; t.buf = tb.buf[s]; t.flat = nullptr;
+    t.wd = tb.wd[s]; t.mom = tb.mom[s]; t.omd = tb.omd[s]; t.nlr = tb.nlr[s];
+    t.pack_only = false;
+    t.has_wd = (fl & kSgdHasWd) != 0;
+    t.has_mom = (fl & kSgdHasMom) != 0;
+    t.nesterov = (fl & CHOCO_SGD_F_NESTEROV) != 0;
+    t.first = (fl & CHOCO_SGD_F_FIRST) != 0;
+    t.grad_mode = false;
+    t.clip = false; t.add_flat = false;
+    t.c = 1.0f;
+    t.rd_p = true; t.rd_g = true;
+    t.rd_b = t.has_mom && !t.first;
+    t.wr_b = t.has_mom;
+    t.wr_p = (mode & CHOCO_SGD_MODE_WRITE_PARAMS) != 0;
+    t.wr_g = false;
+    // master + 4 e is 16-byte aligned at every group start e (a multiple of 8) when master is; a
+    // side q + esz (e - o0) is when q - esz o0 is -- esz the tensor's for g and p, 4 for buf
+    const uintptr_t esz = dt == CHOCO_DT_F32 ? 4u : 2u, o = (uintptr_t)o0;
+    uintptr_t mis = reinterpret_cast<uintptr_t>(t.g) - esz * o;
+    if (t.wr_p) mis |= reinterpret_cast<uintptr_t>(t.p) - esz * o;
+    if (t.wr_b) mis |= reinterpret_cast<uintptr_t>(t.buf) - 4u * o;
+    const bool vec = master16 && (mis & 15u) == 0;
+    if (dt == CHOCO_DT_F32) master_span<CHOCO_DT_F32>(t, master, o0, a, b, vec);
+    else if (dt == CHOCO_DT_BF16) master_span<CHOCO_DT_BF16>(t, master, o0, a, b, vec);
+    else master_span<CHOCO_DT_F16>(t, master, o0, a, b, vec);
+  }
+}
+
 static int sgd_launches(int32_t nseg) { return nseg <= 0 ? 0 : (nseg + kSgdCap - 1) / kSgdCap; }
 
 struct SgdArgs {
@@ -250,6 +356,7 @@ struct SgdArgs {
   bool ext;              // choco_params_sgd_clip: the ADD_FLAT bit and the two arguments below
   const float* norms;    // device, nseg per-tensor norms; nullptr: no clipping
   double clip_threshold;
+  bool master;           // choco_params_sgd_master: flat is the master copy, bufs are fp32
 };
 
 static bool elem_aligned(const void* p, uintptr_t esz) { return (reinterpret_cast<uintptr_t>(p) & (esz - 1)) == 0; }
@@ -260,6 +367,11 @@ static int sgd_check(const SgdArgs& a) {
                 "null table argument");
   CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
   CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
+  if (a.master) {
+    CHOCO_REQUIRE((a.mode & ~CHOCO_SGD_MODE_WRITE_PARAMS) == 0,
+                  "the master update runs in apply mode, optionally | WRITE_PARAMS: mode bits 0x%x", (unsigned)a.mode);
+    CHOCO_REQUIRE(a.flat, "master is null");
+  }
   constexpr int32_t kModes = CHOCO_SGD_MODE_GRAD | CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS;
   CHOCO_REQUIRE((a.mode & ~(kModes | (a.ext ? CHOCO_SGD_MODE_ADD_FLAT : 0))) == 0, "unknown mode bits 0x%x",
                 (unsigned)a.mode);
@@ -276,7 +388,7 @@ static int sgd_check(const SgdArgs& a) {
   CHOCO_REQUIRE(!(!grad_mode && (a.mode & CHOCO_SGD_MODE_WRITE_GRADS)), "apply mode does not write the grads");
   CHOCO_REQUIRE(a.flat || (a.mode & (CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS)),
                 "nothing to write: flat is null and the mode writes neither params nor grads");
-  CHOCO_REQUIRE(aligned4(a.flat), "the flat buffer must be 4-byte aligned");
+  CHOCO_REQUIRE(aligned4(a.flat), "the %s buffer must be 4-byte aligned", a.master ? "master" : "flat");
   int64_t sum = 0;
   for (int32_t s = 0; s < a.nseg; ++s) {
     const int i = (int)s;
@@ -290,7 +402,8 @@ static int sgd_check(const SgdArgs& a) {
     const bool nograd = (a.flags[s] & CHOCO_SGD_F_NOGRAD) != 0;
     CHOCO_REQUIRE(!(nograd && grad_mode), "tensor %d: a no-grad tensor in grad mode", i);
     const uintptr_t esz = a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u;
-    CHOCO_REQUIRE(elem_aligned(a.params[s], esz) && elem_aligned(a.grads[s], esz) && elem_aligned(a.bufs[s], esz),
+    CHOCO_REQUIRE(elem_aligned(a.params[s], esz) && elem_aligned(a.grads[s], esz) &&
+                      elem_aligned(a.bufs[s], a.master ? 4u : esz),  // a master update's buffers are fp32
                   "tensor %d: pointer not aligned to its element size", i);
     if (!nograd) {
       // the reference's constructors refuse these (torch.optim.SGD's rule)
@@ -342,7 +455,10 @@ static int sgd_run(const SgdArgs& a, hipStream_t st) {
     const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
     const float* norms = a.norms ? a.norms + s0 : nullptr;
     const float thr = (float)a.clip_threshold;
-    if (a.ext)
+    if (a.master)
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_master_kernel", "param_sgd_master_kernel", param_sgd_master_kernel,
+                             dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.flat, tile0, flat16, a.mode));
+    else if (a.ext)
       CHOCO_TRY(CHOCO_LAUNCH("param_sgd_kernel", "param_sgd_kernel<clip>", param_sgd_kernel<true>,
                              dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.flat, tile0, flat16, a.mode, norms,
                              thr));
@@ -649,7 +765,19 @@ CHOCO_API int choco_params_sgd(void* const* params, const void* const* grads, vo
                                const double* momentum, const double* dampening, const int32_t* flags, int32_t nseg,
                                float* flat, int64_t n, int32_t mode, void* stream) {
   const SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, flat, n, mode,
-                  false, nullptr, 0.0};
+                  false, nullptr, 0.0, false};
+  return sgd_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_sgd_master_launches(int32_t nseg) { return sgd_launches(nseg); }
+
+CHOCO_API int choco_params_sgd_master(void* const* params, const void* const* grads, void* const* bufs,
+                                      const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                      const double* weight_decay, const double* momentum, const double* dampening,
+                                      const int32_t* flags, int32_t nseg, float* master, int64_t n, int32_t mode,
+                                      void* stream) {
+  const SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, master, n,
+                  mode, false, nullptr, 0.0, true};
   return sgd_run(a, as_stream(stream));
 }
 
@@ -659,7 +787,7 @@ CHOCO_API int choco_params_sgd_clip(void* const* params, const void* const* grad
                                     const int32_t* flags, int32_t nseg, float* flat, int64_t n, int32_t mode,
                                     const float* norms, double clip_threshold, void* stream) {
   const SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, flat, n, mode,
-                  true, norms, clip_threshold};
+                  true, norms, clip_threshold, false};
   return sgd_run(a, as_stream(stream));
 }
 

@@ -60,6 +60,138 @@ def _sgd_plan(params):
     return plan
 
 
+class MasterWeights:
+    """fp32 master weights of a bf16 / fp16 model: the persistent flat fp32 copy of the
+    parameters the optimizer update runs on (apply_gradient(master=...), fused_step(master=...),
+    dpsgd_step(master=...)), so that an update smaller than half a 16-bit ulp of a parameter is
+    kept from one step to the next.  The model's parameters are the round-to-nearest-even
+    narrowing of the master; the momentum buffers of a master update are fp32.
+
+    Built by one pack of the model (widening is exact: narrow(master) == params from the start).
+    Every group must hold one parameter, named once in param_names, as the reference's groups
+    do; the flat layout is param_names' order.
+        flat      the TensorBuffer over the master (`buffer`: its flat fp32 tensor)
+        spare     a second flat buffer of the same size, allocated on first use (dpsgd_step
+                  mixes into it and swaps the two)"""
+
+    def __init__(self, param_groups, param_names):
+        entries = step_entries(param_groups, param_names, "MasterWeights")
+        params = [p for _, p in entries]
+        if not all(p.dtype in codec.PARAM_DTYPES for p in params):
+            raise RuntimeError("MasterWeights needs float32, bfloat16 or float16 parameters")
+        self.param_names = list(param_names)
+        self.flat = TensorBuffer([p.data for p in params], dtype=torch.float32)
+        self._spare = None
+        self._numel = self.flat.buffer.numel()
+        self._seen = None  # entries()' last checked (param_groups, entries, device)
+
+    @property
+    def buffer(self):
+        return self.flat.buffer
+
+    @property
+    def spare(self):
+        if self._spare is None:
+            self._spare = torch.empty_like(self.flat.buffer)
+        return self._spare
+
+    def swap(self):
+        """The spare buffer becomes the master and the other way round."""
+        self.flat.buffer, self._spare = self.spare, self.flat.buffer
+
+    def entries(self, param_groups):
+        """[(group, param)] in the master's order; raises where the master does not fit them
+        (another layout, size or device)."""
+        buf = self.flat.buffer
+        if buf.dtype != torch.float32 or buf.dim() != 1 or not buf.is_contiguous() or buf.numel() != self._numel:
+            raise RuntimeError(f"the master buffer must be a flat contiguous float32 tensor of {self._numel} elements")
+        seen = self._seen
+        # the very objects the last call checked, on the buffer's device: one pass of identity tests
+        if (seen is not None and seen[0] is param_groups and seen[2] == buf.device and len(param_groups) == len(seen[1])
+                and all(len(g["params"]) == 1 and g["params"][0] is p for g, p in seen[1])):
+            return seen[1]
+        entries = step_entries(param_groups, self.param_names, "a step with master weights")
+        if ([p.size() for _, p in entries] != self.flat._tensors_sizes
+                or any(p.device != buf.device for _, p in entries)):
+            raise RuntimeError("the master weights do not fit this model: another layout or device")
+        self._seen = (param_groups, entries, buf.device)
+        return entries
+
+    def to_model(self, param_groups):
+        """The unpack: every parameter = its master slice narrowed to the parameter's dtype."""
+        self.flat.unpack([p.data for _, p in self.entries(param_groups)])
+
+    def from_model(self, param_groups):
+        """The re-pack, after the model's parameters were written from outside (a checkpoint of
+        the 16-bit model, a broadcast): master = the parameters widened."""
+        params = [p.data for _, p in self.entries(param_groups)]
+        self.flat.buffer.copy_(flatten(params, dtype=torch.float32))
+
+    def state_dict(self):
+        return {"master": self.flat.buffer}
+
+    def load_state_dict(self, state_dict):
+        src = state_dict["master"]
+        if src.numel() != self.flat.buffer.numel() or src.dtype != torch.float32:
+            raise RuntimeError(f"the saved master holds {src.numel()} {src.dtype} elements, this one "
+                               f"{self.flat.buffer.numel()} float32")
+        self.flat.buffer.copy_(src.reshape(-1))
+
+
+def apply_gradient_master_loop(param_groups, state, master, write=True):
+    """apply_gradient on master weights as one torch op per line and tensor, on fp32 views of
+    the master with p.grad.float(), then p.data.copy_(view) (write): the path CPU tensors, and
+    anything the batched kernel does not take, keep.  Same bits as the kernel, which in fp32 are
+    apply_gradient_loop's."""
+    entries = master.entries(param_groups)
+    _master_bufs_are_fp32(entries, state)
+    for i, (group, p) in enumerate(entries):
+        if p.grad is None:
+            continue
+        weight_decay, momentum = group["weight_decay"], group["momentum"]
+        view = master.flat[i]
+        d_p = p.grad.data.float()
+        if weight_decay != 0:
+            d_p = d_p.add(view, alpha=weight_decay)  # out of place: p.grad keeps its values
+        if momentum != 0:
+            param_state = state[p]
+            if "momentum_buffer" not in param_state:
+                buf = param_state["momentum_buffer"] = torch.zeros_like(p.data, dtype=torch.float32)
+                buf.mul_(momentum).add_(d_p)
+            else:
+                buf = param_state["momentum_buffer"]
+                buf.mul_(momentum).add_(d_p, alpha=1 - group["dampening"])
+            d_p = d_p.add(buf, alpha=momentum) if group["nesterov"] else buf
+        view.add_(d_p, alpha=-group["lr"])
+        if write:
+            p.data.copy_(view)
+
+
+def _not_fp32(dtype):
+    return RuntimeError(f"a step with master weights needs float32 momentum buffers, found {dtype}: convert "
+                        "optimizer.state's buffers (buf.float()) when switching to master weights")
+
+
+def _master_bufs_are_fp32(entries, state):
+    for _, p in entries:
+        buf = (state.get(p) or {}).get("momentum_buffer")
+        if buf is not None and buf.dtype != torch.float32:
+            raise _not_fp32(buf.dtype)
+
+
+def _sgd_master(param_groups, state, master, write):
+    """apply_gradient on the master weights: the batched launch, or the loop above for tensors
+    the kernel does not take.  Raises, with nothing changed, where the master does not fit the
+    model or a momentum buffer is not fp32."""
+    entries = master.entries(param_groups)
+    plan = _sgd_fill(entries, state, True, master.buffer, master=True)
+    if plan is None:
+        apply_gradient_master_loop(param_groups, state, master, write)
+    else:
+        plan.run_master(master.buffer, write)
+    return plan
+
+
 def _sgd_batched(entries, state, apply_grad_to_model, flat, write):
     """One batched launch (per chunk) for `entries`, a list of (group, param) in flat order.
     Returns False, with nothing changed, where a tensor cannot take it."""
@@ -70,10 +202,11 @@ def _sgd_batched(entries, state, apply_grad_to_model, flat, write):
     return True
 
 
-def _sgd_fill(entries, state, apply_grad_to_model, flat):
+def _sgd_fill(entries, state, apply_grad_to_model, flat, master=False):
     """The plan of `entries` with this step's pointers, flags and hyperparameters written (and
     missing momentum buffers created), ready to run; None, with nothing changed, where a tensor
-    cannot take the batched kernels."""
+    cannot take the batched kernels.  master: `flat` is the master copy and the momentum buffers
+    are fp32 (plan.run_master follows)."""
     if not entries:
         return None
     params = [p for _, p in entries]
@@ -83,7 +216,7 @@ def _sgd_fill(entries, state, apply_grad_to_model, flat):
         return None
     pp, gp, bp, flags, seen = plan.param_ptrs, plan.grad_ptrs, plan.buf_ptrs, plan.flags, plan.seen
     created = []
-    ok = True
+    ok, wrong = True, None
     for i, (group, p) in enumerate(entries):
         momentum = group["momentum"]
         g = p.grad
@@ -99,10 +232,12 @@ def _sgd_fill(entries, state, apply_grad_to_model, flat):
             param_state = state[p]
             buf = param_state.get("momentum_buffer")
             if buf is None:  # written, not read, by its first step
-                buf = param_state["momentum_buffer"] = torch.zeros_like(p.data)
+                buf = torch.zeros_like(p.data, dtype=torch.float32 if master else None)
+                param_state["momentum_buffer"] = buf
                 created.append(param_state)
                 fl |= codec.SGD_F_FIRST
-            if not plan.fits(i, buf):
+            if not (plan.fits_master_buf(i, buf) if master else plan.fits(i, buf)):
+                wrong = buf.dtype if master and buf.dtype != torch.float32 else None
                 ok = False
                 break
             b_ptr = buf.data_ptr()
@@ -117,11 +252,13 @@ def _sgd_fill(entries, state, apply_grad_to_model, flat):
     if not ok:
         for param_state in created:
             del param_state["momentum_buffer"]
+        if wrong is not None:  # a 16-bit step's buffer: no silent fall-back to the loop
+            raise _not_fp32(wrong)
         return None
     return plan
 
 
-def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None):
+def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None, master=None):
     """optim/utils.py:13-47: weight decay, momentum with dampening, optional Nesterov, then
     p -= lr * d_p (apply_grad_to_model) or d_p left as the gradient.  Missing
     state[p]["momentum_buffer"] entries are created.  fp32 / bf16 / fp16 ROCm tensors take ONE
@@ -136,7 +273,20 @@ def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None)
     Two differences from the reference, by design: with apply_grad_to_model the grad tensors
     are never written (the reference adds the weight decay into p.grad in place); without it
     d_p is written into the existing grad tensors' storage and p.grad is not rebound to the
-    momentum buffer object."""
+    momentum buffer object.
+
+    master (a MasterWeights of this model; apply_grad_to_model only, no flat_out): the update
+    runs in fp32 on the master copy, in place, and the parameters receive its values narrowed
+    to their dtype -- one launch of codec.params_sgd_master per chunk.  Missing momentum
+    buffers are created as fp32; an existing one of another dtype raises."""
+    if master is not None:
+        if not apply_grad_to_model:
+            raise RuntimeError("apply_gradient(master=...) updates the model: apply_grad_to_model=False has no "
+                               "master variant")
+        if flat_out is not None:
+            raise RuntimeError("apply_gradient(master=...): the master buffer is the flat copy; flat_out has no use")
+        _sgd_master(param_groups, state, master, write=True)
+        return
     entries = [(group, p) for group in param_groups for p in group["params"]]
     flat = getattr(flat_out, "buffer", flat_out)
     if _sgd_batched(entries, state, apply_grad_to_model, flat, write=True):
@@ -167,7 +317,7 @@ def recover_params(param_groups, param_names, rank=None, neighbor_hat_params=Non
 
 
 def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_params, neighbors_info,
-               consensus_stepsize, rank, defer_receive=False, state=None):
+               consensus_stepsize, rank, defer_receive=False, state=None, master=None):
     """ParallelCHOCO_V.step after apply_gradient (parallel_choco_v.py:115-155), with the
     consensus step fused into the compressor's first pass: recover_params, then
     compress (x += gamma * (memory - x_hat_i) and d = x_new - x_hat_i in one pass), sync,
@@ -187,9 +337,22 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
     g and the momentum buffer and writes the buffer and the flat x.  The launch does not write
     the params (the unpack at the end writes them and nothing in between reads them) and
     recover_params' pack is skipped.  Every group must hold one parameter, named in
-    param_names, as the reference's groups do."""
+    param_names, as the reference's groups do.
+
+    master (a MasterWeights of this model; needs state): the step's first launch is the update
+    on the master copy (the params are not written), and the master's buffer is the step's
+    flatten_params -- no flat buffer is allocated and nothing is packed.  Compress, gossip,
+    sync and uncompress work on it as on any flat x, and the unpack at the end narrows it into
+    the model."""
     flatten_params = None
-    if state is not None:
+    if master is not None:
+        if state is None:
+            raise RuntimeError("fused_step(master=...) runs apply_gradient itself: pass state=optimizer.state")
+        if master.param_names != list(param_names):
+            raise RuntimeError("fused_step(master=...): the master weights were built for other param_names")
+        _sgd_master(param_groups, state, master, write=False)
+        flatten_params = master.flat
+    elif state is not None:
         flatten_params = _sgd_packed(param_groups, param_names, state)
     if defer_receive:
         if flatten_params is None:
@@ -285,16 +448,35 @@ def dpsgd_step_loop(param_groups, param_names, state, aggregator):
     return get_n_bits(flatten_params.buffer)
 
 
-def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info):
+def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, master=None):
     """The decentralized branch of SGD.step (sgd.py:94-121), plain D-PSGD: apply_gradient fused
     with the pack of the new params (one launch; the params themselves are not written yet),
     the exchange of the flat fp32 buffer (_agg(op="get_raw_sync_data")), and ONE mix launch
     that writes sum(x_r * w_r) straight into the params (communication.py:271-277 and the
     unpack of sgd.py:118).  Returns n_bits.  Tensors the kernels do not take run
-    dpsgd_step_loop."""
+    dpsgd_step_loop.
+
+    master (a MasterWeights of this model): the update runs on the master copy in place, the
+    master buffer is what the neighbours exchange, and the mix writes the params and, in fp32,
+    the master's spare buffer (sources and destination never alias); the two buffers are then
+    swapped."""
     entries = step_entries(param_groups, param_names, "dpsgd_step")
     params = [p for _, p in entries]
     dev = params[0].device
+    if master is not None:
+        if master.param_names != list(param_names):
+            raise RuntimeError("dpsgd_step(master=...): the master weights were built for other param_names")
+        plan = _sgd_master(param_groups, state, master, write=False)
+        flat = master.buffer
+        if plan is None:  # the loop ran: the reference's op sequence on the master
+            master.flat.buffer = aggregator._agg(flat, op="weighted")
+            master.flat.unpack(params)
+            return get_n_bits(flat)
+        local_data = aggregator._agg(flat, op="get_raw_sync_data")
+        plan.mix(list(local_data.values()), [neighbors_info[r] for r in local_data], mode=codec.MIX_WRITE_PARAMS,
+                 flat_out=master.spare)
+        master.swap()
+        return get_n_bits(flat)
     flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
     plan = _sgd_fill(entries, state, True, flat)
     if plan is None:

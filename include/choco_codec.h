@@ -568,6 +568,40 @@ int choco_params_sgd(void* const* params, const void* const* grads, void* const*
                      const int32_t* flags, int32_t nseg, float* flat, int64_t n, int32_t mode,
                      void* stream);
 
+/* ------------------------------------------- SGD update on fp32 master weights
+ * apply_gradient (pcode/optim/utils.py:13-47) for a bf16 / fp16 model that keeps a
+ * persistent flat fp32 copy of its parameters (the reference has no 16-bit path; its
+ * fp32 path is the yardstick).  The tables are those of choco_params_sgd, except that
+ * bufs[s], the momentum buffer, holds lens[s] FP32 elements whatever dtypes[s] is (4-byte
+ * aligned); grads[s] has the tensor's dtype.  master (DEVICE, n fp32 elements, never
+ * NULL, 4-byte aligned) is laid out as the flat buffer of choco_params_sgd.  The master
+ * contract, per element (flat index i, element j of tensor s):
+ *     p = master[i]; g = grads[s][j] widened (exact); buf = bufs[s][j]
+ *     the lines of choco_params_sgd in apply mode, computed as for an fp32 tensor:
+ *     nothing is narrowed between them, a skipped op is skipped, the scalars are
+ *     converted as there
+ *     master[i] = p_new (in place); bufs[s][j] = buf (fp32, when momentum != 0)
+ *     WRITE_PARAMS: params[s][j] = p_new narrowed round-to-nearest-even to dtypes[s],
+ *     the narrowing of choco_params_unpack (an fp32 tensor receives p_new itself)
+ * so master follows, bit for bit, the trajectory of the fp32 model on the widened
+ * gradients, and the 16-bit parameters are its narrowing.  A CHOCO_SGD_F_NOGRAD tensor
+ * is passed over: neither its master slice nor its parameter is read or written.
+ * Without WRITE_PARAMS the parameters are not touched at all.
+ *   mode: CHOCO_SGD_MODE_APPLY, optionally | CHOCO_SGD_MODE_WRITE_PARAMS; GRAD,
+ *     WRITE_GRADS and ADD_FLAT are rejected.
+ * Only the bytes of the layout's own elements are written.  Every argument is checked
+ * before the first launch without a HIP call, as choco_params_sgd checks its own (the
+ * NESTEROV rule and sum(lens) == n included), and a bad one returns CHOCO_ERR_INVALID and
+ * launches nothing.  A layout takes choco_params_sgd_master_launches(nseg) launches of
+ * "param_sgd_master_kernel". */
+int choco_params_sgd_master_launches(int32_t nseg);
+/* pcode/optim/utils.py:13-47 */
+int choco_params_sgd_master(void* const* params, const void* const* grads, void* const* bufs,
+                            const int64_t* lens, const int32_t* dtypes, const double* lr,
+                            const double* weight_decay, const double* momentum, const double* dampening,
+                            const int32_t* flags, int32_t nseg, float* master, int64_t n,
+                            int32_t mode, void* stream);
+
 /* ------------------------------------------- DGC's optimizer half
  * DGC._apply_gradient (pcode/optim/dgc.py:279-324) is apply_gradient with one more
  * line: after the weight decay and before the momentum, each tensor's d_p is clipped by

@@ -9,6 +9,10 @@ elements; each parameter its own allocation; weight decay + momentum, no Nestero
                 repository can run it), then utils.recover_params(get_hat_params=False)
   (b) fused_*   utils.apply_gradient(..., flat_out=flat): the update and the pack in one launch
                 per chunk of tensors
+  (c) master_*  utils.apply_gradient(..., master=mw): the update on the persistent fp32 master
+                copy with fp32 momentum buffers, the params written narrowed, one launch per
+                chunk of tensors (param_sgd_master_kernel); its yardstick is the fp32 layout's
+                kernel_tbps_sgd of the same run
   host_us       host wall time per step: `steps` steps queued, one synchronise, divided
   gpu_us        the same window between two device events
   launches      device activities (kernels + copies) of one step, from torch.profiler
@@ -139,17 +143,32 @@ def measure(name, lens, dtype, steps, reps):
     def fused_step():
         utils.apply_gradient(gb, sb, flat_out=flat)
 
+    pm, gm, nm = model(lens, dtype)
+    sm = collections.defaultdict(dict)
+    mw = utils.MasterWeights(gm, nm)
+
+    def master_step():
+        utils.apply_gradient(gm, sm, master=mw)
+
     loop_host, loop_gpu = median_of(loop_step, steps, reps)
     fused_host, fused_gpu = median_of(fused_step, steps, reps)
+    master_host, master_gpu = median_of(master_step, steps, reps)
     sgd_bytes = n * (5 * esz + 4)   # reads p, g, buf; writes buf, p and the fp32 flat
+    master_bytes = n * (2 * esz + 16)  # reads master, g, the fp32 buf; writes buf, master and p
     pack_bytes = n * (esz + 4)
     k_sgd, l_sgd = kernel_time(fused_step, "param_sgd_kernel")
     k_pack, l_pack = kernel_time(loop_step, "param_pack_kernel")
+    k_master, l_master = kernel_time(master_step, "param_sgd_master_kernel")
     row = {"layout": name, "tensors": len(lens), "elements": n, "param_dtype": str(dtype).split(".")[-1],
            "steps": steps, "reps": reps,
            "loop_host_us": round(loop_host, 1), "loop_gpu_us": round(loop_gpu, 1), "loop_launches": count_launches(loop_step),
            "fused_host_us": round(fused_host, 1), "fused_gpu_us": round(fused_gpu, 1),
-           "fused_launches": count_launches(fused_step), "sgd_bytes": sgd_bytes, "pack_bytes": pack_bytes}
+           "fused_launches": count_launches(fused_step), "sgd_bytes": sgd_bytes, "pack_bytes": pack_bytes,
+           "master_host_us": round(master_host, 1), "master_gpu_us": round(master_gpu, 1),
+           "master_launches": count_launches(master_step), "master_bytes": master_bytes}
+    if k_master:
+        row.update(kernel_us_master=round(k_master, 2), kernel_launches_master=l_master,
+                   kernel_tbps_master=round(master_bytes / k_master / 1e6, 3))
     if k_sgd:
         row.update(kernel_us_sgd=round(k_sgd, 2), kernel_launches_sgd=l_sgd,
                    kernel_tbps_sgd=round(sgd_bytes / k_sgd / 1e6, 3))
