@@ -116,6 +116,11 @@ SIGNATURES = {
     "choco_params_sgd_master_launches": (_c_i32, [_c_i32]),
     "choco_params_sgd_master": (_c_i32, [_pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64, _p_i32, _c_i32,
                                          _vp, _c_i64, _c_i32, _vp]),
+    "choco_params_sgd_flatgrad_launches": (_c_i32, [_c_i32]),
+    "choco_params_sgd_flatgrad": (_c_i32, [_pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64, _p_i32,
+                                           _c_i32, _vp, _c_i64, _c_f64, _c_i32, _vp]),
+    "choco_params_sgd_master_flatgrad": (_c_i32, [_pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64,
+                                                  _p_i32, _c_i32, _vp, _vp, _c_i64, _c_f64, _c_i32, _vp]),
     "choco_params_sqnorm_workspace_size":(_c_sz, [_c_i32, _c_i64]),
     "choco_params_sqnorm_launches": (_c_i32, [_c_i32]),
     "choco_params_sqnorm": (_c_i32, [_pp, _pp, _p_i64, _p_i32, _p_f64, _p_i32, _c_i32, _c_i64, _vp, _vp, _c_sz, _vp]),

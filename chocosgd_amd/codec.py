@@ -1169,6 +1169,39 @@ class ParamSgdPlan:
                                                  SGD_MODE_WRITE_PARAMS if write else 0, _stream(self.device)),
                    "choco_params_sgd_master")
 
+    def pack_grads(self, flat):
+        """One choco_params_pack of the gradients behind `grad_ptrs` as they stand into `flat`
+        (fp32, n elements), widening 16-bit gradients (exact): TensorBuffer(grads) of
+        sgd.py:71-74 with no table built per step."""
+        _require(flat, torch.float32, "flat")
+        if flat.device != self.device or flat.numel() != self.n:
+            raise RuntimeError(f"flat must hold {self.n} elements on {self.device}")
+        _lib.check(lib().choco_params_pack(self.grad_ptrs, self.lens, self.dts, self.nseg, _ptr(flat), self.n,
+                                           _stream(self.device)), "choco_params_pack")
+
+    def run_flatgrad(self, gsum, divisor, write=True, write_grads=True, master=None):
+        """One choco_params_sgd_flatgrad (master: choco_params_sgd_master_flatgrad) over the
+        tables as they stand: the update whose gradient is gsum / divisor, gsum the flat fp32
+        buffer of the all-reduced gradient sum (n elements).  write -> the params are written;
+        write_grads -> the averaged gradient goes into the storage behind `grad_ptrs`, narrowed
+        to the tensor's dtype.  master (flat fp32, n elements): the update runs on it in place
+        with fp32 momentum buffers and the unrounded average."""
+        _require(gsum, torch.float32, "gsum")
+        if gsum.device != self.device or gsum.numel() != self.n:
+            raise RuntimeError(f"gsum must hold {self.n} elements on {self.device}")
+        mode = (SGD_MODE_WRITE_PARAMS if write else 0) | (SGD_MODE_WRITE_GRADS if write_grads else 0)
+        head = (self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts, self.lr, self.weight_decay,
+                self.momentum, self.dampening, self.flags, self.nseg, _ptr(gsum))
+        if master is None:
+            _lib.check(lib().choco_params_sgd_flatgrad(*head, self.n, float(divisor), mode, _stream(self.device)),
+                       "choco_params_sgd_flatgrad")
+            return
+        _require(master, torch.float32, "master")
+        if master.device != self.device or master.numel() != self.n:
+            raise RuntimeError(f"master must hold {self.n} elements on {self.device}")
+        _lib.check(lib().choco_params_sgd_master_flatgrad(*head, _ptr(master), self.n, float(divisor), mode,
+                                                          _stream(self.device)), "choco_params_sgd_master_flatgrad")
+
     def mix(self, srcs, weights, lr=0.0, mode=0, ext_a=0.0, ext_b=0.0, flat_out=None, x_out=None):
         """One choco_params_mix over the plan's parameter and gradient pointers as they stand
         (params_mix describes the arguments)."""
@@ -1324,6 +1357,29 @@ def params_sgd_master(params, grads, bufs, lr, weight_decay=0.0, momentum=0.0, d
         raise RuntimeError("params_sgd_master needs the master buffer")
     plan = _sgd_tables(params, grads, bufs, lr, weight_decay, momentum, dampening, nesterov, first, plan, True)
     plan.run_master(master, write)
+    return plan
+
+
+def params_sgd_flatgrad_launches(nseg):
+    """Launches one params_sgd_flatgrad of `nseg` tensors takes (with or without master)."""
+    return int(lib().choco_params_sgd_flatgrad_launches(int(nseg)))
+
+
+def params_sgd_flatgrad(params, grads, bufs, gsum, divisor, lr, weight_decay=0.0, momentum=0.0, dampening=0.0,
+                        nesterov=False, first=False, master=None, write=True, write_grads=True, plan=None):
+    """The all-reduce SGD update (sgd.py:82-89; include/choco_codec.h, choco_params_sgd_flatgrad
+    and choco_params_sgd_master_flatgrad): params_sgd's arguments in apply mode, except that the
+    gradient is gsum / divisor -- gsum the flat fp32 buffer of the summed gradients, the tensors
+    back to back -- narrowed to each tensor's dtype, and grads[s] is where that averaged gradient
+    is written (write_grads; otherwise grads may be None).  master (flat fp32): the update runs
+    on it in place with fp32 bufs and the average is not narrowed.  Returns the plan (pass it
+    back in to reuse its tables)."""
+    plan = _sgd_tables(params, grads, bufs, lr, weight_decay, momentum, dampening, nesterov, first, plan,
+                       master is not None)
+    if not write_grads:  # the grads are outputs here: none written, none needed
+        for i in range(plan.nseg):
+            plan.flags[i] &= ~SGD_F_NOGRAD
+    plan.run_flatgrad(gsum, divisor, write, write_grads, master)
     return plan
 
 

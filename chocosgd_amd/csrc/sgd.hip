@@ -336,6 +336,149 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_master_kernel(const SgdT
   }
 }
 
+// ------------------------------------------------------------------ all-reduce SGD: the flat summed gradient
+// The centralized branch of SGD.step (dl_code/pcode/optim/sgd.py:68-92) after the all-reduce
+// (choco_params_sgd_flatgrad, choco_params_sgd_master_flatgrad): the gradient side of the update
+// is gsum, the flat fp32 buffer holding the all-reduced SUM, and the `/ world_size` of
+// _agg(op="avg") (communication.py:186-187) is folded in.  Per flat index i, element j:
+//     a = __fdiv_rn(gsum[i], div)                a correctly rounded division, never a reciprocal multiply
+//     16-bit / fp32 step:  g = rnd<DT>(a)        flatten_grads.unpack(grads) narrows into the grad's dtype
+//                          sgd_math<DT>(p[j], g, buf[j]) in apply mode; WRITE_GRADS: grad[j] = g
+//     master step:         g = a, not narrowed   sgd_math<F32>(master[i], g, buf32[j]); master[i] = p_new;
+//                          WRITE_PARAMS: p[j] = narrow16(p_new); WRITE_GRADS: grad[j] = narrow16(a)
+// Kernels of their own: param_sgd_kernel and param_sgd_master_kernel are not touched.  Same
+// table, tiles and search; one 8-element group in flight per thread, every load issued before
+// the first store.  A tensor takes the 16-byte path when gsum (and master) is 16-byte aligned
+// and every side it touches is congruent with the group grid at that side's own element size:
+// p, g and buf at the tensor's in the plain step; p and g at the tensor's, buf at 4 bytes in the
+// master step.  Every tensor has a gradient here (the flat buffer has no slot to skip: the host
+// refuses NOGRAD).
+
+// flat index i, element j of the tensor
+template <int DT, bool MASTER>
+CHOCO_DEV void flatgrad_elem(const SgdTensor& t, const float* gsum, float* master, float div, int64_t i, int64_t j) {
+  float a = __fdiv_rn(gsum[i], div);
+  float nb = 0.0f, out;
+  if (MASTER) {
+    const float p = master[i];
+    const float b = t.rd_b ? ld1<CHOCO_DT_F32>(t.buf, j) : 0.0f;
+    sgd_math<CHOCO_DT_F32>(t, p, a, b, nb, out);
+    if (DT != CHOCO_DT_F32) {  // the narrowings below start from the rounded fp32 values (see rnd)
+      asm("" : "+v"(out));
+      asm("" : "+v"(a));
+    }
+    if (t.wr_b) st1<CHOCO_DT_F32>(t.buf, j, nb);
+    master[i] = out;
+    if (t.wr_p) st1<DT>(t.p, j, out);
+    if (t.wr_g) st1<DT>(t.g, j, a);
+  } else {
+    const float p = ld1<DT>(t.p, j);
+    const float b = t.rd_b ? ld1<DT>(t.buf, j) : 0.0f;
+    const float g = rnd<DT>(a);
+    sgd_math<DT>(t, p, g, b, nb, out);
+    if (t.wr_b) st1<DT>(t.buf, j, nb);
+    if (t.wr_p) st1<DT>(t.p, j, out);
+    if (t.wr_g) st1<DT>(t.g, j, g);
+  }
+}
+
+// Flat elements [a, b) of a tensor at flat offset o0, a < b inside this workgroup's tile.
+template <int DT, bool MASTER>
+CHOCO_DEV void flatgrad_span(const SgdTensor& t, const float* gsum, float* master, float div, int64_t o0, int64_t a,
+                             int64_t b, bool vec) {
+  constexpr int BDT = MASTER ? CHOCO_DT_F32 : DT;  // the momentum buffer's dtype
+  const int tid = threadIdx.x;
+  if (!vec) {
+    for (int64_t i = a + tid; i < b; i += kPbThreads) flatgrad_elem<DT, MASTER>(t, gsum, master, div, i, i - o0);
+    return;
+  }
+  const int64_t g0 = a >> 3, g1 = (b - 1) >> 3;  // groups at absolute flat offsets, inclusive
+  for (int64_t gb = g0; gb <= g1; gb += kPbThreads) {
+    const int64_t e = (gb + tid) * kPbGroup;
+    if (e >= a && e + kPbGroup <= b) {
+      Raw8 rs, rp, rb;
+      ld8<CHOCO_DT_F32>(rs, gsum, e);
+      if (MASTER) ld8<CHOCO_DT_F32>(rp, master, e);
+      else ld8<DT>(rp, t.p, e - o0);
+      if (t.rd_b) ld8<BDT>(rb, t.buf, e - o0);
+      float g[8], p[8], bi[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      float nb[8] = {0, 0, 0, 0, 0, 0, 0, 0}, out[8];
+      widen8<CHOCO_DT_F32>(rs, g);
+      widen8<MASTER ? CHOCO_DT_F32 : DT>(rp, p);
+      if (t.rd_b) widen8<BDT>(rb, bi);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        g[k] = __fdiv_rn(g[k], div);
+        if (MASTER) {
+          sgd_math<CHOCO_DT_F32>(t, p[k], g[k], bi[k], nb[k], out[k]);
+          if (DT != CHOCO_DT_F32) {
+            asm("" : "+v"(out[k]));
+            asm("" : "+v"(g[k]));
+          }
+        } else {
+          g[k] = rnd<DT>(g[k]);
+          sgd_math<DT>(t, p[k], g[k], bi[k], nb[k], out[k]);
+        }
+      }
+      if (t.wr_b) st8<BDT>(t.buf, e - o0, nb);
+      if (MASTER) st8<CHOCO_DT_F32>(master, e, out);
+      if (t.wr_p) st8<DT>(t.p, e - o0, out);
+      if (t.wr_g) st8<DT>(t.g, e - o0, g);
+    } else {
+      // a group cut by the tensor's start or end (or past the span): its own elements only
+      const int64_t ea = e > a ? e : a, eb = e + kPbGroup < b ? e + kPbGroup : b;
+      for (int64_t i = ea; i < eb; ++i) flatgrad_elem<DT, MASTER>(t, gsum, master, div, i, i - o0);
+    }
+  }
+}
+
+// al16: bit 0 gsum, bit 1 master 16-byte aligned
+template <bool MASTER>
+__global__ __launch_bounds__(kPbThreads) void param_sgd_flatgrad_kernel(const SgdTable tb, const float* gsum,
+                                                                        float* master, int64_t tile0, float div,
+                                                                        int32_t al16, int32_t mode) {
+  const int nt = tb.nt;
+  int64_t tlo, thi;
+  const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
+  if (s0 < 0) return;
+  for (int s = s0; s < nt; ++s) {
+    const int64_t o0 = tb.off[s];
+    if (o0 >= thi) break;
+    const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);
+    if (a >= b) continue;  // zero-length tensor
+    const uint32_t fl = tb.fl[s];
+    const int dt = tb.dt[s];
+    SgdTensor t;
+    t.p = tb.p[s]; t.g = tb.g[s]; t.buf = tb.buf[s]; t.flat = nullptr;
+    t.wd = tb.wd[s]; t.mom = tb.mom[s]; t.omd = tb.omd[s]; t.nlr = tb.nlr[s];
+    t.pack_only = false;
+    t.has_wd = (fl & kSgdHasWd) != 0;
+    t.has_mom = (fl & kSgdHasMom) != 0;
+    t.nesterov = (fl & CHOCO_SGD_F_NESTEROV) != 0;
+    t.first = (fl & CHOCO_SGD_F_FIRST) != 0;
+    t.grad_mode = false;
+    t.clip = false; t.add_flat = false;
+    t.c = 1.0f;
+    t.rd_p = true; t.rd_g = false;
+    t.rd_b = t.has_mom && !t.first;
+    t.wr_b = t.has_mom;
+    t.wr_p = (mode & CHOCO_SGD_MODE_WRITE_PARAMS) != 0;
+    t.wr_g = (mode & CHOCO_SGD_MODE_WRITE_GRADS) != 0;
+    // gsum + 4 e (and master + 4 e) is 16-byte aligned at every group start e (a multiple of 8)
+    // when gsum is; a side q + esz (e - o0) is when q - esz o0 is -- esz the tensor's, but 4 for
+    // the master step's buf
+    const uintptr_t esz = dt == CHOCO_DT_F32 ? 4u : 2u, o = (uintptr_t)o0;
+    uintptr_t mis = 0;
+    if (!MASTER || t.wr_p) mis |= reinterpret_cast<uintptr_t>(t.p) - esz * o;
+    if (t.wr_g) mis |= reinterpret_cast<uintptr_t>(t.g) - esz * o;
+    if (t.wr_b) mis |= reinterpret_cast<uintptr_t>(t.buf) - (MASTER ? 4u : esz) * o;
+    const bool vec = al16 == (MASTER ? 3 : 1) && (mis & 15u) == 0;
+    if (dt == CHOCO_DT_F32) flatgrad_span<CHOCO_DT_F32, MASTER>(t, gsum, master, div, o0, a, b, vec);
+    else if (dt == CHOCO_DT_BF16) flatgrad_span<CHOCO_DT_BF16, MASTER>(t, gsum, master, div, o0, a, b, vec);
+    else flatgrad_span<CHOCO_DT_F16, MASTER>(t, gsum, master, div, o0, a, b, vec);
+  }
+}
+
 static int sgd_launches(int32_t nseg) { return nseg <= 0 ? 0 : (nseg + kSgdCap - 1) / kSgdCap; }
 
 struct SgdArgs {
@@ -357,9 +500,58 @@ struct SgdArgs {
   const float* norms;    // device, nseg per-tensor norms; nullptr: no clipping
   double clip_threshold;
   bool master;           // choco_params_sgd_master: flat is the master copy, bufs are fp32
+  const float* gsum;     // choco_params_sgd[_master]_flatgrad: the all-reduced sum, n fp32 (else nullptr)
+  double divisor;        // ... and what it is divided by
+  bool flatgrad;         // one of those two entry points
 };
 
 static bool elem_aligned(const void* p, uintptr_t esz) { return (reinterpret_cast<uintptr_t>(p) & (esz - 1)) == 0; }
+
+// choco_params_sgd_flatgrad / choco_params_sgd_master_flatgrad (a.flat is the
+// master copy or nullptr; a.grads, the table, may be null without WRITE_GRADS)
+static int flatgrad_check(const SgdArgs& a) {
+  const bool wr_g = (a.mode & CHOCO_SGD_MODE_WRITE_GRADS) != 0;
+  CHOCO_REQUIRE(a.params && a.bufs && a.lens && a.dtypes && a.lr && a.wd && a.mom && a.damp && a.flags,
+                "null table argument");
+  CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
+  CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
+  CHOCO_REQUIRE(!(a.mode & CHOCO_SGD_MODE_GRAD), "the flat-gradient update runs in apply mode: mode bits 0x%x",
+                (unsigned)a.mode);
+  CHOCO_REQUIRE((a.mode & ~(CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS)) == 0, "unknown mode bits 0x%x",
+                (unsigned)a.mode);
+  CHOCO_REQUIRE(a.grads || !wr_g, "WRITE_GRADS with a null grads table");
+  CHOCO_REQUIRE(aligned4(a.gsum), "gsum must be 4-byte aligned");
+  if (a.master) CHOCO_REQUIRE(a.flat && aligned4(a.flat), "master must be a 4-byte aligned device pointer");
+  // tested as the kernel divides: by the fp32 value
+  CHOCO_REQUIRE(std::isfinite(a.divisor) && (float)a.divisor != 0.0f && std::isfinite((float)a.divisor),
+                "divisor must be finite and nonzero as an fp32 value, got %g", a.divisor);
+  int64_t sum = 0;
+  for (int32_t s = 0; s < a.nseg; ++s) {
+    const int i = (int)s;
+    CHOCO_REQUIRE(a.lens[s] >= 0, "tensor %d: negative length", i);
+    CHOCO_REQUIRE(a.dtypes[s] >= CHOCO_DT_F32 && a.dtypes[s] <= CHOCO_DT_F16, "tensor %d: unknown dtype code %d", i,
+                  (int)a.dtypes[s]);
+    CHOCO_REQUIRE(a.lens[s] <= a.n - sum, "the lengths add up to more than n = %lld", (long long)a.n);
+    sum += a.lens[s];
+    constexpr int32_t kFlags = CHOCO_SGD_F_NESTEROV | CHOCO_SGD_F_FIRST | CHOCO_SGD_F_NOGRAD;
+    CHOCO_REQUIRE((a.flags[s] & ~kFlags) == 0, "tensor %d: unknown flag bits 0x%x", i, (unsigned)a.flags[s]);
+    CHOCO_REQUIRE(!(a.flags[s] & CHOCO_SGD_F_NOGRAD),
+                  "tensor %d: a no-grad tensor has no slot to skip in the flat gradient", i);
+    const uintptr_t esz = a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u;
+    CHOCO_REQUIRE(elem_aligned(a.params[s], esz) && (!a.grads || elem_aligned(a.grads[s], esz)) &&
+                      elem_aligned(a.bufs[s], a.master ? 4u : esz),  // a master update's buffers are fp32
+                  "tensor %d: pointer not aligned to its element size", i);
+    CHOCO_REQUIRE(!((a.flags[s] & CHOCO_SGD_F_NESTEROV) && (!(a.mom[s] > 0.0) || a.damp[s] != 0.0)),
+                  "tensor %d: nesterov needs momentum > 0 and dampening == 0", i);
+    if (a.lens[s] == 0) continue;
+    CHOCO_REQUIRE(a.params[s], "tensor %d: null param pointer", i);
+    CHOCO_REQUIRE(!wr_g || a.grads[s], "tensor %d: null grad pointer with WRITE_GRADS", i);
+    CHOCO_REQUIRE(a.bufs[s] || a.mom[s] == 0.0, "tensor %d: null momentum buffer with momentum != 0", i);
+  }
+  CHOCO_REQUIRE(sum == a.n, "the lengths add up to %lld, n is %lld", (long long)sum, (long long)a.n);
+  CHOCO_REQUIRE(a.n == 0 || a.gsum, "gsum is null");
+  return CHOCO_OK;
+}
 
 // Every argument is checked before the first launch, with no HIP call.
 static int sgd_check(const SgdArgs& a) {
@@ -421,7 +613,7 @@ static int sgd_check(const SgdArgs& a) {
 }
 
 static int sgd_run(const SgdArgs& a, hipStream_t st) {
-  const int rc = sgd_check(a);
+  const int rc = a.flatgrad ? flatgrad_check(a) : sgd_check(a);
   if (rc) return rc;
   const int32_t flat16 = aligned16(a.flat) ? 1 : 0;
   SgdTable tb;
@@ -435,7 +627,7 @@ static int sgd_run(const SgdArgs& a, hipStream_t st) {
       const int32_t s = s0 + i;
       const bool upd = in && !(a.flags[s] & CHOCO_SGD_F_NOGRAD);
       tb.p[i] = in ? a.params[s] : nullptr;
-      tb.g[i] = upd ? const_cast<void*>(a.grads[s]) : nullptr;
+      tb.g[i] = upd && a.grads ? const_cast<void*>(a.grads[s]) : nullptr;
       tb.buf[i] = upd ? a.bufs[s] : nullptr;
       // torch's conversion of a Python scalar for an fp32 tensor
       tb.wd[i] = upd ? (float)a.wd[s] : 0.0f;
@@ -455,7 +647,16 @@ static int sgd_run(const SgdArgs& a, hipStream_t st) {
     const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
     const float* norms = a.norms ? a.norms + s0 : nullptr;
     const float thr = (float)a.clip_threshold;
-    if (a.master)
+    const int32_t al16 = (aligned16(a.gsum) ? 1 : 0) | (a.master ? 2 * flat16 : 0);
+    if (a.flatgrad && a.master)
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_master_flatgrad_kernel", "param_sgd_master_flatgrad_kernel",
+                             param_sgd_flatgrad_kernel<true>, dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.gsum,
+                             a.flat, tile0, (float)a.divisor, al16, a.mode));
+    else if (a.flatgrad)
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_flatgrad_kernel", "param_sgd_flatgrad_kernel", param_sgd_flatgrad_kernel<false>,
+                             dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.gsum, (float*)nullptr, tile0,
+                             (float)a.divisor, al16, a.mode));
+    else if (a.master)
       CHOCO_TRY(CHOCO_LAUNCH("param_sgd_master_kernel", "param_sgd_master_kernel", param_sgd_master_kernel,
                              dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.flat, tile0, flat16, a.mode));
     else if (a.ext)
@@ -778,6 +979,35 @@ CHOCO_API int choco_params_sgd_master(void* const* params, const void* const* gr
                                       void* stream) {
   const SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, master, n,
                   mode, false, nullptr, 0.0, true};
+  return sgd_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_sgd_flatgrad_launches(int32_t nseg) { return sgd_launches(nseg); }
+
+CHOCO_API int choco_params_sgd_flatgrad(void* const* params, void* const* grads, void* const* bufs,
+                                        const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                        const double* weight_decay, const double* momentum, const double* dampening,
+                                        const int32_t* flags, int32_t nseg, const float* gsum, int64_t n,
+                                        double divisor, int32_t mode, void* stream) {
+  SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, nullptr, n, mode,
+            false, nullptr, 0.0, false};
+  a.gsum = gsum;
+  a.divisor = divisor;
+  a.flatgrad = true;
+  return sgd_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_sgd_master_flatgrad(void* const* params, void* const* grads, void* const* bufs,
+                                               const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                               const double* weight_decay, const double* momentum,
+                                               const double* dampening, const int32_t* flags, int32_t nseg,
+                                               const float* gsum, float* master, int64_t n, double divisor,
+                                               int32_t mode, void* stream) {
+  SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, master, n, mode,
+            false, nullptr, 0.0, true};
+  a.gsum = gsum;
+  a.divisor = divisor;
+  a.flatgrad = true;
   return sgd_run(a, as_stream(stream));
 }
 

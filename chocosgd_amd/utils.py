@@ -138,11 +138,12 @@ class MasterWeights:
         self.flat.buffer.copy_(src.reshape(-1))
 
 
-def apply_gradient_master_loop(param_groups, state, master, write=True):
+def apply_gradient_master_loop(param_groups, state, master, write=True, grads32=None):
     """apply_gradient on master weights as one torch op per line and tensor, on fp32 views of
     the master with p.grad.float(), then p.data.copy_(view) (write): the path CPU tensors, and
     anything the batched kernel does not take, keep.  Same bits as the kernel, which in fp32 are
-    apply_gradient_loop's."""
+    apply_gradient_loop's.  grads32 (fp32 tensors in the master's order): the gradients in
+    place of p.grad.float() (allreduce_sgd_step_loop's unrounded average)."""
     entries = master.entries(param_groups)
     _master_bufs_are_fp32(entries, state)
     for i, (group, p) in enumerate(entries):
@@ -150,7 +151,7 @@ def apply_gradient_master_loop(param_groups, state, master, write=True):
             continue
         weight_decay, momentum = group["weight_decay"], group["momentum"]
         view = master.flat[i]
-        d_p = p.grad.data.float()
+        d_p = p.grad.data.float() if grads32 is None else grads32[i]
         if weight_decay != 0:
             d_p = d_p.add(view, alpha=weight_decay)  # out of place: p.grad keeps its values
         if momentum != 0:
@@ -488,6 +489,109 @@ def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, mas
     # the running sum of more than one launch's sources needs a flat buffer of its own
     run = torch.empty_like(flat) if len(srcs) > 8 else None
     plan.mix(srcs, weights, mode=codec.MIX_WRITE_PARAMS, flat_out=run)
+    return get_n_bits(flat)
+
+
+def _allreduce_entries(param_groups, param_names, master):
+    entries = step_entries(param_groups, param_names, "allreduce_sgd_step", need_grads=True)
+    if master is not None:
+        if master.param_names != list(param_names):
+            raise RuntimeError("allreduce_sgd_step(master=...): the master weights were built for other param_names")
+        entries = master.entries(param_groups)
+    return entries
+
+
+def _apply_averaged_loop(entries, state, grads):
+    """apply_gradient_loop's lines (apply mode) with grads[i] as the gradient of entry i, each
+    line one torch op in fp32 on the widened operands and one narrowing to the tensor's dtype:
+    the kernels' documented model.  For fp32 tensors the widening and the narrowing are no-ops
+    and these are apply_gradient_loop's very ops.  For 16-bit tensors torch's own ops are not
+    that model everywhere: an fp16 op on the device rounds the exact result once, a 16-bit op on
+    the CPU rounds the product before the sum."""
+    for (group, p), g in zip(entries, grads):
+        weight_decay, momentum = group["weight_decay"], group["momentum"]
+        dt = p.dtype
+        d_p = g.data
+        if weight_decay != 0:
+            d_p = d_p.float().add(p.data.float(), alpha=weight_decay).to(dt)
+        if momentum != 0:
+            param_state = state[p]
+            first = "momentum_buffer" not in param_state
+            if first:
+                param_state["momentum_buffer"] = torch.zeros_like(p.data)
+            buf = param_state["momentum_buffer"]
+            t = buf.float().mul(momentum).to(dt)                                   # buf.mul_(momentum)
+            t = t.float().add(d_p.float(), alpha=1 if first else 1 - group["dampening"]).to(dt)  # .add_(d_p, alpha=)
+            buf.copy_(t)
+            d_p = d_p.float().add(buf.float(), alpha=momentum).to(dt) if group["nesterov"] else buf
+        p.data.copy_(p.data.float().add(d_p.float(), alpha=-group["lr"]).to(dt))
+
+
+def allreduce_sgd_step_loop(param_groups, param_names, state, aggregator, distributed=True, write_grads=True,
+                            master=None):
+    """allreduce_sgd_step as the reference's op sequence (sgd.py:69-92), one torch op per line:
+    TensorBuffer(grads) in fp32, the all-reduce, the division by the world size, the unpack into
+    the grads, apply_gradient_loop's lines (_apply_averaged_loop: for fp32 tensors the same ops;
+    16-bit tensors are widened for each line).  The path CPU tensors, and anything the batched
+    kernels do not take, keep; same bits as the kernels.  _agg(op="avg") is written out as _agg(op="sum")
+    and one division by a 0-dim tensor: on CPU tensors the same bits, and on the device a true
+    division too (torch multiplies a device tensor by the reciprocal of a Python scalar).
+
+    master: the division's fp32 result is the gradient of apply_gradient_master_loop's lines,
+    unrounded, and is then narrowed into p.grad (write_grads)."""
+    entries = _allreduce_entries(param_groups, param_names, master)
+    if master is not None:
+        _master_bufs_are_fp32(entries, state)
+    grads = [p.grad.data for _, p in entries]
+    floating = all(g.dtype in codec.PARAM_DTYPES for g in grads)
+    flatten_grads = TensorBuffer(grads, dtype=torch.float32 if floating else None)
+    flatten_grads.buffer = aggregator._agg(flatten_grads.buffer, op="sum", distributed=distributed)
+    divisor = float(aggregator.world_size) if distributed else 1.0
+    flatten_grads.buffer.div_(torch.full((), divisor, dtype=flatten_grads.buffer.dtype,
+                                         device=flatten_grads.buffer.device))
+    if master is not None:
+        apply_gradient_master_loop(param_groups, state, master, write=True,
+                                   grads32=[flatten_grads[i] for i in range(len(entries))])
+        if write_grads:
+            flatten_grads.unpack(grads)
+    else:
+        avg = grads if write_grads else [torch.empty_like(g) for g in grads]  # p.grad keeps its values
+        flatten_grads.unpack(avg)
+        _apply_averaged_loop(entries, state, avg)
+    return get_n_bits(flatten_grads.buffer)
+
+
+def allreduce_sgd_step(param_groups, param_names, state, aggregator, distributed=True, write_grads=True, master=None):
+    """The centralized branch of SGD.step (sgd.py:68-92), plain all-reduce data-parallel SGD, end
+    to end: ONE pack launch per chunk of the gradients into a flat fp32 buffer (16-bit
+    gradients are widened, which is exact), aggregator._agg(flat, op="sum",
+    distributed=distributed), and ONE update launch per chunk of 72 tensors
+    (codec.params_sgd_flatgrad) that divides the sum by aggregator.world_size (1.0 when not
+    distributed; a true division), narrows the average into each gradient's dtype and runs
+    apply_gradient's lines on it.  Returns n_bits of the flat fp32 gradient buffer.  Only
+    _agg(op="sum") and .world_size of the aggregator are used: this package's
+    CentralizedAggregation and the reference's both serve.  Every group must hold one parameter
+    with a gradient, named once in param_names, as the reference's groups do.  Tensors the
+    kernels do not take run allreduce_sgd_step_loop.
+
+    write_grads (default): p.grad's storage receives the averaged gradient, as the reference's
+    unflatten leaves it; False skips that store.  Two differences from the reference, by design:
+    its later in-place weight decay on p.grad is not reproduced (as with apply_gradient), and
+    p.grad is written in its own dtype's storage, never rebound.
+
+    master (a MasterWeights of this model): the update runs in fp32 on the master copy in place,
+    on the unrounded average, with fp32 momentum buffers (created as such; one of another dtype
+    raises), and the parameters receive the new master values narrowed
+    (codec.params_sgd_flatgrad(master=...)); p.grad receives the average narrowed."""
+    entries = _allreduce_entries(param_groups, param_names, master)
+    plan = _sgd_fill(entries, state, True, None if master is None else master.buffer, master=master is not None)
+    if plan is None:
+        return allreduce_sgd_step_loop(param_groups, param_names, state, aggregator, distributed, write_grads, master)
+    flat = torch.empty(plan.n, dtype=torch.float32, device=plan.device)
+    plan.pack_grads(flat)
+    flat = aggregator._agg(flat, op="sum", distributed=distributed)
+    plan.run_flatgrad(flat, float(aggregator.world_size) if distributed else 1.0, write=True, write_grads=write_grads,
+                      master=None if master is None else master.buffer)
     return get_n_bits(flat)
 
 

@@ -602,6 +602,57 @@ int choco_params_sgd_master(void* const* params, const void* const* grads, void*
                             const int32_t* flags, int32_t nseg, float* master, int64_t n,
                             int32_t mode, void* stream);
 
+/* ------------------------------------------- all-reduce SGD: the update reads the flat sum
+ * The centralized branch of SGD.step (pcode/optim/sgd.py:68-92), plain all-reduce
+ * data-parallel SGD, after its all-reduce: unflatten of the averaged gradient and
+ * apply_gradient as ONE launch per chunk of tensors.  The tables are those of
+ * choco_params_sgd; the gradient side of the update is gsum (DEVICE, n fp32 elements,
+ * 4-byte aligned, read only), the flat buffer of the gradients after the all-reduce SUM
+ * (sgd.py:78-80), laid out as the flat buffer of choco_params_sgd.  Per element (flat
+ * index i, element j of tensor s), every line with exactly one rounding:
+ *     a = gsum[i] / (float)divisor      communication.py:186-187, data / world_size: a
+ *                                       correctly rounded IEEE division, never a
+ *                                       reciprocal multiply; divisor == 1 runs like any other
+ *   choco_params_sgd_flatgrad (the fp32 / 16-bit step):
+ *     g = a narrowed round-to-nearest-even to dtypes[s]   flatten_grads.unpack(grads), sgd.py:84
+ *     the lines of choco_params_sgd in apply mode on params[s][j], g, bufs[s][j]
+ *     WRITE_PARAMS: params[s][j] = p_new;  WRITE_GRADS: grads[s][j] = g
+ *   choco_params_sgd_master_flatgrad (master, bufs as in choco_params_sgd_master):
+ *     g = a, fp32, NOT narrowed (the gain over the 16-bit step)
+ *     the lines of choco_params_sgd_master on master[i], g, bufs[s][j] (fp32);
+ *     master[i] = p_new
+ *     WRITE_PARAMS: params[s][j] = p_new narrowed;  WRITE_GRADS: grads[s][j] = a narrowed
+ * bufs[s] is written whenever momentum != 0.  There is no flat output of the new
+ * parameters.  grads is an OUTPUT table here: it is read by nobody, may be NULL (as may
+ * its entries) without WRITE_GRADS, and the reference's later in-place weight decay on
+ * p.grad is not reproduced.  Zero-length tensors are skipped.
+ *   mode: CHOCO_SGD_MODE_APPLY | CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS,
+ *     the two write bits usable together.
+ * Only the bytes of the layout's own elements are written; pointers need their element's
+ * alignment only.  Every argument is checked before the first launch without a HIP call,
+ * as choco_params_sgd checks its own, and these return CHOCO_ERR_INVALID and launch
+ * nothing: CHOCO_SGD_MODE_GRAD; unknown mode bits; a CHOCO_SGD_F_NOGRAD tensor (the flat
+ * gradient has no slot to skip); WRITE_GRADS with a NULL grads table or a NULL grad
+ * pointer; a divisor that is zero or not finite when cast to float; a NULL or misaligned
+ * gsum or master; momentum buffers of the master call that are not 4-byte aligned (16-bit
+ * buffers; the Python layer refuses them by dtype); misaligned element pointers.  A layout
+ * takes choco_params_sgd_flatgrad_launches(nseg) launches of "param_sgd_flatgrad_kernel"
+ * or "param_sgd_master_flatgrad_kernel". */
+int choco_params_sgd_flatgrad_launches(int32_t nseg);
+/* pcode/optim/sgd.py:68-92 */
+int choco_params_sgd_flatgrad(void* const* params, void* const* grads, void* const* bufs,
+                              const int64_t* lens, const int32_t* dtypes, const double* lr,
+                              const double* weight_decay, const double* momentum,
+                              const double* dampening, const int32_t* flags, int32_t nseg,
+                              const float* gsum, int64_t n, double divisor, int32_t mode,
+                              void* stream);
+int choco_params_sgd_master_flatgrad(void* const* params, void* const* grads, void* const* bufs,
+                                     const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                     const double* weight_decay, const double* momentum,
+                                     const double* dampening, const int32_t* flags, int32_t nseg,
+                                     const float* gsum, float* master, int64_t n, double divisor,
+                                     int32_t mode, void* stream);
+
 /* ------------------------------------------- DGC's optimizer half
  * DGC._apply_gradient (pcode/optim/dgc.py:279-324) is apply_gradient with one more
  * line: after the weight decay and before the momentum, each tensor's d_p is clipped by

@@ -20,6 +20,18 @@ elements; each parameter its own allocation; weight decay + momentum, no Nestero
                 param_pack_kernel (in (a)), and the bytes each moves divided by it
 (medians over `reps` windows after a warm-up window).
 
+All-reduce rows (--rows allreduce, or with everything else by default; one JSON line per layout:
+ResNet-50 in fp32, in bf16 and in bf16 with master weights, 3000 tensors of 100 elements), the
+centralized SGD step with a loopback aggregator (_agg returns the buffer, world size 1.0):
+  step_*     utils.allreduce_sgd_step: one pack launch and one update launch per chunk
+             (param_sgd_flatgrad_kernel / param_sgd_master_flatgrad_kernel)
+  parent_*   the four passes it replaces: codec.params_pack of the gradients, a torch divide that
+             allocates a new flat buffer, TensorBuffer.unpack into p.grad, utils.apply_gradient
+             (master: apply_gradient(master=mw), which sees the rounded gradients)
+  kernel_us_update / kernel_tbps_update: the new update kernel alone, against bytes_update;
+  kernel_us_step: pack + update; kernel_us_parent: pack + unpack + the SGD kernel, dispatch
+  attached, plus div_gpu_us, the torch divide alone between two device events.
+
 Parity rows: elements of p, buf and flat on which three steps of the kernel differ from the
 same three steps of torch's own op sequence on the device, per dtype, on the fixture layout
 (tests/golden/sgd_inputs.npz) and on one tensor of 2^20 elements.
@@ -178,6 +190,78 @@ def measure(name, lens, dtype, steps, reps):
     return row
 
 
+class _Loopback:
+    """The aggregator of a single process: the sum is the buffer itself; the world size only
+    sets the divisor (1.0: the gradients keep their magnitude over the timed steps; the kernel
+    divides all the same)."""
+    world_size = 1.0
+
+    def _agg(self, data, op=None, distributed=True):
+        return data
+
+
+def measure_allreduce(name, lens, dtype, master, steps, reps):
+    from chocosgd_amd.tensor_buffer import TensorBuffer
+    n, esz = sum(lens), torch.empty(0, dtype=dtype).element_size()
+    agg = _Loopback()
+    pa, ga, na = model(lens, dtype)
+    sa = collections.defaultdict(dict)
+    mwa = utils.MasterWeights(ga, na) if master else None
+
+    def new_step():
+        utils.allreduce_sgd_step(ga, na, sa, agg, master=mwa)
+
+    pb, gb, nb = model(lens, dtype)
+    sb = collections.defaultdict(dict)
+    mwb = utils.MasterWeights(gb, nb) if master else None
+    grads = [p.grad for p in pb]
+    sizes = [g.size() for g in grads]
+    flat = torch.empty(n, device=DEV)
+
+    def parent_step():
+        codec.params_pack(grads, flat)
+        avg = agg._agg(flat, op="sum") / agg.world_size
+        TensorBuffer.from_flat(avg, sizes).unpack(grads)
+        utils.apply_gradient(gb, sb, master=mwb)
+
+    step_host, step_gpu = median_of(new_step, steps, reps)
+    parent_host, parent_gpu = median_of(parent_step, steps, reps)
+    _, div_gpu = median_of(lambda: flat / agg.world_size, steps, reps)
+    upd = "param_sgd_master_flatgrad_kernel" if master else "param_sgd_flatgrad_kernel"
+    old = "param_sgd_master_kernel" if master else "param_sgd_kernel"
+    bytes_update = n * ((20 + 2 * esz) if master else (4 + 5 * esz))  # with the grad write
+    bytes_parent = n * (esz + 4) + n * 8 + n * (4 + esz) + (n * (2 * esz + 16) if master else n * 5 * esz)
+    k_upd, l_upd = kernel_time(new_step, upd)
+    k_pack, l_pack = kernel_time(new_step, "param_pack_kernel")
+    k_ppack, _ = kernel_time(parent_step, "param_pack_kernel")
+    k_unpack, _ = kernel_time(parent_step, "param_unpack_kernel")
+    k_old, l_old = kernel_time(parent_step, old)
+    row = {"allreduce": name, "tensors": len(lens), "elements": n, "param_dtype": str(dtype).split(".")[-1],
+           "master": master, "steps": steps, "reps": reps,
+           "step_host_us": round(step_host, 1), "step_gpu_us": round(step_gpu, 1),
+           "step_launches": count_launches(new_step), "bytes_update": bytes_update,
+           "bytes_step": bytes_update + n * (esz + 4),
+           "parent_host_us": round(parent_host, 1), "parent_gpu_us": round(parent_gpu, 1),
+           "parent_launches": count_launches(parent_step), "bytes_parent": bytes_parent,
+           "div_gpu_us": round(div_gpu, 2)}
+    if k_upd and k_pack:
+        row.update(kernel_us_update=round(k_upd, 2), kernel_launches_update=l_upd,
+                   kernel_tbps_update=round(bytes_update / k_upd / 1e6, 3), kernel_us_pack=round(k_pack, 2),
+                   kernel_us_step=round(k_upd + k_pack, 2))
+    if k_ppack and k_unpack and k_old:
+        row.update(kernel_us_parent_pack=round(k_ppack, 2), kernel_us_parent_unpack=round(k_unpack, 2),
+                   kernel_us_parent_sgd=round(k_old, 2), kernel_launches_parent_sgd=l_old,
+                   kernel_us_parent=round(k_ppack + k_unpack + k_old + div_gpu, 2))
+    return row
+
+
+def allreduce_layouts():
+    with open(os.path.join(ROOT, "tests", "golden", "layouts.json")) as f:
+        r50 = json.load(f)["resnet50_imagenet"]
+    return [("resnet50_fp32", r50, torch.float32, False), ("resnet50_bf16", r50, torch.bfloat16, False),
+            ("resnet50_bf16_master", r50, torch.bfloat16, True), ("t3000x100_fp32", [100] * 3000, torch.float32, False)]
+
+
 def _differ(a, b):
     a, b = a.float().reshape(-1), b.float().reshape(-1)
     same = (a.view(torch.int32) == b.view(torch.int32)) | (torch.isnan(a) & torch.isnan(b))
@@ -237,13 +321,19 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--rows", choices=["all", "allreduce"], default="all")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "the probe needs a ROCm device"
     rows = []
     for name, lens, dtype in layouts():
-        rows.append(measure(name, lens, dtype, args.steps, args.reps))
+        # the fp32 ResNet-50 row stays in an all-reduce run: its kernel_tbps_sgd is the yardstick
+        if args.rows == "all" or name == "resnet50_fp32":
+            rows.append(measure(name, lens, dtype, args.steps, args.reps))
+            print(json.dumps(rows[-1]), flush=True)
+    for name, lens, dtype, master in allreduce_layouts():
+        rows.append(measure_allreduce(name, lens, dtype, master, args.steps, args.reps))
         print(json.dumps(rows[-1]), flush=True)
-    for row in parity_rows():
+    for row in (parity_rows() if args.rows == "all" else []):
         rows.append(row)
         print(json.dumps(row), flush=True)
     if args.out:
