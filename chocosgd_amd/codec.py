@@ -1052,11 +1052,24 @@ def params_unpack(flat, tensors):
 SGD_F_NESTEROV, SGD_F_FIRST, SGD_F_NOGRAD = 1, 2, 4                    # CHOCO_SGD_F_*
 SGD_MODE_GRAD, SGD_MODE_WRITE_PARAMS, SGD_MODE_WRITE_GRADS = 1, 2, 4   # CHOCO_SGD_MODE_*
 SGD_MODE_ADD_FLAT = 8                                                  # choco_params_sgd_clip only
+SGD_MODE_WRITE_CLIPPED = 16                                            # choco_params_sgd[_master]_gclip only
 
 
 def params_sgd_launches(nseg):
     """Launches one params_sgd of `nseg` tensors takes."""
     return int(lib().choco_params_sgd_launches(int(nseg)))
+
+
+def params_gradnorm_launches(nseg, pinned=False):
+    """Launches one ParamSgdPlan.gradnorm of `nseg` tensors takes (pinned: with total_norm)."""
+    return int(lib().choco_params_gradnorm_launches(int(nseg), 1 if pinned else 0))
+
+
+def common_grad_dtype(dtypes):
+    """The dtype of clip_grad_norm_'s coefficient for gradients of these dtypes: all bfloat16 ->
+    bfloat16, all float16 -> float16, any float32 or any mix (or none) -> float32."""
+    kinds = set(dtypes)
+    return kinds.pop() if len(kinds) == 1 else torch.float32
 
 
 class ParamSgdPlan:
@@ -1089,6 +1102,7 @@ class ParamSgdPlan:
         self.n = sum(self.numels)
         self.seen = [None] * nseg  # the hyperparameter tuple last written, per tensor
         self._norms = self._norm_ws = None  # sqnorm()'s output and workspace, allocated on first use
+        self._gn_out = self._gn_ws = None   # gradnorm()'s
         self._refs = [weakref.ref(p) for p in params]
 
     def holds(self, params):
@@ -1114,7 +1128,55 @@ class ParamSgdPlan:
                                          self._norm_ws.numel(), _stream(self.device)), "choco_params_sqnorm")
         return self._norms
 
-    def run(self, flat=None, grad_mode=False, write=True, norms=None, clip_threshold=None, add_flat=False):
+    def gradnorm(self, max_norm, coef_dtype=None, total_norm=None, norms=None):
+        """One choco_params_gradnorm over the gradient pointers and flags as they stand:
+        torch.nn.utils.clip_grad_norm_'s total L2 norm over every tensor that has a gradient
+        (fp64 accumulation in a fixed order) and its clip coefficient, both left on the device.
+        Returns the plan's own two-element fp32 tensor [total, coefficient], overwritten by the
+        next call: hand it to run(gclip=...) / run_master(gclip=...).
+
+        coef_dtype: the dtype the coefficient is computed in; default: the common dtype of the
+        gradients (common_grad_dtype).  total_norm (a one-element tensor or a float): the total
+        is pinned to it -- no norm pass, one launch.  norms (fp32 device tensor of nseg; not
+        with total_norm) receives the per-tensor norms, sqnorm()'s at zero weight decay."""
+        L = lib()
+        if coef_dtype is None:
+            coef_dtype = common_grad_dtype(dt for dt, fl in zip(self.dtypes, self.flags) if not fl & SGD_F_NOGRAD)
+        cd = PARAM_DTYPES.get(coef_dtype)
+        if cd is None:
+            raise RuntimeError(f"coef_dtype must be float32, bfloat16 or float16, got {coef_dtype}")
+        if self._gn_out is None:
+            self._gn_out = torch.empty(2, dtype=torch.float32, device=self.device)
+        if total_norm is not None:
+            if norms is not None:
+                raise RuntimeError("norms with a pinned total_norm: there is no norm pass to take them from")
+            if not torch.is_tensor(total_norm):
+                total_norm = torch.tensor([float(total_norm)], dtype=torch.float32)
+            if total_norm.numel() != 1:
+                raise RuntimeError("total_norm must hold one element")
+            total_norm = total_norm.detach().reshape(1).to(device=self.device, dtype=torch.float32)
+        elif self._gn_ws is None:
+            self._gn_ws = torch.empty(int(L.choco_params_gradnorm_workspace_size(self.nseg, self.n)),
+                                      dtype=torch.uint8, device=self.device)
+        if norms is not None:
+            _require(norms, torch.float32, "norms")
+            if norms.device != self.device or norms.numel() != self.nseg:
+                raise RuntimeError(f"norms must hold {self.nseg} elements on {self.device}")
+        ws = None if total_norm is not None else self._gn_ws
+        _lib.check(L.choco_params_gradnorm(self.grad_ptrs, self.lens, self.dts, self.flags, self.nseg, self.n,
+                                           float(max_norm), cd, _ptr(total_norm), _ptr(self._gn_out), _ptr(norms),
+                                           _ptr(ws), 0 if ws is None else ws.numel(), _stream(self.device)),
+                   "choco_params_gradnorm")
+        return self._gn_out
+
+    def _coef_ptr(self, gclip):
+        _require(gclip, torch.float32, "gclip")
+        if gclip.device != self.device or gclip.numel() != 2:
+            raise RuntimeError(f"gclip must be gradnorm()'s two-element tensor on {self.device}")
+        return gclip.data_ptr() + 4
+
+    def run(self, flat=None, grad_mode=False, write=True, norms=None, clip_threshold=None, add_flat=False,
+            gclip=None, write_clipped=False):
         """One choco_params_sgd over the tables as they stand.  apply mode (grad_mode False):
         write -> the params are updated; grad mode: write -> d_p goes into the grads' storage.
         flat (fp32, n elements, or None) receives the new params / d_p in the same pass.
@@ -1122,13 +1184,33 @@ class ParamSgdPlan:
         norms (fp32 device tensor of nseg, e.g. sqnorm()'s) with clip_threshold (a Python float,
         clip_grad_val / sqrt(n_nodes)): DGC's per-tensor clipping between the weight decay and
         the momentum; add_flat (grad mode): flat += d_p instead of flat = d_p.  Either one takes
-        choco_params_sgd_clip; the defaults are choco_params_sgd, as before."""
+        choco_params_sgd_clip; the defaults are choco_params_sgd, as before.
+
+        gclip (gradnorm()'s tensor): choco_params_sgd_gclip -- every gradient is scaled by the
+        global-norm clip coefficient as it is loaded; write_clipped (apply mode): the clipped
+        gradient is also stored into the grads' storage.  Not together with norms /
+        clip_threshold / add_flat."""
         if flat is not None:
             _require(flat, torch.float32, "flat")
             if flat.device != self.device or flat.numel() != self.n:
                 raise RuntimeError(f"flat must hold {self.n} elements on {self.device}")
         mode = (SGD_MODE_GRAD | (SGD_MODE_WRITE_GRADS if write else 0)) if grad_mode else \
             (SGD_MODE_WRITE_PARAMS if write else 0)
+        if gclip is None and write_clipped:
+            raise RuntimeError("write_clipped needs gclip (gradnorm()'s tensor)")
+        if gclip is not None:
+            if norms is not None or clip_threshold is not None or add_flat:
+                raise RuntimeError("gclip (global-norm clipping) does not combine with norms / clip_threshold / "
+                                   "add_flat (DGC's per-tensor clipping)")
+            if write_clipped and grad_mode:
+                raise RuntimeError("write_clipped is for apply mode: grad mode writes d_p into the grads")
+            _lib.check(lib().choco_params_sgd_gclip(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts,
+                                                    self.lr, self.weight_decay, self.momentum, self.dampening,
+                                                    self.flags, self.nseg, _ptr(flat), self.n,
+                                                    mode | (SGD_MODE_WRITE_CLIPPED if write_clipped else 0),
+                                                    self._coef_ptr(gclip), _stream(self.device)),
+                       "choco_params_sgd_gclip")
+            return
         if clip_threshold is not None and norms is None:
             raise RuntimeError("clip_threshold needs norms (sqnorm()'s, or recorded ones): nothing would be clipped")
         if norms is not None or add_flat:
@@ -1155,14 +1237,28 @@ class ParamSgdPlan:
         return (t.dtype == torch.float32 and t.device == self.device and t.numel() == self.numels[i]
                 and t.is_contiguous())
 
-    def run_master(self, master, write=True):
+    def run_master(self, master, write=True, gclip=None, write_clipped=False):
         """One choco_params_sgd_master over the tables as they stand: the update runs on
         `master` (the persistent flat fp32 copy of the parameters, n elements) in place, with
         fp32 momentum buffers behind `buf_ptrs` and the gradients in their parameters' dtype;
-        write -> the parameters receive the new master values narrowed to their dtype."""
+        write -> the parameters receive the new master values narrowed to their dtype.
+
+        gclip (gradnorm(coef_dtype=torch.float32)'s tensor): choco_params_sgd_master_gclip --
+        g = c * g in fp32, not narrowed, in front of the update; write_clipped: that product,
+        narrowed, is stored into the grads' storage."""
         _require(master, torch.float32, "master")
         if master.device != self.device or master.numel() != self.n:
             raise RuntimeError(f"master must hold {self.n} elements on {self.device}")
+        if gclip is None and write_clipped:
+            raise RuntimeError("write_clipped needs gclip (gradnorm()'s tensor)")
+        if gclip is not None:
+            mode = (SGD_MODE_WRITE_PARAMS if write else 0) | (SGD_MODE_WRITE_CLIPPED if write_clipped else 0)
+            _lib.check(lib().choco_params_sgd_master_gclip(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens,
+                                                           self.dts, self.lr, self.weight_decay, self.momentum,
+                                                           self.dampening, self.flags, self.nseg, _ptr(master), self.n,
+                                                           mode, self._coef_ptr(gclip), _stream(self.device)),
+                       "choco_params_sgd_master_gclip")
+            return
         _lib.check(lib().choco_params_sgd_master(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts,
                                                  self.lr, self.weight_decay, self.momentum, self.dampening,
                                                  self.flags, self.nseg, _ptr(master), self.n,

@@ -68,6 +68,8 @@ struct SgdTensor {
   bool grad_mode, pack_only;
   bool clip, add_flat;     // choco_params_sgd_clip: d = c * d after the weight decay; flat += out
   float c;                 // the tensor's clip coefficient
+  bool wr_c;               // the gclip kernels: the clipped gradient goes back into g (WRITE_CLIPPED)
+  float gc;                // ... and the global clip coefficient, *coef
 };
 
 // The value as the storage dtype holds it.  v is the fp32 result of its line and is narrowed
@@ -105,13 +107,18 @@ CHOCO_DEV void sgd_math(const SgdTensor& t, float p, float g, float b, float& bu
   out = t.grad_mode ? d : rnd<DT>(fmaf(t.nlr, d, p));
 }
 
-// flat index i, element j of the tensor
-template <int DT>
+// flat index i, element j of the tensor.  GC (the gclip kernel's instantiations): the gradient
+// is clipped as it is loaded, g = rnd(gc * g), one fp32 multiply narrowed to the tensor's dtype.
+template <int DT, bool GC = false>
 CHOCO_DEV void sgd_elem(const SgdTensor& t, int64_t i, int64_t j) {
   const float p = t.rd_p ? ld1<DT>(t.p, j) : 0.0f;
-  const float g = t.rd_g ? ld1<DT>(t.g, j) : 0.0f;
+  float g = t.rd_g ? ld1<DT>(t.g, j) : 0.0f;
   const float b = t.rd_b ? ld1<DT>(t.buf, j) : 0.0f;
   float nb = 0.0f, out;
+  if (GC) {
+    g = rnd<DT>(__fmul_rn(t.gc, g));
+    if (t.wr_c) st1<DT>(t.g, j, g);
+  }
   sgd_math<DT>(t, p, g, b, nb, out);
   if (t.wr_b) st1<DT>(t.buf, j, nb);
   if (t.wr_p) st1<DT>(t.p, j, out);
@@ -121,11 +128,11 @@ CHOCO_DEV void sgd_elem(const SgdTensor& t, int64_t i, int64_t j) {
 
 // Flat elements [a, b) of a tensor at flat offset o0, a < b inside this workgroup's tile.
 // vec: every side the update touches is 16-byte aligned at every whole group's start.
-template <int DT>
+template <int DT, bool GC = false>
 CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, bool vec) {
   const int tid = threadIdx.x;
   if (!vec) {
-    for (int64_t i = a + tid; i < b; i += kPbThreads) sgd_elem<DT>(t, i, i - o0);
+    for (int64_t i = a + tid; i < b; i += kPbThreads) sgd_elem<DT, GC>(t, i, i - o0);
     return;
   }
   const int64_t g0 = a >> 3, g1 = (b - 1) >> 3;  // groups at absolute flat offsets, inclusive
@@ -153,6 +160,11 @@ CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, bo
         if (t.rd_p) widen8<DT>(rp[u], p);
         if (t.rd_g) widen8<DT>(rg[u], g);
         if (t.rd_b) widen8<DT>(rb[u], bi);
+        if (GC) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) g[k] = rnd<DT>(__fmul_rn(t.gc, g[k]));
+          if (t.wr_c) st8<DT>(t.g, e - o0, g);
+        }
 #pragma unroll
         for (int k = 0; k < 8; ++k) sgd_math<DT>(t, p[k], g[k], bi[k], nb[k], out[k]);
         if (t.wr_b) st8<DT>(t.buf, e - o0, nb);
@@ -168,7 +180,7 @@ CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, bo
       } else {
         // a group cut by the tensor's start or end (or past the span): its own elements only
         const int64_t ea = e > a ? e : a, eb = e + kPbGroup < b ? e + kPbGroup : b;
-        for (int64_t i = ea; i < eb; ++i) sgd_elem<DT>(t, i, i - o0);
+        for (int64_t i = ea; i < eb; ++i) sgd_elem<DT, GC>(t, i, i - o0);
       }
     }
   }
@@ -176,7 +188,11 @@ CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, bo
 
 // EXT: the instantiation choco_params_sgd_clip launches (clip coefficients from norms[s] when
 // norms != nullptr, ADD_FLAT); choco_params_sgd's own has neither compiled in.
-template <bool EXT>
+// GC: the instantiation choco_params_sgd_gclip launches ("param_sgd_gclip_kernel"): `norms` is
+// then coef, ONE float, the global-norm clip coefficient every gradient is scaled by on the load
+// the update does anyway, and thr is not used; the multiply is compiled into neither of the
+// other two, whose argument list this is.
+template <bool EXT, bool GC = false>
 __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb, float* flat, int64_t tile0,
                                                                int32_t flat16, int32_t mode, const float* norms,
                                                                float thr) {
@@ -185,6 +201,7 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
   const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
   if (s0 < 0) return;
   const bool grad_mode = (mode & CHOCO_SGD_MODE_GRAD) != 0;
+  const float gc = GC ? *norms : 1.0f;  // a uniform load
   for (int s = s0; s < nt; ++s) {
     const int64_t o0 = tb.off[s];
     if (o0 >= thi) break;
@@ -216,6 +233,8 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
     t.wr_b = !t.pack_only && t.has_mom;
     t.wr_p = !t.pack_only && !grad_mode && (mode & CHOCO_SGD_MODE_WRITE_PARAMS) != 0;
     t.wr_g = !t.pack_only && grad_mode && (mode & CHOCO_SGD_MODE_WRITE_GRADS) != 0;
+    t.wr_c = GC && !t.pack_only && (mode & CHOCO_SGD_MODE_WRITE_CLIPPED) != 0;  // apply mode (the host's check)
+    t.gc = gc;
     // flat + 4 e is 16-byte aligned at every group start e (a multiple of 8) when flat is; a
     // tensor's side q + esz (e - o0) is when q - esz o0 is, esz e being a multiple of 16
     const uintptr_t esz = dt == CHOCO_DT_F32 ? 4u : 2u, back = esz * (uintptr_t)o0;
@@ -224,9 +243,9 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
     if (t.rd_g || t.wr_g) mis |= reinterpret_cast<uintptr_t>(t.g) - back;
     if (t.rd_b || t.wr_b) mis |= reinterpret_cast<uintptr_t>(t.buf) - back;
     const bool vec = (flat == nullptr || flat16) && (mis & 15u) == 0;
-    if (dt == CHOCO_DT_F32) sgd_span<CHOCO_DT_F32>(t, o0, a, b, vec);
-    else if (dt == CHOCO_DT_BF16) sgd_span<CHOCO_DT_BF16>(t, o0, a, b, vec);
-    else sgd_span<CHOCO_DT_F16>(t, o0, a, b, vec);
+    if (dt == CHOCO_DT_F32) sgd_span<CHOCO_DT_F32, GC>(t, o0, a, b, vec);
+    else if (dt == CHOCO_DT_BF16) sgd_span<CHOCO_DT_BF16, GC>(t, o0, a, b, vec);
+    else sgd_span<CHOCO_DT_F16, GC>(t, o0, a, b, vec);
   }
 }
 
@@ -243,12 +262,19 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
 // at 4 bytes.
 
 // flat index i, element j of the tensor
-template <int DT>
+// GC (the gclip kernel's instantiations): g = gc * g in fp32, not narrowed, in front of the
+// lines; WRITE_CLIPPED stores that product narrowed to the gradient's dtype.
+template <int DT, bool GC = false>
 CHOCO_DEV void master_elem(const SgdTensor& t, float* master, int64_t i, int64_t j) {
   const float p = master[i];
-  const float g = ld1<DT>(t.g, j);
+  float g = ld1<DT>(t.g, j);
   const float b = t.rd_b ? ld1<CHOCO_DT_F32>(t.buf, j) : 0.0f;
   float nb = 0.0f, out;
+  if (GC) {
+    g = __fmul_rn(t.gc, g);
+    if (DT != CHOCO_DT_F32) asm("" : "+v"(g));  // the narrowing below starts from the rounded fp32 (see rnd)
+    if (t.wr_c) st1<DT>(t.g, j, g);
+  }
   sgd_math<CHOCO_DT_F32>(t, p, g, b, nb, out);
   if (DT != CHOCO_DT_F32) asm("" : "+v"(out));  // the narrowing below starts from the rounded fp32 (see rnd)
   if (t.wr_b) st1<CHOCO_DT_F32>(t.buf, j, nb);
@@ -258,11 +284,11 @@ CHOCO_DEV void master_elem(const SgdTensor& t, float* master, int64_t i, int64_t
 
 // Flat elements [a, b) of a tensor at flat offset o0, a < b inside this workgroup's tile; one
 // 8-element group in flight per thread, every load issued before the first store.
-template <int DT>
+template <int DT, bool GC = false>
 CHOCO_DEV void master_span(const SgdTensor& t, float* master, int64_t o0, int64_t a, int64_t b, bool vec) {
   const int tid = threadIdx.x;
   if (!vec) {
-    for (int64_t i = a + tid; i < b; i += kPbThreads) master_elem<DT>(t, master, i, i - o0);
+    for (int64_t i = a + tid; i < b; i += kPbThreads) master_elem<DT, GC>(t, master, i, i - o0);
     return;
   }
   const int64_t g0 = a >> 3, g1 = (b - 1) >> 3;  // groups at absolute flat offsets, inclusive
@@ -278,6 +304,14 @@ CHOCO_DEV void master_span(const SgdTensor& t, float* master, int64_t o0, int64_
       widen8<CHOCO_DT_F32>(rp, p);
       widen8<DT>(rg, g);
       if (t.rd_b) widen8<CHOCO_DT_F32>(rb, bi);
+      if (GC) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          g[k] = __fmul_rn(t.gc, g[k]);
+          if (DT != CHOCO_DT_F32) asm("" : "+v"(g[k]));
+        }
+        if (t.wr_c) st8<DT>(t.g, e - o0, g);
+      }
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         sgd_math<CHOCO_DT_F32>(t, p[k], g[k], bi[k], nb[k], out[k]);
@@ -289,17 +323,23 @@ CHOCO_DEV void master_span(const SgdTensor& t, float* master, int64_t o0, int64_
     } else {
       // a group cut by the tensor's start or end (or past the span): its own elements only
       const int64_t ea = e > a ? e : a, eb = e + kPbGroup < b ? e + kPbGroup : b;
-      for (int64_t i = ea; i < eb; ++i) master_elem<DT>(t, master, i, i - o0);
+      for (int64_t i = ea; i < eb; ++i) master_elem<DT, GC>(t, master, i, i - o0);
     }
   }
 }
 
+// COEF: no argument at all (param_sgd_master_kernel, the argument list it always had), or one
+// `const float*`, the global-norm clip coefficient ("param_sgd_master_gclip_kernel").
+template <typename... COEF>
 __global__ __launch_bounds__(kPbThreads) void param_sgd_master_kernel(const SgdTable tb, float* master, int64_t tile0,
-                                                                      int32_t master16, int32_t mode) {
+                                                                      int32_t master16, int32_t mode, COEF... coef) {
+  constexpr bool GC = sizeof...(COEF) != 0;
   const int nt = tb.nt;
   int64_t tlo, thi;
   const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
   if (s0 < 0) return;
+  float gc = 1.0f;
+  ((gc = *coef), ...);  // a uniform load
   for (int s = s0; s < nt; ++s) {
     const int64_t o0 = tb.off[s];
     if (o0 >= thi) break;
@@ -323,6 +363,8 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_master_kernel(const SgdT
     t.wr_b = t.has_mom;
     t.wr_p = (mode & CHOCO_SGD_MODE_WRITE_PARAMS) != 0;
     t.wr_g = false;
+    t.wr_c = GC && (mode & CHOCO_SGD_MODE_WRITE_CLIPPED) != 0;
+    t.gc = gc;
     // master + 4 e is 16-byte aligned at every group start e (a multiple of 8) when master is; a
     // side q + esz (e - o0) is when q - esz o0 is -- esz the tensor's for g and p, 4 for buf
     const uintptr_t esz = dt == CHOCO_DT_F32 ? 4u : 2u, o = (uintptr_t)o0;
@@ -330,11 +372,12 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_master_kernel(const SgdT
     if (t.wr_p) mis |= reinterpret_cast<uintptr_t>(t.p) - esz * o;
     if (t.wr_b) mis |= reinterpret_cast<uintptr_t>(t.buf) - 4u * o;
     const bool vec = master16 && (mis & 15u) == 0;
-    if (dt == CHOCO_DT_F32) master_span<CHOCO_DT_F32>(t, master, o0, a, b, vec);
-    else if (dt == CHOCO_DT_BF16) master_span<CHOCO_DT_BF16>(t, master, o0, a, b, vec);
-    else master_span<CHOCO_DT_F16>(t, master, o0, a, b, vec);
+    if (dt == CHOCO_DT_F32) master_span<CHOCO_DT_F32, GC>(t, master, o0, a, b, vec);
+    else if (dt == CHOCO_DT_BF16) master_span<CHOCO_DT_BF16, GC>(t, master, o0, a, b, vec);
+    else master_span<CHOCO_DT_F16, GC>(t, master, o0, a, b, vec);
   }
 }
+
 
 // ------------------------------------------------------------------ all-reduce SGD: the flat summed gradient
 // The centralized branch of SGD.step (dl_code/pcode/optim/sgd.py:68-92) after the all-reduce
@@ -503,6 +546,8 @@ struct SgdArgs {
   const float* gsum;     // choco_params_sgd[_master]_flatgrad: the all-reduced sum, n fp32 (else nullptr)
   double divisor;        // ... and what it is divided by
   bool flatgrad;         // one of those two entry points
+  bool gclip;            // choco_params_sgd[_master]_gclip: the WRITE_CLIPPED bit and the argument below
+  const float* coef;     // device, the global-norm clip coefficient (choco_params_gradnorm's out + 1)
 };
 
 static bool elem_aligned(const void* p, uintptr_t esz) { return (reinterpret_cast<uintptr_t>(p) & (esz - 1)) == 0; }
@@ -559,15 +604,23 @@ static int sgd_check(const SgdArgs& a) {
                 "null table argument");
   CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
   CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
+  const int32_t clipped = a.gclip ? CHOCO_SGD_MODE_WRITE_CLIPPED : 0;
   if (a.master) {
-    CHOCO_REQUIRE((a.mode & ~CHOCO_SGD_MODE_WRITE_PARAMS) == 0,
-                  "the master update runs in apply mode, optionally | WRITE_PARAMS: mode bits 0x%x", (unsigned)a.mode);
+    CHOCO_REQUIRE((a.mode & ~(CHOCO_SGD_MODE_WRITE_PARAMS | clipped)) == 0,
+                  "the master update runs in apply mode, optionally | WRITE_PARAMS%s: mode bits 0x%x",
+                  a.gclip ? " | WRITE_CLIPPED" : "", (unsigned)a.mode);
     CHOCO_REQUIRE(a.flat, "master is null");
   }
   constexpr int32_t kModes = CHOCO_SGD_MODE_GRAD | CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS;
-  CHOCO_REQUIRE((a.mode & ~(kModes | (a.ext ? CHOCO_SGD_MODE_ADD_FLAT : 0))) == 0, "unknown mode bits 0x%x",
+  if (a.gclip) CHOCO_REQUIRE(!(a.mode & CHOCO_SGD_MODE_ADD_FLAT), "ADD_FLAT has no global-norm clipped variant");
+  CHOCO_REQUIRE((a.mode & ~(kModes | (a.ext ? CHOCO_SGD_MODE_ADD_FLAT : 0) | clipped)) == 0, "unknown mode bits 0x%x",
                 (unsigned)a.mode);
   const bool grad_mode = (a.mode & CHOCO_SGD_MODE_GRAD) != 0;
+  if (a.gclip) {
+    CHOCO_REQUIRE(a.coef && aligned4(a.coef), "coef must be a 4-byte aligned device pointer");
+    CHOCO_REQUIRE(!(grad_mode && (a.mode & CHOCO_SGD_MODE_WRITE_CLIPPED)),
+                  "WRITE_CLIPPED is for apply mode: grad mode writes d_p into the grads");
+  }
   if (a.mode & CHOCO_SGD_MODE_ADD_FLAT)
     CHOCO_REQUIRE(grad_mode && a.flat, "ADD_FLAT needs grad mode and a flat buffer");
   if (a.norms) {
@@ -578,7 +631,7 @@ static int sgd_check(const SgdArgs& a) {
   }
   CHOCO_REQUIRE(!(grad_mode && (a.mode & CHOCO_SGD_MODE_WRITE_PARAMS)), "grad mode does not write the params");
   CHOCO_REQUIRE(!(!grad_mode && (a.mode & CHOCO_SGD_MODE_WRITE_GRADS)), "apply mode does not write the grads");
-  CHOCO_REQUIRE(a.flat || (a.mode & (CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS)),
+  CHOCO_REQUIRE(a.flat || (a.mode & (CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS | clipped)),
                 "nothing to write: flat is null and the mode writes neither params nor grads");
   CHOCO_REQUIRE(aligned4(a.flat), "the %s buffer must be 4-byte aligned", a.master ? "master" : "flat");
   int64_t sum = 0;
@@ -656,8 +709,16 @@ static int sgd_run(const SgdArgs& a, hipStream_t st) {
       CHOCO_TRY(CHOCO_LAUNCH("param_sgd_flatgrad_kernel", "param_sgd_flatgrad_kernel", param_sgd_flatgrad_kernel<false>,
                              dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.gsum, (float*)nullptr, tile0,
                              (float)a.divisor, al16, a.mode));
+    else if (a.gclip && a.master)
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_master_gclip_kernel", "param_sgd_master_gclip_kernel",
+                             param_sgd_master_kernel<const float*>, dim3((unsigned)tiles), dim3(kPbThreads), st, tb,
+                             a.flat, tile0, flat16, a.mode, a.coef));
+    else if (a.gclip)
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_gclip_kernel", "param_sgd_gclip_kernel", param_sgd_kernel<false, true>,
+                             dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.flat, tile0, flat16, a.mode, a.coef,
+                             0.0f));
     else if (a.master)
-      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_master_kernel", "param_sgd_master_kernel", param_sgd_master_kernel,
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_master_kernel", "param_sgd_master_kernel", param_sgd_master_kernel<>,
                              dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.flat, tile0, flat16, a.mode));
     else if (a.ext)
       CHOCO_TRY(CHOCO_LAUNCH("param_sgd_kernel", "param_sgd_kernel<clip>", param_sgd_kernel<true>,
@@ -847,6 +908,7 @@ __global__ __launch_bounds__(kPbThreads) void param_sqnorm_kernel(const NormTabl
 // sqrt in fp64, rounded to fp32 and, for a 16-bit tensor, again to its dtype (grad.norm()
 // returns the gradient's dtype)
 constexpr int kNormFinishWaves = kPbThreads / 64;
+
 __global__ __launch_bounds__(kPbThreads) void param_sqnorm_finish_kernel(const double* slots, const int32_t* meta,
                                                                          float* norms, int32_t nseg) {
   const int lane = threadIdx.x & 63;
@@ -865,6 +927,94 @@ __global__ __launch_bounds__(kPbThreads) void param_sqnorm_finish_kernel(const d
   if (dt == CHOCO_DT_BF16) r = rnd<CHOCO_DT_BF16>(r);
   else if (dt == CHOCO_DT_F16) r = rnd<CHOCO_DT_F16>(r);
   if (lane == 0) norms[s] = r;
+}
+
+// ------------------------------------------------------------------ the global gradient norm and its clip coefficient
+// torch.nn.utils.clip_grad_norm_(parameters, max_norm) (distributed_running_nlp.py:96) up to the
+// coefficient, on the device (choco_params_gradnorm): after param_sqnorm_kernel on the raw
+// gradients, ONE workgroup adds every tensor's partials as the finish kernel above does (its
+// waves take the tensors in turn; sums[s] keeps the fp64 sum, norms[s] the per-tensor norm), then
+// its first wave adds sums[0 .. nseg) in ascending order, takes the square root in fp64 and
+// evaluates, with CD = the coefficient's dtype,
+//     total = rnd_CD((float)sqrt(sum))      or rnd_CD(*total_in): the pinned total, no norm pass
+//     t = rnd_CD(total + 1e-6f);  r = rnd_CD(1.0f / t);  c = rnd_CD(r * max_norm);  c = c > 1 ? 1 : c
+// -- torch's `max_norm / (total_norm + 1e-6)` is total.reciprocal() * max_norm, clamped with
+// max = 1.0: a NaN stays NaN, an inf total gives 0.  out[0] = total, out[1] = c.  No atomics: the
+// order of every addition is fixed.  One workgroup means latency, not bandwidth, is the cost: the
+// slots, the meta words and the per-tensor sums of a layout that fits (ResNet-50: 3281 slots) are
+// staged in LDS by one coalesced pass, and a lane's value reaches the sum through v_readlane
+// (the lane index is uniform), not through the LDS crossbar.  A larger layout reads the workspace
+// in place, with the same additions in the same order.
+
+// v[0] + v[1] + ... + v[cnt - 1], added in that order by one wave as the finish kernel above adds a
+// tensor's slots (cnt uniform); every lane gets the sum
+CHOCO_DEV double wave_ordered_sum(const double* v, int32_t cnt, int lane) {
+  double acc = 0.0;
+  for (int32_t base = 0; base < cnt; base += 64) {
+    const int32_t i = base + lane;
+    const double x = i < cnt ? v[i] : 0.0;
+    const int hi = __double2hiint(x), lo = __double2loint(x);
+    const int32_t m = cnt - base < 64 ? cnt - base : 64;
+    for (int32_t l = 0; l < m; ++l)
+      acc += __hiloint2double(__builtin_amdgcn_readlane(hi, l), __builtin_amdgcn_readlane(lo, l));
+  }
+  return acc;
+}
+
+// v as dtype dt (a CHOCO_DT_* code) holds it
+CHOCO_DEV float rnd_as(float v, int dt) {
+  if (dt == CHOCO_DT_BF16) return rnd<CHOCO_DT_BF16>(v);
+  if (dt == CHOCO_DT_F16) return rnd<CHOCO_DT_F16>(v);
+  return v;
+}
+
+constexpr int kTotalThreads = 1024;
+constexpr int kTotalStageSlots = 5120;  // 40 KB of fp64 slots, 8 KB of meta words and 8 KB of sums in LDS
+constexpr int kTotalStageSegs = 1024;
+__global__ __launch_bounds__(kTotalThreads) void param_gradnorm_total_kernel(const double* slots, int32_t nslots,
+                                                                             const int32_t* meta, double* sums,
+                                                                             float* norms, int32_t nseg,
+                                                                             const float* total_in, float max_norm,
+                                                                             int32_t cd, float* out) {
+  __shared__ double s_slots[kTotalStageSlots];
+  __shared__ int32_t s_meta[2 * kTotalStageSegs];
+  __shared__ double s_sums[kTotalStageSegs];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  float total;
+  if (total_in != nullptr) {
+    total = *total_in;
+  } else {
+    if (nslots <= kTotalStageSlots && nseg <= kTotalStageSegs) {
+      // slots no (tile, tensor) pair wrote hold whatever the workspace held: moved, never added
+      for (int32_t i = tid; i < nslots; i += kTotalThreads) s_slots[i] = slots[i];
+      for (int32_t i = tid; i < 2 * nseg; i += kTotalThreads) s_meta[i] = meta[i];
+      __syncthreads();
+      slots = s_slots;
+      meta = s_meta;
+      sums = s_sums;
+    }
+    for (int32_t s = wave; s < nseg; s += kTotalThreads / 64) {
+      const int32_t slot0 = __builtin_amdgcn_readfirstlane(meta[2 * s]);
+      const int32_t w = __builtin_amdgcn_readfirstlane(meta[2 * s + 1]);
+      const double acc = wave_ordered_sum(slots + slot0, w & 0xffffff, lane);
+      if (lane == 0) {
+        sums[s] = acc;
+        if (norms != nullptr) norms[s] = rnd_as((float)sqrt(acc), w >> 24);
+      }
+    }
+    __syncthreads();  // sums[] of every wave, written above, is read by the first one
+    if (wave != 0) return;
+    total = (float)sqrt(wave_ordered_sum(sums, nseg, lane));
+  }
+  if (tid != 0) return;
+  total = rnd_as(total, cd);
+  const float t = rnd_as(__fadd_rn(total, 1e-6f), cd);
+  const float r = rnd_as(__fdiv_rn(1.0f, t), cd);
+  float c = rnd_as(__fmul_rn(r, max_norm), cd);
+  c = c > 1.0f ? 1.0f : c;
+  out[0] = total;
+  out[1] = c;
 }
 
 static int norm_launches(int32_t nseg) { return nseg <= 0 ? 0 : (nseg + kNormCap - 1) / kNormCap + 1; }
@@ -918,11 +1068,8 @@ static int norm_check(const NormArgs& a) {
   return CHOCO_OK;
 }
 
-static int norm_run(const NormArgs& a, hipStream_t st) {
-  const int rc = norm_check(a);
-  if (rc) return rc;
-  double* slots = reinterpret_cast<double*>(a.ws);
-  int32_t* meta = reinterpret_cast<int32_t*>(slots + norm_slots(a.nseg, a.n));
+// the norm pass: one param_sqnorm_kernel launch per chunk (a.params / a.wd null: raw gradients)
+static int norm_pass(const NormArgs& a, double* slots, int32_t* meta, hipStream_t st) {
   NormTable tb;
   int64_t base = 0;
   for (int32_t s0 = 0; s0 < a.nseg; s0 += kNormCap) {
@@ -933,12 +1080,12 @@ static int norm_run(const NormArgs& a, hipStream_t st) {
       const bool in = i < nt;
       const int32_t s = s0 + i;
       const bool upd = in && !(a.flags[s] & CHOCO_SGD_F_NOGRAD);
-      tb.p[i] = upd ? a.params[s] : nullptr;
+      tb.p[i] = upd && a.params ? a.params[s] : nullptr;
       tb.g[i] = upd ? a.grads[s] : nullptr;
-      tb.wd[i] = upd ? (float)a.wd[s] : 0.0f;
+      tb.wd[i] = upd && a.wd ? (float)a.wd[s] : 0.0f;
       tb.dt[i] = in ? (uint8_t)a.dtypes[s] : (uint8_t)0;
       uint32_t fl = in ? (uint32_t)(a.flags[s] & CHOCO_SGD_F_NOGRAD) : 0u;
-      if (upd && a.wd[s] != 0.0) fl |= kSgdHasWd;
+      if (upd && a.wd && a.wd[s] != 0.0) fl |= kSgdHasWd;
       tb.fl[i] = (uint8_t)fl;
       base += in ? a.lens[s] : 0;
       tb.off[i + 1] = base;
@@ -948,10 +1095,104 @@ static int norm_run(const NormArgs& a, hipStream_t st) {
     CHOCO_TRY(CHOCO_LAUNCH("param_sqnorm_kernel", "param_sqnorm_kernel", param_sqnorm_kernel, dim3((unsigned)tiles),
                            dim3(kPbThreads), st, tb, slots, meta + 2 * (size_t)s0, tile0, s0));
   }
+  return CHOCO_OK;
+}
+
+static int norm_run(const NormArgs& a, hipStream_t st) {
+  const int rc = norm_check(a);
+  if (rc) return rc;
+  double* slots = reinterpret_cast<double*>(a.ws);
+  int32_t* meta = reinterpret_cast<int32_t*>(slots + norm_slots(a.nseg, a.n));
+  CHOCO_TRY(norm_pass(a, slots, meta, st));
   const unsigned blocks = (unsigned)((a.nseg + kNormFinishWaves - 1) / kNormFinishWaves);
   CHOCO_TRY(CHOCO_LAUNCH("param_sqnorm_finish_kernel", "param_sqnorm_finish_kernel", param_sqnorm_finish_kernel,
                          dim3(blocks), dim3(kPbThreads), st, (const double*)slots, (const int32_t*)meta, a.norms,
                          a.nseg));
+  return CHOCO_OK;
+}
+
+// choco_params_gradnorm: the norm pass and param_gradnorm_total_kernel, or that launch alone from
+// a pinned total.  Workspace: the sqnorm slots, one fp64 sum per tensor, the meta words.
+static int gradnorm_launches(int32_t nseg, int32_t pinned) {
+  return nseg <= 0 ? 0 : pinned ? 1 : (nseg + kNormCap - 1) / kNormCap + 1;
+}
+static size_t gradnorm_ws_bytes(int32_t nseg, int64_t n) {
+  if (nseg <= 0 || n < 0) return 0;
+  return align_up((norm_slots(nseg, n) + (size_t)nseg) * sizeof(double) + (size_t)nseg * 2 * sizeof(int32_t), 256);
+}
+
+struct GradnormArgs {
+  const void* const* grads;
+  const int64_t* lens;
+  const int32_t* dtypes;
+  const int32_t* flags;
+  int32_t nseg;
+  int64_t n;
+  double max_norm;
+  int32_t coef_dtype;
+  const float* total_in;
+  float* out;
+  float* norms;
+  void* ws;
+  size_t ws_bytes;
+};
+
+static int gradnorm_check(const GradnormArgs& a) {
+  CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
+  CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
+  // tested as the kernel uses it: the fp32 value
+  CHOCO_REQUIRE(a.max_norm >= 0.0 && a.max_norm <= 3.4028234663852886e38,
+                "max_norm must be >= 0 and finite as an fp32 value, got %g", a.max_norm);
+  CHOCO_REQUIRE(a.coef_dtype >= CHOCO_DT_F32 && a.coef_dtype <= CHOCO_DT_F16, "unknown coef_dtype code %d",
+                (int)a.coef_dtype);
+  CHOCO_REQUIRE(a.out && aligned4(a.out), "out must be a 4-byte aligned device pointer");
+  CHOCO_REQUIRE(aligned4(a.norms), "norms must be 4-byte aligned");
+  if (a.total_in) {  // parity mode: nothing of the layout is read
+    CHOCO_REQUIRE(aligned4(a.total_in), "total_in must be 4-byte aligned");
+    CHOCO_REQUIRE(!a.norms, "norms with a pinned total: there is no norm pass to take them from");
+    return CHOCO_OK;
+  }
+  CHOCO_REQUIRE(a.grads && a.lens && a.dtypes && a.flags, "null table argument");
+  CHOCO_REQUIRE(a.ws && (reinterpret_cast<uintptr_t>(a.ws) & 7u) == 0, "the workspace must be 8-byte aligned");
+  if (a.ws_bytes < gradnorm_ws_bytes(a.nseg, a.n))
+    return fail(CHOCO_ERR_WORKSPACE, "workspace too small: %zu bytes, need %zu", a.ws_bytes,
+                gradnorm_ws_bytes(a.nseg, a.n));
+  int64_t sum = 0;
+  for (int32_t s = 0; s < a.nseg; ++s) {
+    const int i = (int)s;
+    CHOCO_REQUIRE(a.lens[s] >= 0, "tensor %d: negative length", i);
+    CHOCO_REQUIRE(a.dtypes[s] >= CHOCO_DT_F32 && a.dtypes[s] <= CHOCO_DT_F16, "tensor %d: unknown dtype code %d", i,
+                  (int)a.dtypes[s]);
+    CHOCO_REQUIRE(a.lens[s] <= a.n - sum, "the lengths add up to more than n = %lld", (long long)a.n);
+    sum += a.lens[s];
+    constexpr int32_t kFlags = CHOCO_SGD_F_NESTEROV | CHOCO_SGD_F_FIRST | CHOCO_SGD_F_NOGRAD;
+    CHOCO_REQUIRE((a.flags[s] & ~kFlags) == 0, "tensor %d: unknown flag bits 0x%x", i, (unsigned)a.flags[s]);
+    CHOCO_REQUIRE(elem_aligned(a.grads[s], a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u),
+                  "tensor %d: pointer not aligned to its element size", i);
+    if (a.lens[s] == 0 || (a.flags[s] & CHOCO_SGD_F_NOGRAD)) continue;
+    CHOCO_REQUIRE(a.grads[s], "tensor %d: null grad pointer without the no-grad flag", i);
+  }
+  CHOCO_REQUIRE(sum == a.n, "the lengths add up to %lld, n is %lld", (long long)sum, (long long)a.n);
+  return CHOCO_OK;
+}
+
+static int gradnorm_run(const GradnormArgs& a, hipStream_t st) {
+  const int rc = gradnorm_check(a);
+  if (rc) return rc;
+  double* slots = nullptr;
+  double* sums = nullptr;
+  int32_t* meta = nullptr;
+  if (!a.total_in) {
+    slots = reinterpret_cast<double*>(a.ws);
+    sums = slots + norm_slots(a.nseg, a.n);
+    meta = reinterpret_cast<int32_t*>(sums + a.nseg);
+    const NormArgs pass{nullptr, a.grads, a.lens, a.dtypes, nullptr, a.flags, a.nseg, a.n, nullptr, a.ws, a.ws_bytes};
+    CHOCO_TRY(norm_pass(pass, slots, meta, st));
+  }
+  CHOCO_TRY(CHOCO_LAUNCH("param_gradnorm_total_kernel", "param_gradnorm_total_kernel", param_gradnorm_total_kernel,
+                         dim3(1), dim3(kTotalThreads), st, (const double*)slots,
+                         (int32_t)(a.total_in ? 0 : norm_slots(a.nseg, a.n)), (const int32_t*)meta, sums, a.norms,
+                         a.nseg, a.total_in, (float)a.max_norm, a.coef_dtype, a.out));
   return CHOCO_OK;
 }
 
@@ -1018,6 +1259,42 @@ CHOCO_API int choco_params_sgd_clip(void* const* params, const void* const* grad
                                     const float* norms, double clip_threshold, void* stream) {
   const SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, flat, n, mode,
                   true, norms, clip_threshold, false};
+  return sgd_run(a, as_stream(stream));
+}
+
+CHOCO_API size_t choco_params_gradnorm_workspace_size(int32_t nseg, int64_t n) { return gradnorm_ws_bytes(nseg, n); }
+CHOCO_API int choco_params_gradnorm_launches(int32_t nseg, int32_t pinned) { return gradnorm_launches(nseg, pinned); }
+
+CHOCO_API int choco_params_gradnorm(const void* const* grads, const int64_t* lens, const int32_t* dtypes,
+                                    const int32_t* flags, int32_t nseg, int64_t n, double max_norm,
+                                    int32_t coef_dtype, const float* total_in, float* out, float* norms, void* ws,
+                                    size_t ws_bytes, void* stream) {
+  const GradnormArgs a{grads, lens, dtypes, flags, nseg, n, max_norm, coef_dtype, total_in, out, norms, ws, ws_bytes};
+  return gradnorm_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_sgd_gclip(void* const* params, const void* const* grads, void* const* bufs,
+                                     const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                     const double* weight_decay, const double* momentum, const double* dampening,
+                                     const int32_t* flags, int32_t nseg, float* flat, int64_t n, int32_t mode,
+                                     const float* coef, void* stream) {
+  SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, flat, n, mode,
+            false, nullptr, 0.0, false};
+  a.gclip = true;
+  a.coef = coef;
+  return sgd_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_sgd_master_gclip(void* const* params, const void* const* grads, void* const* bufs,
+                                            const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                            const double* weight_decay, const double* momentum,
+                                            const double* dampening, const int32_t* flags, int32_t nseg,
+                                            float* master, int64_t n, int32_t mode, const float* coef,
+                                            void* stream) {
+  SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, master, n, mode,
+            false, nullptr, 0.0, true};
+  a.gclip = true;
+  a.coef = coef;
   return sgd_run(a, as_stream(stream));
 }
 

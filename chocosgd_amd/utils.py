@@ -41,6 +41,91 @@ def apply_gradient_loop(param_groups, state, apply_grad_to_model=True):
                 p.grad.data.copy_(d_p)  # into the grad's own storage: p.grad is not rebound
 
 
+def _params_with_grad(parameters):
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    return [p for p in parameters if p.grad is not None]
+
+
+def _total_norm(grads, total_norm, coef_dtype):
+    """The total L2 norm of `grads` as a 0-dim tensor of coef_dtype: sqrt of the fp64 sum of
+    squares over every element, rounded once to fp32 and then to coef_dtype -- or `total_norm`
+    (a tensor or a float) in its place."""
+    dev = grads[0].device
+    if total_norm is not None:
+        return torch.as_tensor(total_norm, dtype=torch.float32).detach().reshape(()).to(dev).to(coef_dtype)
+    sq = [g.detach().double().pow(2).sum().to(dev) for g in grads]
+    return torch.stack(sq).sum().sqrt().float().to(coef_dtype)
+
+
+def clip_grad_norm_loop(parameters, max_norm, total_norm=None, norm_type=2.0):
+    """torch.nn.utils.clip_grad_norm_ (distributed_running_nlp.py:96) with torch ops: the path
+    CPU tensors, and anything the batched kernels do not take, keep.  The total is this
+    package's (_total_norm: fp64 accumulation, one rounding to fp32 and one to the gradients'
+    common dtype) unless one is given; the scaling is torch.nn.utils.clip_grads_with_norm_.
+    norm_type != 2: torch's own total (torch.nn.utils.get_total_norm).  Returns the total."""
+    params = _params_with_grad(parameters)
+    if not params:
+        return torch.tensor(0.0)
+    grads = [p.grad for p in params]
+    if float(norm_type) != 2.0 and total_norm is None:
+        total = torch.nn.utils.get_total_norm(grads, norm_type)
+    else:
+        total = _total_norm(grads, total_norm, codec.common_grad_dtype(g.dtype for g in grads))
+    torch.nn.utils.clip_grads_with_norm_(params, max_norm, total)
+    return total
+
+
+def _clip_plan(params):
+    """The plan of `params` (each with a gradient) filled for the clip alone: grad mode, zero
+    hyperparameter tables, no buffers; None where a tensor cannot take the batched kernels."""
+    plan = _sgd_plan(params)
+    if plan is None or not all(plan.fits(i, p.grad) for i, p in enumerate(params)):
+        return None
+    zero = (0.0, 0.0, 0.0, 0.0)
+    for i, p in enumerate(params):
+        plan.param_ptrs[i], plan.grad_ptrs[i], plan.buf_ptrs[i], plan.flags[i] = p.data_ptr(), p.grad.data_ptr(), None, 0
+        if plan.seen[i] != zero:
+            plan.lr[i], plan.weight_decay[i], plan.momentum[i], plan.dampening[i] = zero
+            plan.seen[i] = zero
+    return plan
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None, total_norm=None):
+    """Drop-in for torch.nn.utils.clip_grad_norm_(model.parameters(), conf.rnn_clip)
+    (distributed_running_nlp.py:96): scales the gradients in place by
+    min(1, max_norm / (total + 1e-6)), torch's own op sequence for the coefficient, and returns
+    the total norm as a 0-dim device tensor (a copy).  fp32 / bf16 / fp16 ROCm gradients take
+    one norm pass (codec ParamSgdPlan.gradnorm) and ONE launch per chunk of tensors that reads
+    each gradient once and writes it once; the coefficient never leaves the device.  Parameters
+    without a gradient are skipped.  CPU tensors, other dtypes, non-contiguous gradients,
+    several devices and norm_type != 2 take clip_grad_norm_loop.
+
+    One difference from torch, by design: the total is sqrt of the fp64 sum of squares over all
+    elements, rounded once to fp32 (and to a 16-bit common dtype), not the norm of per-tensor
+    fp32 norms.  total_norm (a tensor or a float) pins the total instead.  `foreach` is
+    accepted and ignored.  error_if_nonfinite reads the total on the host, the only case that
+    does."""
+    params = _params_with_grad(parameters)
+    plan = _clip_plan(params) if params and float(norm_type) == 2.0 else None
+    if plan is None:
+        total = clip_grad_norm_loop(params, max_norm, total_norm, norm_type)
+    else:
+        out = plan.gradnorm(max_norm, total_norm=total_norm)
+        plan.run(None, grad_mode=True, write=True, gclip=out)
+        total = out[0].clone()
+    if error_if_nonfinite and not bool(torch.isfinite(total)):
+        raise RuntimeError(f"The total norm of order {norm_type} for gradients from `parameters` is non-finite, so "
+                           "it cannot be clipped. To disable this error and scale the gradients by the non-finite "
+                           "norm anyway, set `error_if_nonfinite=False`")
+    return total
+
+
+def _clip_coef32(total, max_norm):
+    """clip_grads_with_norm_'s coefficient lines on an fp32 0-dim tensor."""
+    return torch.clamp((total + 1e-6).reciprocal() * max_norm, max=1.0)
+
+
 _plans = {}  # id of a list's first parameter -> its ParamSgdPlan (which holds weak references only)
 
 
@@ -180,27 +265,66 @@ def _master_bufs_are_fp32(entries, state):
             raise _not_fp32(buf.dtype)
 
 
-def _sgd_master(param_groups, state, master, write):
+def _sgd_master(param_groups, state, master, write, clip=None):
     """apply_gradient on the master weights: the batched launch, or the loop above for tensors
     the kernel does not take.  Raises, with nothing changed, where the master does not fit the
-    model or a momentum buffer is not fp32."""
+    model or a momentum buffer is not fp32.  clip, a (clip_norm, write_clipped, total_norm)
+    tuple: global-norm clipping in front, the coefficient in fp32 and the clipped gradient not
+    narrowed before the update."""
     entries = master.entries(param_groups)
     plan = _sgd_fill(entries, state, True, master.buffer, master=True)
+    if clip is None:
+        if plan is None:
+            apply_gradient_master_loop(param_groups, state, master, write)
+        else:
+            plan.run_master(master.buffer, write)
+        return plan
+    clip_norm, write_clipped, total_norm = clip
     if plan is None:
-        apply_gradient_master_loop(param_groups, state, master, write)
+        grads = [p.grad for _, p in entries if p.grad is not None]
+        grads32 = [None] * len(entries)
+        if grads:
+            c = _clip_coef32(_total_norm(grads, total_norm, torch.float32), clip_norm)
+            for i, (_, p) in enumerate(entries):
+                if p.grad is not None:
+                    grads32[i] = p.grad.data.float() * c.to(p.grad.device)
+        apply_gradient_master_loop(param_groups, state, master, write, grads32=grads32)
+        if write_clipped:
+            for (_, p), g in zip(entries, grads32):
+                if g is not None:
+                    p.grad.data.copy_(g)
     else:
-        plan.run_master(master.buffer, write)
+        out = plan.gradnorm(clip_norm, coef_dtype=torch.float32, total_norm=total_norm)
+        plan.run_master(master.buffer, write, gclip=out, write_clipped=write_clipped)
     return plan
 
 
-def _sgd_batched(entries, state, apply_grad_to_model, flat, write):
+def _sgd_batched(entries, state, apply_grad_to_model, flat, write, clip=None):
     """One batched launch (per chunk) for `entries`, a list of (group, param) in flat order.
-    Returns False, with nothing changed, where a tensor cannot take it."""
+    Returns False, with nothing changed, where a tensor cannot take it.  clip, a (clip_norm,
+    write_clipped, total_norm) tuple: the norm pass in front and the clipped update."""
     plan = _sgd_fill(entries, state, apply_grad_to_model, flat)
     if plan is None:
         return False
-    plan.run(flat, grad_mode=not apply_grad_to_model, write=write)
+    if clip is None:
+        plan.run(flat, grad_mode=not apply_grad_to_model, write=write)
+    else:
+        plan.run(flat, grad_mode=not apply_grad_to_model, write=write,
+                 gclip=plan.gradnorm(clip[0], total_norm=clip[2]), write_clipped=clip[1])
     return True
+
+
+def _clipped_loop(param_groups, state, apply_grad_to_model, clip):
+    """clip_grad_norm_loop, then apply_gradient_loop.  Without write_clipped the gradients
+    get their own values back in apply mode, as the batched path leaves them."""
+    clip_norm, write_clipped, total_norm = clip
+    params = [p for group in param_groups for p in group["params"] if p.grad is not None]
+    saved = None if write_clipped or not apply_grad_to_model else [p.grad.data.clone() for p in params]
+    clip_grad_norm_loop(params, clip_norm, total_norm)
+    apply_gradient_loop(param_groups, state, apply_grad_to_model)
+    if saved is not None:
+        for p, g in zip(params, saved):
+            p.grad.data.copy_(g)
 
 
 def _sgd_fill(entries, state, apply_grad_to_model, flat, master=False):
@@ -259,7 +383,20 @@ def _sgd_fill(entries, state, apply_grad_to_model, flat, master=False):
     return plan
 
 
-def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None, master=None):
+def _clip_args(what, clip_norm, write_clipped=False, total_norm=None, apply_grad_to_model=True):
+    """The (clip_norm, write_clipped, total_norm) tuple of a clipped step, or None without one."""
+    if clip_norm is None:
+        if write_clipped or total_norm is not None:
+            raise RuntimeError(f"{what}: write_clipped / total_norm need clip_norm")
+        return None
+    if write_clipped and not apply_grad_to_model:
+        raise RuntimeError(f"{what}: write_clipped is for apply_grad_to_model=True; without it d_p is what the "
+                           "gradients receive")
+    return float(clip_norm), bool(write_clipped), total_norm
+
+
+def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None, master=None, clip_norm=None,
+                   write_clipped=False, total_norm=None):
     """optim/utils.py:13-47: weight decay, momentum with dampening, optional Nesterov, then
     p -= lr * d_p (apply_grad_to_model) or d_p left as the gradient.  Missing
     state[p]["momentum_buffer"] entries are created.  fp32 / bf16 / fp16 ROCm tensors take ONE
@@ -279,20 +416,33 @@ def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None,
     master (a MasterWeights of this model; apply_grad_to_model only, no flat_out): the update
     runs in fp32 on the master copy, in place, and the parameters receive its values narrowed
     to their dtype -- one launch of codec.params_sgd_master per chunk.  Missing momentum
-    buffers are created as fp32; an existing one of another dtype raises."""
+    buffers are created as fp32; an existing one of another dtype raises.
+
+    clip_norm (conf.rnn_clip): torch.nn.utils.clip_grad_norm_(params, clip_norm) in front of the
+    update (distributed_running_nlp.py:96-97), fused: one norm pass over the gradients, the
+    coefficient computed on the device with torch's op sequence, and the update launch scales
+    g by it on the load it does anyway.  The total norm is clip_grad_norm_'s of this module
+    (fp64 accumulation over all elements); total_norm (a tensor or a float) pins it.
+    p.grad is not written unless write_clipped (apply_grad_to_model only), which stores the
+    clipped gradient as torch's call leaves it.  With master the coefficient is computed in
+    fp32 and the clipped gradient is not narrowed before the update."""
+    clip = _clip_args("apply_gradient", clip_norm, write_clipped, total_norm, apply_grad_to_model)
     if master is not None:
         if not apply_grad_to_model:
             raise RuntimeError("apply_gradient(master=...) updates the model: apply_grad_to_model=False has no "
                                "master variant")
         if flat_out is not None:
             raise RuntimeError("apply_gradient(master=...): the master buffer is the flat copy; flat_out has no use")
-        _sgd_master(param_groups, state, master, write=True)
+        _sgd_master(param_groups, state, master, write=True, clip=clip)
         return
     entries = [(group, p) for group in param_groups for p in group["params"]]
     flat = getattr(flat_out, "buffer", flat_out)
-    if _sgd_batched(entries, state, apply_grad_to_model, flat, write=True):
+    if _sgd_batched(entries, state, apply_grad_to_model, flat, write=True, clip=clip):
         return
-    apply_gradient_loop(param_groups, state, apply_grad_to_model)
+    if clip is None:
+        apply_gradient_loop(param_groups, state, apply_grad_to_model)
+    else:
+        _clipped_loop(param_groups, state, apply_grad_to_model, clip)
     if flat is not None:
         flat.copy_(flatten([p.data if apply_grad_to_model else p.grad.data for _, p in entries], dtype=flat.dtype))
 
@@ -318,7 +468,7 @@ def recover_params(param_groups, param_names, rank=None, neighbor_hat_params=Non
 
 
 def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_params, neighbors_info,
-               consensus_stepsize, rank, defer_receive=False, state=None, master=None):
+               consensus_stepsize, rank, defer_receive=False, state=None, master=None, clip_norm=None):
     """ParallelCHOCO_V.step after apply_gradient (parallel_choco_v.py:115-155), with the
     consensus step fused into the compressor's first pass: recover_params, then
     compress (x += gamma * (memory - x_hat_i) and d = x_new - x_hat_i in one pass), sync,
@@ -344,17 +494,25 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
     on the master copy (the params are not written), and the master's buffer is the step's
     flatten_params -- no flat buffer is allocated and nothing is packed.  Compress, gossip,
     sync and uncompress work on it as on any flat x, and the unpack at the end narrows it into
-    the model."""
+    the model.
+
+    clip_norm (needs state; conf.rnn_clip): apply_gradient(clip_norm=...)'s global-norm
+    clipping in front of the step's update.  Without state the caller has run apply_gradient
+    already and there is nothing left to clip: that raises."""
     flatten_params = None
+    clip = _clip_args("fused_step", clip_norm)
+    if clip is not None and state is None:
+        raise RuntimeError("fused_step(clip_norm=...) clips in front of the step's own apply_gradient: pass "
+                           "state=optimizer.state (without it the caller's apply_gradient has already run)")
     if master is not None:
         if state is None:
             raise RuntimeError("fused_step(master=...) runs apply_gradient itself: pass state=optimizer.state")
         if master.param_names != list(param_names):
             raise RuntimeError("fused_step(master=...): the master weights were built for other param_names")
-        _sgd_master(param_groups, state, master, write=False)
+        _sgd_master(param_groups, state, master, write=False, clip=clip)
         flatten_params = master.flat
     elif state is not None:
-        flatten_params = _sgd_packed(param_groups, param_names, state)
+        flatten_params = _sgd_packed(param_groups, param_names, state, clip)
     if defer_receive:
         if flatten_params is None:
             params, flatten_params = recover_params(param_groups, param_names, get_hat_params=False)
@@ -382,16 +540,19 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
     return sync_buffer
 
 
-def _sgd_packed(param_groups, param_names, state):
+def _sgd_packed(param_groups, param_names, state, clip=None):
     """fused_step(state=...): apply_gradient and the pack of the new params in one launch.
     Returns the flat TensorBuffer, or None after the per-tensor loop has updated the params
     (tensors the batched kernel does not take: recover_params packs them as before)."""
     entries = step_entries(param_groups, param_names, "fused_step(state=...)")
     dev = entries[0][1].device
     flat = torch.empty(sum(p.numel() for _, p in entries), dtype=torch.float32, device=dev)
-    if dev.type == "cuda" and _sgd_batched(entries, state, True, flat, write=False):
+    if dev.type == "cuda" and _sgd_batched(entries, state, True, flat, write=False, clip=clip):
         return TensorBuffer.from_flat(flat, [p.size() for _, p in entries])
-    apply_gradient_loop(param_groups, state, True)
+    if clip is None:
+        apply_gradient_loop(param_groups, state, True)
+    else:
+        _clipped_loop(param_groups, state, True, clip)
     return None
 
 
@@ -439,17 +600,20 @@ def weighted_sum(buffers, weights):
     return sum([b * w for b, w in zip(buffers, weights)])
 
 
-def dpsgd_step_loop(param_groups, param_names, state, aggregator):
+def dpsgd_step_loop(param_groups, param_names, state, aggregator, clip=None):
     """dpsgd_step as the reference's op sequence (sgd.py:94-121), one torch op per line: the path
     CPU tensors, and anything the batched kernels do not take, keep."""
-    apply_gradient_loop(param_groups, state, True)
+    if clip is None:
+        apply_gradient_loop(param_groups, state, True)
+    else:
+        _clipped_loop(param_groups, state, True, clip)
     params, flatten_params = recover_params(param_groups, param_names, get_hat_params=False)
     flatten_params.buffer = aggregator._agg(flatten_params.buffer, op="weighted")
     flatten_params.unpack(params)
     return get_n_bits(flatten_params.buffer)
 
 
-def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, master=None):
+def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, master=None, clip_norm=None):
     """The decentralized branch of SGD.step (sgd.py:94-121), plain D-PSGD: apply_gradient fused
     with the pack of the new params (one launch; the params themselves are not written yet),
     the exchange of the flat fp32 buffer (_agg(op="get_raw_sync_data")), and ONE mix launch
@@ -460,14 +624,18 @@ def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, mas
     master (a MasterWeights of this model): the update runs on the master copy in place, the
     master buffer is what the neighbours exchange, and the mix writes the params and, in fp32,
     the master's spare buffer (sources and destination never alias); the two buffers are then
-    swapped."""
+    swapped.
+
+    clip_norm (conf.rnn_clip): apply_gradient(clip_norm=...)'s global-norm clipping in front of
+    the update."""
+    clip = _clip_args("dpsgd_step", clip_norm)
     entries = step_entries(param_groups, param_names, "dpsgd_step")
     params = [p for _, p in entries]
     dev = params[0].device
     if master is not None:
         if master.param_names != list(param_names):
             raise RuntimeError("dpsgd_step(master=...): the master weights were built for other param_names")
-        plan = _sgd_master(param_groups, state, master, write=False)
+        plan = _sgd_master(param_groups, state, master, write=False, clip=clip)
         flat = master.buffer
         if plan is None:  # the loop ran: the reference's op sequence on the master
             master.flat.buffer = aggregator._agg(flat, op="weighted")
@@ -481,8 +649,11 @@ def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, mas
     flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
     plan = _sgd_fill(entries, state, True, flat)
     if plan is None:
-        return dpsgd_step_loop(param_groups, param_names, state, aggregator)
-    plan.run(flat, grad_mode=False, write=False)
+        return dpsgd_step_loop(param_groups, param_names, state, aggregator, clip)
+    if clip is None:
+        plan.run(flat, grad_mode=False, write=False)
+    else:
+        plan.run(flat, grad_mode=False, write=False, gclip=plan.gradnorm(clip[0]))
     local_data = aggregator._agg(flat, op="get_raw_sync_data")
     srcs = list(local_data.values())
     weights = [neighbors_info[r] for r in local_data]

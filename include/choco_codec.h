@@ -725,6 +725,97 @@ int choco_params_mask(void* const* bufs, const int64_t* lens, const int32_t* dty
                       const int64_t* k_per_seg, int32_t nseg, const float* values,
                       const int32_t* indices, int64_t k, float* memory, int64_t n, void* stream);
 
+/* ------------------------------------------- global-norm gradient clipping
+ * torch.nn.utils.clip_grad_norm_(model.parameters(), conf.rnn_clip) in front of
+ * optimizer.step (pcode/distributed_running_nlp.py:94-97), fused into the batched update:
+ * one extra read of the gradients for the norm, a coefficient that never leaves the
+ * device, and an update that applies it to g on the load it already does.  Three entry
+ * points with the tables of choco_params_sgd.  With CD = coef_dtype, the gradients' common
+ * dtype (all bf16 -> bf16, all fp16 -> fp16, any fp32 or any mix -> fp32; the caller says
+ * which), every line one torch op with one rounding:
+ *     total = the total L2 norm, a value on CD's grid
+ *     t = rnd_CD(total + (float)1e-6)
+ *     r = rnd_CD(1.0f / t)                 a correctly rounded reciprocal, NOT max_norm / t:
+ *                                          torch's `max_norm / tensor` is reciprocal() * max_norm
+ *     c = rnd_CD(r * (float)max_norm)
+ *     c = c > 1 ? 1 : c                    clamp(max=1.0): a NaN stays NaN
+ *     g = rnd_DT(c * g)                    for EVERY element of every tensor with a gradient,
+ *                                          also when c == 1: c in fp32 times the widened g,
+ *                                          narrowed once to the gradient's dtype DT
+ * A NaN total makes every gradient NaN, a +inf total gives c = 0 (signed zeros), a zero
+ * total c = 1.  There is no `total >= max_norm` shortcut: a gradient whose norm equals
+ * max_norm is still scaled by (1 / (max_norm + 1e-6)) * max_norm < 1.
+ *
+ * choco_params_gradnorm: out (DEVICE, 2 floats, 4-byte aligned): out[0] = total, out[1] = c.
+ *   The total is the one place that differs from torch by design (torch: fp32 per-tensor
+ *   norms in its own reduction order, each rounded to the gradient's dtype, then the norm
+ *   of the stacked norms): here total = sqrt(sum over all elements of all tensors with a
+ *   gradient of g^2), squares and sums in fp64 in a fixed order with no floating-point
+ *   atomics, rounded once to fp32 and, for a 16-bit CD, to CD.  CHOCO_SGD_F_NOGRAD and
+ *   zero-length tensors contribute 0.  The norm pass is choco_params_sqnorm's
+ *   "param_sqnorm_kernel" on the raw gradients (no weight decay), one launch per chunk;
+ *   then ONE single-workgroup launch of "param_gradnorm_total_kernel" adds each tensor's
+ *   partials in the order choco_params_sqnorm's finish uses, adds the per-tensor fp64 sums
+ *   in ascending tensor order, takes the square root in fp64 and evaluates the lines above.
+ *   norms (DEVICE, nseg floats, or NULL): norms[s] = the per-tensor norm from the same
+ *   partials, bit for bit what choco_params_sqnorm gives at zero weight decay.  Two calls
+ *   on the same data give the same bits.  The workspace
+ *   (choco_params_gradnorm_workspace_size bytes, 8-byte aligned) needs no initialisation:
+ *   everything read from it is written by the same call.  total_in != NULL (DEVICE, one
+ *   float) is parity mode: no norm pass, nothing of the layout or the workspace is read
+ *   (they may be NULL), total = rnd_CD(*total_in), and norms must be NULL.  The host never
+ *   reads the total or the coefficient.  Launches:
+ *   choco_params_gradnorm_launches(nseg, pinned) -- chunks of 112 tensors plus one, or 1
+ *   when pinned; 0 for nseg <= 0.  Rejected (CHOCO_ERR_INVALID, nothing launched): nseg <= 0;
+ *   n outside [0, 2^31); a max_norm that is NaN, negative or not finite as a float; an
+ *   unknown coef_dtype; a NULL or misaligned out; a misaligned norms or total_in; norms
+ *   with total_in; and, unpinned, null tables, negative or oversumming lengths, lengths
+ *   that do not sum to n, unknown dtype or flag bits, misaligned gradient pointers, a NULL
+ *   grad without NOGRAD, a NULL or misaligned workspace.  A short workspace returns
+ *   CHOCO_ERR_WORKSPACE.
+ *
+ * choco_params_sgd_gclip: choco_params_sgd with one line in front, g = rnd_DT(c * g) with
+ *   c = *coef (DEVICE, one float, 4-byte aligned, e.g. out + 1 of choco_params_gradnorm),
+ *   read by the kernel.  Apply mode and grad mode, with or without flat.
+ *   CHOCO_SGD_MODE_WRITE_CLIPPED (apply mode only) also stores the clipped g into grads[s]
+ *   -- what clip_grad_norm_ leaves in p.grad; without the bit the gradients are not
+ *   written in apply mode, as in choco_params_sgd, and flat may then be NULL with the bit
+ *   as the only write.  NOGRAD tensors stay a pure pack.  In grad mode with zero weight
+ *   decay and momentum and WRITE_GRADS this is the in-place clip itself: g read once,
+ *   written once.  Launches: choco_params_sgd_launches(nseg) of "param_sgd_gclip_kernel", an
+ *   instantiation of its own: "param_sgd_kernel" carries neither the pointer nor the multiply.
+ *
+ * choco_params_sgd_master_gclip: choco_params_sgd_master with g = c * g in fp32 in front,
+ *   NOT narrowed before the master lines (the caller computes c with CD = fp32: the point
+ *   of the master path, and a documented difference from torch for 16-bit models).
+ *   WRITE_CLIPPED stores that product narrowed to the gradient's dtype into grads[s].
+ *   Launches: choco_params_sgd_master_launches(nseg) of "param_sgd_master_gclip_kernel".
+ *
+ * Both check every argument before the first launch without a HIP call and reject, in
+ * addition to the base function's own list: coef NULL or not 4-byte aligned;
+ * WRITE_CLIPPED in grad mode; WRITE_CLIPPED with a NULL grad pointer (a NULL grad without
+ * NOGRAD is rejected with or without the bit); CHOCO_SGD_MODE_ADD_FLAT; unknown mode bits. */
+#define CHOCO_SGD_MODE_WRITE_CLIPPED 16
+size_t choco_params_gradnorm_workspace_size(int32_t nseg, int64_t n);
+int choco_params_gradnorm_launches(int32_t nseg, int32_t pinned);
+/* pcode/distributed_running_nlp.py:96 */
+int choco_params_gradnorm(const void* const* grads, const int64_t* lens, const int32_t* dtypes,
+                          const int32_t* flags, int32_t nseg, int64_t n, double max_norm,
+                          int32_t coef_dtype, const float* total_in, float* out, float* norms,
+                          void* ws, size_t ws_bytes, void* stream);
+/* pcode/distributed_running_nlp.py:96-97 */
+int choco_params_sgd_gclip(void* const* params, const void* const* grads, void* const* bufs,
+                           const int64_t* lens, const int32_t* dtypes, const double* lr,
+                           const double* weight_decay, const double* momentum,
+                           const double* dampening, const int32_t* flags, int32_t nseg, float* flat,
+                           int64_t n, int32_t mode, const float* coef, void* stream);
+int choco_params_sgd_master_gclip(void* const* params, const void* const* grads, void* const* bufs,
+                                  const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                  const double* weight_decay, const double* momentum,
+                                  const double* dampening, const int32_t* flags, int32_t nseg,
+                                  float* master, int64_t n, int32_t mode, const float* coef,
+                                  void* stream);
+
 /* ------------------------------------------- neighbour-weighted model mix
  * The dense line three decentralized optimizers of the reference share,
  *     sum([hat_r.buffer * neighbors_info[r] for r, hat_r in ...])
