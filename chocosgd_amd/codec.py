@@ -1103,6 +1103,7 @@ class ParamSgdPlan:
         self.seen = [None] * nseg  # the hyperparameter tuple last written, per tensor
         self._norms = self._norm_ws = None  # sqnorm()'s output and workspace, allocated on first use
         self._gn_out = self._gn_ws = None   # gradnorm()'s
+        self._ls_out = None                 # gradnorm_scaled()'s
         self._refs = [weakref.ref(p) for p in params]
 
     def holds(self, params):
@@ -1169,6 +1170,57 @@ class ParamSgdPlan:
                    "choco_params_gradnorm")
         return self._gn_out
 
+    def gradnorm_scaled(self, scaler, max_norm=None, coef_dtype=None, norms=None):
+        """One choco_params_gradnorm_scaled over the gradient pointers and flags as they stand,
+        the gradients still multiplied by the loss scale: gradnorm()'s norm pass, then ONE
+        launch that tests the fp64 sum of squares for an inf / NaN, unscales the total, computes
+        the clip coefficient (max_norm None: 1) times 1 / scale, and updates `scaler`'s device
+        state as torch._amp_update_scale_ does.  scaler: a utils.LossScaler (its `_scale` and
+        `_growth_tracker` tensors on this device, and its three factors).  Returns the plan's
+        own four-element fp32 tensor [total, coefficient / scale, found, scale], overwritten by
+        the next call: hand it to run(scaled=...) / run_master(scaled=...).  Nothing is read on
+        the host.  There is no pinned total: it would have no norm pass to detect an overflow
+        from."""
+        L = lib()
+        if coef_dtype is None:
+            coef_dtype = common_grad_dtype(dt for dt, fl in zip(self.dtypes, self.flags) if not fl & SGD_F_NOGRAD)
+        cd = PARAM_DTYPES.get(coef_dtype)
+        if cd is None:
+            raise RuntimeError(f"coef_dtype must be float32, bfloat16 or float16, got {coef_dtype}")
+        scale, tracker = scaler._scale, scaler._growth_tracker
+        _require(scale, torch.float32, "the loss scale")
+        _require(tracker, torch.int32, "the growth tracker")
+        if scale.device != self.device or tracker.device != self.device or scale.numel() != 1 or tracker.numel() != 1:
+            raise RuntimeError(f"the loss scaler's state must be one-element tensors on {self.device}")
+        if self._ls_out is None:
+            self._ls_out = torch.empty(4, dtype=torch.float32, device=self.device)
+        if self._gn_ws is None:
+            self._gn_ws = torch.empty(int(L.choco_params_gradnorm_workspace_size(self.nseg, self.n)),
+                                      dtype=torch.uint8, device=self.device)
+        if norms is not None:
+            _require(norms, torch.float32, "norms")
+            if norms.device != self.device or norms.numel() != self.nseg:
+                raise RuntimeError(f"norms must hold {self.nseg} elements on {self.device}")
+        _lib.check(L.choco_params_gradnorm_scaled(self.grad_ptrs, self.lens, self.dts, self.flags, self.nseg, self.n,
+                                                  0.0 if max_norm is None else float(max_norm), cd, _ptr(scale),
+                                                  _ptr(tracker), float(scaler.growth_factor),
+                                                  float(scaler.backoff_factor), int(scaler.growth_interval),
+                                                  0 if max_norm is None else 1, _ptr(self._ls_out), _ptr(norms),
+                                                  _ptr(self._gn_ws), self._gn_ws.numel(), _stream(self.device)),
+                   "choco_params_gradnorm_scaled")
+        return self._ls_out
+
+    def _scaled_ptr(self, scaled, others):
+        """scaled (gradnorm_scaled()'s tensor) as a pointer; `others`: whether a keyword it does
+        not combine with was given."""
+        if others:
+            raise RuntimeError("scaled (the loss-scaled step) does not combine with gclip, norms / clip_threshold / "
+                               "add_flat or grad_mode: its clip is gradnorm_scaled(max_norm=)'s")
+        _require(scaled, torch.float32, "scaled")
+        if scaled.device != self.device or scaled.numel() != 4:
+            raise RuntimeError(f"scaled must be gradnorm_scaled()'s four-element tensor on {self.device}")
+        return scaled.data_ptr()
+
     def _coef_ptr(self, gclip):
         _require(gclip, torch.float32, "gclip")
         if gclip.device != self.device or gclip.numel() != 2:
@@ -1176,7 +1228,7 @@ class ParamSgdPlan:
         return gclip.data_ptr() + 4
 
     def run(self, flat=None, grad_mode=False, write=True, norms=None, clip_threshold=None, add_flat=False,
-            gclip=None, write_clipped=False):
+            gclip=None, write_clipped=False, scaled=None):
         """One choco_params_sgd over the tables as they stand.  apply mode (grad_mode False):
         write -> the params are updated; grad mode: write -> d_p goes into the grads' storage.
         flat (fp32, n elements, or None) receives the new params / d_p in the same pass.
@@ -1189,13 +1241,28 @@ class ParamSgdPlan:
         gclip (gradnorm()'s tensor): choco_params_sgd_gclip -- every gradient is scaled by the
         global-norm clip coefficient as it is loaded; write_clipped (apply mode): the clipped
         gradient is also stored into the grads' storage.  Not together with norms /
-        clip_threshold / add_flat."""
+        clip_threshold / add_flat.
+
+        scaled (gradnorm_scaled()'s tensor; apply mode, none of the keywords above):
+        choco_params_sgd_scaled -- every gradient is multiplied by its second element (the clip
+        coefficient over the loss scale), and where its third says the gradients held an inf or
+        a NaN the step is skipped on the device: flat receives the unchanged params and nothing
+        else is written.  write_clipped stores the unscaled, clipped gradient."""
         if flat is not None:
             _require(flat, torch.float32, "flat")
             if flat.device != self.device or flat.numel() != self.n:
                 raise RuntimeError(f"flat must hold {self.n} elements on {self.device}")
         mode = (SGD_MODE_GRAD | (SGD_MODE_WRITE_GRADS if write else 0)) if grad_mode else \
             (SGD_MODE_WRITE_PARAMS if write else 0)
+        if scaled is not None:
+            out = self._scaled_ptr(scaled, gclip is not None or norms is not None or clip_threshold is not None
+                                   or add_flat or grad_mode)
+            _lib.check(lib().choco_params_sgd_scaled(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens,
+                                                     self.dts, self.lr, self.weight_decay, self.momentum,
+                                                     self.dampening, self.flags, self.nseg, _ptr(flat), self.n,
+                                                     mode | (SGD_MODE_WRITE_CLIPPED if write_clipped else 0), out,
+                                                     _stream(self.device)), "choco_params_sgd_scaled")
+            return
         if gclip is None and write_clipped:
             raise RuntimeError("write_clipped needs gclip (gradnorm()'s tensor)")
         if gclip is not None:
@@ -1237,7 +1304,7 @@ class ParamSgdPlan:
         return (t.dtype == torch.float32 and t.device == self.device and t.numel() == self.numels[i]
                 and t.is_contiguous())
 
-    def run_master(self, master, write=True, gclip=None, write_clipped=False):
+    def run_master(self, master, write=True, gclip=None, write_clipped=False, scaled=None):
         """One choco_params_sgd_master over the tables as they stand: the update runs on
         `master` (the persistent flat fp32 copy of the parameters, n elements) in place, with
         fp32 momentum buffers behind `buf_ptrs` and the gradients in their parameters' dtype;
@@ -1245,10 +1312,23 @@ class ParamSgdPlan:
 
         gclip (gradnorm(coef_dtype=torch.float32)'s tensor): choco_params_sgd_master_gclip --
         g = c * g in fp32, not narrowed, in front of the update; write_clipped: that product,
-        narrowed, is stored into the grads' storage."""
+        narrowed, is stored into the grads' storage.
+
+        scaled (gradnorm_scaled(coef_dtype=torch.float32)'s tensor; not with gclip):
+        choco_params_sgd_master_scaled -- the same with its second element as the coefficient,
+        and a step its third element marks as overflowed touches nothing."""
         _require(master, torch.float32, "master")
         if master.device != self.device or master.numel() != self.n:
             raise RuntimeError(f"master must hold {self.n} elements on {self.device}")
+        if scaled is not None:
+            out = self._scaled_ptr(scaled, gclip is not None)
+            mode = (SGD_MODE_WRITE_PARAMS if write else 0) | (SGD_MODE_WRITE_CLIPPED if write_clipped else 0)
+            _lib.check(lib().choco_params_sgd_master_scaled(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens,
+                                                            self.dts, self.lr, self.weight_decay, self.momentum,
+                                                            self.dampening, self.flags, self.nseg, _ptr(master),
+                                                            self.n, mode, out, _stream(self.device)),
+                       "choco_params_sgd_master_scaled")
+            return
         if gclip is None and write_clipped:
             raise RuntimeError("write_clipped needs gclip (gradnorm()'s tensor)")
         if gclip is not None:

@@ -192,7 +192,14 @@ CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, bo
 // then coef, ONE float, the global-norm clip coefficient every gradient is scaled by on the load
 // the update does anyway, and thr is not used; the multiply is compiled into neither of the
 // other two, whose argument list this is.
-template <bool EXT, bool GC = false>
+//
+// SC ("param_sgd_scaled_kernel", choco_params_sgd_scaled; GC with it): `norms` is then the
+// four floats choco_params_gradnorm_scaled leaves, the coefficient is norms[1] (the clip
+// coefficient times 1 / loss scale) and norms[2] != 0 says the raw gradients held an inf or a NaN:
+// the step is skipped on the device -- every tensor is a pack_only one (flat = p, nothing else
+// written), and with no flat side the workgroup returns.  Both are uniform loads, one each per
+// workgroup.  The test is compiled into that instantiation only.
+template <bool EXT, bool GC = false, bool SC = false>
 __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb, float* flat, int64_t tile0,
                                                                int32_t flat16, int32_t mode, const float* norms,
                                                                float thr) {
@@ -201,7 +208,9 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
   const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
   if (s0 < 0) return;
   const bool grad_mode = (mode & CHOCO_SGD_MODE_GRAD) != 0;
-  const float gc = GC ? *norms : 1.0f;  // a uniform load
+  const float gc = GC ? norms[SC ? 1 : 0] : 1.0f;  // a uniform load
+  const bool found = SC && norms[2] != 0.0f;       // ... and another
+  if (SC && found && flat == nullptr) return;
   for (int s = s0; s < nt; ++s) {
     const int64_t o0 = tb.off[s];
     if (o0 >= thi) break;
@@ -212,7 +221,7 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
     SgdTensor t;
     t.p = tb.p[s]; t.g = tb.g[s]; t.buf = tb.buf[s]; t.flat = flat;
     t.wd = tb.wd[s]; t.mom = tb.mom[s]; t.omd = tb.omd[s]; t.nlr = tb.nlr[s];
-    t.pack_only = (fl & CHOCO_SGD_F_NOGRAD) != 0;
+    t.pack_only = (fl & CHOCO_SGD_F_NOGRAD) != 0 || (SC && found);
     t.has_wd = (fl & kSgdHasWd) != 0;
     t.has_mom = (fl & kSgdHasMom) != 0;
     t.nesterov = (fl & CHOCO_SGD_F_NESTEROV) != 0;
@@ -330,6 +339,17 @@ CHOCO_DEV void master_span(const SgdTensor& t, float* master, int64_t o0, int64_
 
 // COEF: no argument at all (param_sgd_master_kernel, the argument list it always had), or one
 // `const float*`, the global-norm clip coefficient ("param_sgd_master_gclip_kernel").
+// Or one ScaledOut ("param_sgd_master_scaled_kernel", choco_params_sgd_master_scaled):
+// choco_params_gradnorm_scaled's four floats -- the coefficient is out[1], and out[2] != 0 (an inf
+// or a NaN among the raw gradients) makes the workgroup return before it touches anything.
+struct ScaledOut {
+  const float* out;
+};
+CHOCO_DEV float coef_of(const float* coef) { return *coef; }
+CHOCO_DEV float coef_of(ScaledOut s) { return s.out[1]; }
+CHOCO_DEV bool found_of(const float*) { return false; }
+CHOCO_DEV bool found_of(ScaledOut s) { return s.out[2] != 0.0f; }
+
 template <typename... COEF>
 __global__ __launch_bounds__(kPbThreads) void param_sgd_master_kernel(const SgdTable tb, float* master, int64_t tile0,
                                                                       int32_t master16, int32_t mode, COEF... coef) {
@@ -339,7 +359,8 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_master_kernel(const SgdT
   const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
   if (s0 < 0) return;
   float gc = 1.0f;
-  ((gc = *coef), ...);  // a uniform load
+  ((gc = coef_of(coef)), ...);  // a uniform load
+  if ((found_of(coef) || ...)) return;  // ... and, in the scaled instantiation alone, another
   for (int s = s0; s < nt; ++s) {
     const int64_t o0 = tb.off[s];
     if (o0 >= thi) break;
@@ -377,6 +398,7 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_master_kernel(const SgdT
     else master_span<CHOCO_DT_F16, GC>(t, master, o0, a, b, vec);
   }
 }
+
 
 
 // ------------------------------------------------------------------ all-reduce SGD: the flat summed gradient
@@ -548,6 +570,8 @@ struct SgdArgs {
   bool flatgrad;         // one of those two entry points
   bool gclip;            // choco_params_sgd[_master]_gclip: the WRITE_CLIPPED bit and the argument below
   const float* coef;     // device, the global-norm clip coefficient (choco_params_gradnorm's out + 1)
+  bool scaled;           // choco_params_sgd[_master]_scaled (gclip with it): coef is choco_params_gradnorm_scaled's
+                         // out, four floats, and the step is skipped on the device where out[2] != 0
 };
 
 static bool elem_aligned(const void* p, uintptr_t esz) { return (reinterpret_cast<uintptr_t>(p) & (esz - 1)) == 0; }
@@ -612,11 +636,16 @@ static int sgd_check(const SgdArgs& a) {
     CHOCO_REQUIRE(a.flat, "master is null");
   }
   constexpr int32_t kModes = CHOCO_SGD_MODE_GRAD | CHOCO_SGD_MODE_WRITE_PARAMS | CHOCO_SGD_MODE_WRITE_GRADS;
-  if (a.gclip) CHOCO_REQUIRE(!(a.mode & CHOCO_SGD_MODE_ADD_FLAT), "ADD_FLAT has no global-norm clipped variant");
+  if (a.gclip)
+    CHOCO_REQUIRE(!(a.mode & CHOCO_SGD_MODE_ADD_FLAT), "ADD_FLAT has no %s variant",
+                  a.scaled ? "loss-scaled" : "global-norm clipped");
   CHOCO_REQUIRE((a.mode & ~(kModes | (a.ext ? CHOCO_SGD_MODE_ADD_FLAT : 0) | clipped)) == 0, "unknown mode bits 0x%x",
                 (unsigned)a.mode);
   const bool grad_mode = (a.mode & CHOCO_SGD_MODE_GRAD) != 0;
-  if (a.gclip) {
+  if (a.scaled) {
+    CHOCO_REQUIRE(a.coef && aligned4(a.coef), "out must be a 4-byte aligned device pointer");
+    CHOCO_REQUIRE(!grad_mode, "the loss-scaled update runs in apply mode: mode bits 0x%x", (unsigned)a.mode);
+  } else if (a.gclip) {
     CHOCO_REQUIRE(a.coef && aligned4(a.coef), "coef must be a 4-byte aligned device pointer");
     CHOCO_REQUIRE(!(grad_mode && (a.mode & CHOCO_SGD_MODE_WRITE_CLIPPED)),
                   "WRITE_CLIPPED is for apply mode: grad mode writes d_p into the grads");
@@ -709,6 +738,14 @@ static int sgd_run(const SgdArgs& a, hipStream_t st) {
       CHOCO_TRY(CHOCO_LAUNCH("param_sgd_flatgrad_kernel", "param_sgd_flatgrad_kernel", param_sgd_flatgrad_kernel<false>,
                              dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.gsum, (float*)nullptr, tile0,
                              (float)a.divisor, al16, a.mode));
+    else if (a.scaled && a.master)
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_master_scaled_kernel", "param_sgd_master_scaled_kernel",
+                             param_sgd_master_kernel<ScaledOut>, dim3((unsigned)tiles), dim3(kPbThreads), st, tb,
+                             a.flat, tile0, flat16, a.mode, ScaledOut{a.coef}));
+    else if (a.scaled)
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_scaled_kernel", "param_sgd_scaled_kernel", param_sgd_kernel<false, true, true>,
+                             dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.flat, tile0, flat16, a.mode, a.coef,
+                             0.0f));
     else if (a.gclip && a.master)
       CHOCO_TRY(CHOCO_LAUNCH("param_sgd_master_gclip_kernel", "param_sgd_master_gclip_kernel",
                              param_sgd_master_kernel<const float*>, dim3((unsigned)tiles), dim3(kPbThreads), st, tb,
@@ -968,20 +1005,80 @@ CHOCO_DEV float rnd_as(float v, int dt) {
   return v;
 }
 
+//
+// The scaled variant (choco_params_gradnorm_scaled, "param_gradnorm_scaled_total_kernel"): dynamic
+// loss scaling on the same sum.  The gradients are still multiplied by the loss scale, so with
+// scale = *ls.scale and inv = (float)(1.0 / (double)scale)
+//     found = !isfinite(sum)                          the fp64 sum, not the fp32 total: squares are
+//                                                     non-negative and their fp64 sum cannot overflow
+//     total = rnd_CD((float)sqrt(sum) * inv)          the norm of the unscaled gradient
+//     c     = the lines above (has_clip), or 1
+//     gc    = c * inv                                 fp32, not narrowed
+//     out   = [total, gc, found ? 1 : 0, scale]
+// and then torch's _amp_update_scale_ on the device state, by the lane that writes out[]:
+//     found:  scale = (float)((double)scale * backoff), tracker = 0
+//     else:   tracker + 1 == interval ? (s = (float)((double)scale * growth), kept if finite; tracker = 0)
+//                                     : tracker += 1
+// Same staging, same additions in the same order; the host never reads any of it.
+struct LossScale {
+  float* scale;      // device, the fp32 loss scale
+  int32_t* tracker;  // device, steps since the scale last changed
+  double growth, backoff;
+  int32_t interval, has_clip;
+};
+
+// the one lane that writes out[]: sum = the fp64 sum of squares, root = (float)sqrt(sum)
+CHOCO_DEV void scaled_finish(double sum, float root, float max_norm, int32_t cd, float* out, const LossScale& ls) {
+  const float scale = *ls.scale;
+  const float inv = (float)(1.0 / (double)scale);
+  const bool found = !__builtin_isfinite(sum);
+  const float total = rnd_as(__fmul_rn(root, inv), cd);
+  float c = 1.0f;
+  if (ls.has_clip) {
+    const float t = rnd_as(__fadd_rn(total, 1e-6f), cd);
+    const float r = rnd_as(__fdiv_rn(1.0f, t), cd);
+    c = rnd_as(__fmul_rn(r, max_norm), cd);
+    c = c > 1.0f ? 1.0f : c;
+  }
+  out[0] = total;
+  out[1] = __fmul_rn(c, inv);
+  out[2] = found ? 1.0f : 0.0f;
+  out[3] = scale;
+  if (found) {
+    *ls.scale = (float)((double)scale * ls.backoff);
+    *ls.tracker = 0;
+  } else {
+    const int32_t ok = *ls.tracker + 1;
+    if (ok == ls.interval) {
+      const float s = (float)((double)scale * ls.growth);
+      if (__builtin_isfinite(s)) *ls.scale = s;
+      *ls.tracker = 0;
+    } else {
+      *ls.tracker = ok;
+    }
+  }
+}
+
 constexpr int kTotalThreads = 1024;
 constexpr int kTotalStageSlots = 5120;  // 40 KB of fp64 slots, 8 KB of meta words and 8 KB of sums in LDS
 constexpr int kTotalStageSegs = 1024;
+// LS: no argument at all (param_gradnorm_total_kernel, the argument list it always had), or one
+// LossScale ("param_gradnorm_scaled_total_kernel"; total_in is then null: a pinned total has no
+// norm pass to detect an overflow from).
+template <typename... LS>
 __global__ __launch_bounds__(kTotalThreads) void param_gradnorm_total_kernel(const double* slots, int32_t nslots,
                                                                              const int32_t* meta, double* sums,
                                                                              float* norms, int32_t nseg,
                                                                              const float* total_in, float max_norm,
-                                                                             int32_t cd, float* out) {
+                                                                             int32_t cd, float* out, const LS... ls) {
+  constexpr bool SC = sizeof...(LS) != 0;
   __shared__ double s_slots[kTotalStageSlots];
   __shared__ int32_t s_meta[2 * kTotalStageSegs];
   __shared__ double s_sums[kTotalStageSegs];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   float total;
+  double sum = 0.0;  // the fp64 sum of squares: what the scaled variant tests for an overflow
   if (total_in != nullptr) {
     total = *total_in;
   } else {
@@ -1005,9 +1102,14 @@ __global__ __launch_bounds__(kTotalThreads) void param_gradnorm_total_kernel(con
     }
     __syncthreads();  // sums[] of every wave, written above, is read by the first one
     if (wave != 0) return;
-    total = (float)sqrt(wave_ordered_sum(sums, nseg, lane));
+    sum = wave_ordered_sum(sums, nseg, lane);
+    total = (float)sqrt(sum);
   }
   if (tid != 0) return;
+  if constexpr (SC) {
+    (scaled_finish(sum, total, max_norm, cd, out, ls), ...);
+    return;
+  }
   total = rnd_as(total, cd);
   const float t = rnd_as(__fadd_rn(total, 1e-6f), cd);
   const float r = rnd_as(__fdiv_rn(1.0f, t), cd);
@@ -1016,6 +1118,7 @@ __global__ __launch_bounds__(kTotalThreads) void param_gradnorm_total_kernel(con
   out[0] = total;
   out[1] = c;
 }
+
 
 static int norm_launches(int32_t nseg) { return nseg <= 0 ? 0 : (nseg + kNormCap - 1) / kNormCap + 1; }
 static size_t norm_slots(int32_t nseg, int64_t n) { return (size_t)(n / kPbTile + 1) + (size_t)nseg; }
@@ -1135,14 +1238,26 @@ struct GradnormArgs {
   float* norms;
   void* ws;
   size_t ws_bytes;
+  bool scaled;   // choco_params_gradnorm_scaled: out holds four floats and ls is the loss-scale state
+  LossScale ls;
 };
 
 static int gradnorm_check(const GradnormArgs& a) {
   CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
   CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
-  // tested as the kernel uses it: the fp32 value
-  CHOCO_REQUIRE(a.max_norm >= 0.0 && a.max_norm <= 3.4028234663852886e38,
-                "max_norm must be >= 0 and finite as an fp32 value, got %g", a.max_norm);
+  // tested as the kernel uses it: the fp32 value (a scaled call without a clip does not use it)
+  if (!a.scaled || a.ls.has_clip)
+    CHOCO_REQUIRE(a.max_norm >= 0.0 && a.max_norm <= 3.4028234663852886e38,
+                  "max_norm must be >= 0 and finite as an fp32 value, got %g", a.max_norm);
+  if (a.scaled) {
+    CHOCO_REQUIRE(a.ls.scale && aligned4(a.ls.scale), "scale_state must be a 4-byte aligned device pointer");
+    CHOCO_REQUIRE(a.ls.tracker && aligned4(a.ls.tracker), "growth_tracker must be a 4-byte aligned device pointer");
+    CHOCO_REQUIRE(a.ls.growth > 1.0 && std::isfinite(a.ls.growth), "growth must be finite and > 1, got %g",
+                  a.ls.growth);
+    CHOCO_REQUIRE(a.ls.backoff > 0.0 && a.ls.backoff < 1.0, "backoff must be in (0, 1), got %g", a.ls.backoff);
+    CHOCO_REQUIRE(a.ls.interval >= 1, "interval must be >= 1, got %d", (int)a.ls.interval);
+    CHOCO_REQUIRE(a.ls.has_clip == 0 || a.ls.has_clip == 1, "has_clip must be 0 or 1, got %d", (int)a.ls.has_clip);
+  }
   CHOCO_REQUIRE(a.coef_dtype >= CHOCO_DT_F32 && a.coef_dtype <= CHOCO_DT_F16, "unknown coef_dtype code %d",
                 (int)a.coef_dtype);
   CHOCO_REQUIRE(a.out && aligned4(a.out), "out must be a 4-byte aligned device pointer");
@@ -1189,7 +1304,15 @@ static int gradnorm_run(const GradnormArgs& a, hipStream_t st) {
     const NormArgs pass{nullptr, a.grads, a.lens, a.dtypes, nullptr, a.flags, a.nseg, a.n, nullptr, a.ws, a.ws_bytes};
     CHOCO_TRY(norm_pass(pass, slots, meta, st));
   }
-  CHOCO_TRY(CHOCO_LAUNCH("param_gradnorm_total_kernel", "param_gradnorm_total_kernel", param_gradnorm_total_kernel,
+  if (a.scaled) {
+    CHOCO_TRY(CHOCO_LAUNCH("param_gradnorm_scaled_total_kernel", "param_gradnorm_scaled_total_kernel",
+                           param_gradnorm_total_kernel<LossScale>, dim3(1), dim3(kTotalThreads), st,
+                           (const double*)slots, (int32_t)norm_slots(a.nseg, a.n), (const int32_t*)meta, sums, a.norms,
+                           a.nseg, (const float*)nullptr, (float)(a.ls.has_clip ? a.max_norm : 0.0), a.coef_dtype,
+                           a.out, a.ls));
+    return CHOCO_OK;
+  }
+  CHOCO_TRY(CHOCO_LAUNCH("param_gradnorm_total_kernel", "param_gradnorm_total_kernel", param_gradnorm_total_kernel<>,
                          dim3(1), dim3(kTotalThreads), st, (const double*)slots,
                          (int32_t)(a.total_in ? 0 : norm_slots(a.nseg, a.n)), (const int32_t*)meta, sums, a.norms,
                          a.nseg, a.total_in, (float)a.max_norm, a.coef_dtype, a.out));
@@ -1273,6 +1396,16 @@ CHOCO_API int choco_params_gradnorm(const void* const* grads, const int64_t* len
   return gradnorm_run(a, as_stream(stream));
 }
 
+CHOCO_API int choco_params_gradnorm_scaled(const void* const* grads, const int64_t* lens, const int32_t* dtypes,
+                                           const int32_t* flags, int32_t nseg, int64_t n, double max_norm,
+                                           int32_t coef_dtype, float* scale_state, int32_t* growth_tracker,
+                                           double growth, double backoff, int32_t interval, int32_t has_clip,
+                                           float* out, float* norms, void* ws, size_t ws_bytes, void* stream) {
+  const GradnormArgs a{grads, lens, dtypes, flags, nseg, n, max_norm, coef_dtype, nullptr, out, norms, ws, ws_bytes,
+                       true, LossScale{scale_state, growth_tracker, growth, backoff, interval, has_clip}};
+  return gradnorm_run(a, as_stream(stream));
+}
+
 CHOCO_API int choco_params_sgd_gclip(void* const* params, const void* const* grads, void* const* bufs,
                                      const int64_t* lens, const int32_t* dtypes, const double* lr,
                                      const double* weight_decay, const double* momentum, const double* dampening,
@@ -1306,4 +1439,29 @@ CHOCO_API int choco_params_sqnorm(const void* const* params, const void* const* 
                                   int64_t n, float* norms, void* ws, size_t ws_bytes, void* stream) {
   const NormArgs a{params, grads, lens, dtypes, weight_decay, flags, nseg, n, norms, ws, ws_bytes};
   return norm_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_sgd_scaled(void* const* params, const void* const* grads, void* const* bufs,
+                                      const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                      const double* weight_decay, const double* momentum, const double* dampening,
+                                      const int32_t* flags, int32_t nseg, float* flat, int64_t n, int32_t mode,
+                                      const float* out, void* stream) {
+  SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, flat, n, mode,
+            false, nullptr, 0.0, false};
+  a.gclip = a.scaled = true;
+  a.coef = out;
+  return sgd_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_sgd_master_scaled(void* const* params, const void* const* grads, void* const* bufs,
+                                             const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                             const double* weight_decay, const double* momentum,
+                                             const double* dampening, const int32_t* flags, int32_t nseg,
+                                             float* master, int64_t n, int32_t mode, const float* out,
+                                             void* stream) {
+  SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, master, n, mode,
+            false, nullptr, 0.0, true};
+  a.gclip = a.scaled = true;
+  a.coef = out;
+  return sgd_run(a, as_stream(stream));
 }

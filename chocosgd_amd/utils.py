@@ -265,14 +265,24 @@ def _master_bufs_are_fp32(entries, state):
             raise _not_fp32(buf.dtype)
 
 
-def _sgd_master(param_groups, state, master, write, clip=None):
+def _sgd_master(param_groups, state, master, write, clip=None, ls=None):
     """apply_gradient on the master weights: the batched launch, or the loop above for tensors
     the kernel does not take.  Raises, with nothing changed, where the master does not fit the
     model or a momentum buffer is not fp32.  clip, a (clip_norm, write_clipped, total_norm)
     tuple: global-norm clipping in front, the coefficient in fp32 and the clipped gradient not
-    narrowed before the update."""
+    narrowed before the update.  ls, a (scaler, clip_norm or None, write_clipped) tuple: the
+    loss-scaled step (clip is then None)."""
     entries = master.entries(param_groups)
     plan = _sgd_fill(entries, state, True, master.buffer, master=True)
+    if ls is not None:
+        scaler, max_norm, write_clipped = ls
+        if plan is None:
+            apply_gradient_scaled_loop(param_groups, state, scaler, master, max_norm, write_clipped, write)
+        else:
+            out = scaler.last = plan.gradnorm_scaled(scaler, max_norm, coef_dtype=torch.float32)
+            if not _first_step_overflow(plan, out):
+                plan.run_master(master.buffer, write, scaled=out, write_clipped=write_clipped)
+        return plan
     if clip is None:
         if plan is None:
             apply_gradient_master_loop(param_groups, state, master, write)
@@ -299,19 +309,33 @@ def _sgd_master(param_groups, state, master, write, clip=None):
     return plan
 
 
-def _sgd_batched(entries, state, apply_grad_to_model, flat, write, clip=None):
+def _sgd_batched(entries, state, apply_grad_to_model, flat, write, clip=None, ls=None):
     """One batched launch (per chunk) for `entries`, a list of (group, param) in flat order.
     Returns False, with nothing changed, where a tensor cannot take it.  clip, a (clip_norm,
-    write_clipped, total_norm) tuple: the norm pass in front and the clipped update."""
+    write_clipped, total_norm) tuple: the norm pass in front and the clipped update.  ls, a
+    (scaler, clip_norm or None, write_clipped) tuple: the loss-scaled step; a first step that
+    overflowed launches the pack of the unchanged params alone."""
     plan = _sgd_fill(entries, state, apply_grad_to_model, flat)
     if plan is None:
         return False
-    if clip is None:
+    if ls is not None:
+        _run_scaled(plan, [p for _, p in entries], flat, write, ls)
+    elif clip is None:
         plan.run(flat, grad_mode=not apply_grad_to_model, write=write)
     else:
         plan.run(flat, grad_mode=not apply_grad_to_model, write=write,
                  gclip=plan.gradnorm(clip[0], total_norm=clip[2]), write_clipped=clip[1])
     return True
+
+
+def _run_scaled(plan, params, flat, write, ls):
+    """The loss-scaled norm launch and update of a filled plan (not the master's)."""
+    scaler, max_norm, write_clipped = ls
+    out = scaler.last = plan.gradnorm_scaled(scaler, max_norm)
+    if not _first_step_overflow(plan, out):
+        plan.run(flat, write=write, scaled=out, write_clipped=write_clipped)
+    elif flat is not None:
+        codec.params_pack([p.data for p in params], flat)
 
 
 def _clipped_loop(param_groups, state, apply_grad_to_model, clip):
@@ -331,7 +355,8 @@ def _sgd_fill(entries, state, apply_grad_to_model, flat, master=False):
     """The plan of `entries` with this step's pointers, flags and hyperparameters written (and
     missing momentum buffers created), ready to run; None, with nothing changed, where a tensor
     cannot take the batched kernels.  master: `flat` is the master copy and the momentum buffers
-    are fp32 (plan.run_master follows)."""
+    are fp32 (plan.run_master follows).  plan.created: the state entries whose buffer this call
+    created (a loss-scaled step that overflows takes them back, _first_step_overflow)."""
     if not entries:
         return None
     params = [p for _, p in entries]
@@ -380,7 +405,146 @@ def _sgd_fill(entries, state, apply_grad_to_model, flat, master=False):
         if wrong is not None:  # a 16-bit step's buffer: no silent fall-back to the loop
             raise _not_fp32(wrong)
         return None
+    plan.created = created
     return plan
+
+
+class LossScaler:
+    """Dynamic loss scaling for fp16 (and bf16) models, torch.amp.GradScaler's rule with its
+    work fused into the step: `scaler.scale(loss).backward()`, then apply_gradient / fused_step /
+    dpsgd_step(..., loss_scale=scaler).  The step's norm pass tests the still scaled gradients
+    for an inf or a NaN, the update multiplies by 1 / scale (times the clip coefficient) on the
+    load it does anyway, an overflowed step is skipped on the device, and the scale is backed
+    off or grown there too: no unscale_ pass, no found_inf.item(), no second norm pass.
+
+    Device state: `_scale` (fp32) and `_growth_tracker` (int32), one element each.
+        scale(loss)   loss * scale, a device multiply
+        last          the last step's [total norm of the unscaled gradient, coefficient / scale,
+                      found (1.0: the step was skipped), the scale it ran with], on the device
+        get_scale(), skipped()   read the scale / last[2] on the host: the only calls that sync
+    state_dict / load_state_dict use torch.amp.GradScaler's keys: its checkpoints load."""
+
+    def __init__(self, device, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+        self.device = torch.device(device)
+        self._check(init_scale, growth_factor, backoff_factor, growth_interval)
+        self.growth_factor, self.backoff_factor = float(growth_factor), float(backoff_factor)
+        self.growth_interval = int(growth_interval)
+        self._scale = torch.full((1,), float(init_scale), dtype=torch.float32, device=self.device)
+        self._growth_tracker = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.last = None
+
+    @staticmethod
+    def _check(scale, growth_factor, backoff_factor, growth_interval):
+        s32 = torch.tensor(float(scale), dtype=torch.float32)
+        if not (bool(torch.isfinite(s32)) and float(s32) > 0.0):
+            raise RuntimeError(f"LossScaler: the scale must be finite and > 0 as an fp32 value, got {scale}")
+        if not (1.0 < float(growth_factor) < float("inf")):
+            raise RuntimeError(f"LossScaler: growth_factor must be finite and > 1, got {growth_factor}")
+        if not 0.0 < float(backoff_factor) < 1.0:
+            raise RuntimeError(f"LossScaler: backoff_factor must be in (0, 1), got {backoff_factor}")
+        if int(growth_interval) != growth_interval or int(growth_interval) < 1:
+            raise RuntimeError(f"LossScaler: growth_interval must be an integer >= 1, got {growth_interval}")
+
+    def scale(self, loss):
+        """loss * scale on the device (no sync); the loss keeps its shape and dtype."""
+        return loss * self._scale.reshape(())
+
+    def get_scale(self):
+        return float(self._scale)
+
+    def skipped(self):
+        """Whether the last step overflowed and was skipped (reads `last` on the host)."""
+        return self.last is not None and bool(self.last[2] != 0)
+
+    def state_dict(self):
+        return {"scale": self.get_scale(), "growth_factor": self.growth_factor,
+                "backoff_factor": self.backoff_factor, "growth_interval": self.growth_interval,
+                "_growth_tracker": int(self._growth_tracker)}
+
+    def load_state_dict(self, state_dict):
+        sd = state_dict
+        self._check(sd["scale"], sd["growth_factor"], sd["backoff_factor"], sd["growth_interval"])
+        self.growth_factor, self.backoff_factor = float(sd["growth_factor"]), float(sd["backoff_factor"])
+        self.growth_interval = int(sd["growth_interval"])
+        self._scale.fill_(float(sd["scale"]))
+        self._growth_tracker.fill_(int(sd["_growth_tracker"]))
+
+
+def apply_gradient_scaled_loop(param_groups, state, scaler, master=None, clip_norm=None, write_clipped=False,
+                               write=True):
+    """The loss-scaled step (apply_gradient(loss_scale=)) as one torch op per line: the path CPU
+    tensors, and anything the batched kernels do not take, keep.  The lines are the kernels'
+    (include/choco_codec.h, dynamic loss scaling); the state update is torch._amp_update_scale_,
+    the update apply_gradient_master_loop(grads32=) or apply_gradient_loop, and the skip is a
+    host branch.  Returns [total, coefficient / scale, found, scale] (also scaler.last)."""
+    if master is not None:
+        params = [p for _, p in master.entries(param_groups)]
+    else:
+        params = [p for group in param_groups for p in group["params"]]
+    grads = [p.grad for p in params if p.grad is not None]
+    if not grads:
+        return None
+    dev = grads[0].device
+    cd = torch.float32 if master is not None else codec.common_grad_dtype(g.dtype for g in grads)
+    scale = scaler._scale.reshape(()).clone()
+    inv = scale.double().reciprocal().float()
+    ssq = torch.stack([g.detach().double().pow(2).sum().to(dev) for g in grads]).sum()
+    found = (~torch.isfinite(ssq)).float()
+    total = (ssq.sqrt().float() * inv).to(cd)
+    c = torch.ones((), dtype=cd, device=dev) if clip_norm is None else _clip_coef32(total, clip_norm)
+    gc = c.float() * inv
+    out = scaler.last = torch.stack([total.float(), gc, found, scale])
+    torch._amp_update_scale_(scaler._scale, scaler._growth_tracker, found.reshape(1), scaler.growth_factor,
+                             scaler.backoff_factor, scaler.growth_interval)
+    if bool(found):
+        return out
+    if master is not None:
+        grads32 = [None if p.grad is None else p.grad.data.float() * gc for p in params]
+        apply_gradient_master_loop(param_groups, state, master, write, grads32=grads32)
+        if write_clipped:
+            for p, g in zip(params, grads32):
+                if g is not None:
+                    p.grad.data.copy_(g)
+        return out
+    params = [p for p in params if p.grad is not None]
+    saved = None if write_clipped else [p.grad.data.clone() for p in params]
+    for p in params:
+        p.grad.data.copy_(p.grad.data.float() * gc)  # one fp32 product, narrowed once
+    apply_gradient_loop(param_groups, state, True)
+    if saved is not None:
+        for p, g in zip(params, saved):
+            p.grad.data.copy_(g)
+    return out
+
+
+def _first_step_overflow(plan, out):
+    """SGD_F_FIRST is decided on the host, from a missing momentum buffer: a step skipped on the
+    device would leave a zero buffer that the next step reads as initialised (wrong whenever
+    dampening != 0).  So while a step creates a buffer, `found` is read on the host -- the one
+    sync of the loss-scaled path, gone from the first taken step on -- and on overflow the
+    created buffers are taken back.  True: launch no update."""
+    if not plan.created or not bool(out[2] != 0):
+        return False
+    for param_state in plan.created:
+        del param_state["momentum_buffer"]
+    plan.created = []
+    return True
+
+
+def _scale_args(what, loss_scale, clip_norm=None, write_clipped=False, total_norm=None, apply_grad_to_model=True):
+    """(clip, ls) of a step: without loss_scale its _clip_args tuple and None; with it None --
+    the clip is the scaled norm launch's own -- and (scaler, clip_norm or None, write_clipped)."""
+    if loss_scale is None:
+        return _clip_args(what, clip_norm, write_clipped, total_norm, apply_grad_to_model), None
+    if not isinstance(loss_scale, LossScaler):
+        raise RuntimeError(f"{what}: loss_scale must be a LossScaler")
+    if not apply_grad_to_model:
+        raise RuntimeError(f"{what}: loss_scale updates the model; apply_grad_to_model=False (grad mode) has no "
+                           "loss-scaled variant")
+    if total_norm is not None:
+        raise RuntimeError(f"{what}: loss_scale with a pinned total_norm: there is no norm pass to detect an "
+                           "overflow from")
+    return None, (loss_scale, None if clip_norm is None else float(clip_norm), bool(write_clipped))
 
 
 def _clip_args(what, clip_norm, write_clipped=False, total_norm=None, apply_grad_to_model=True):
@@ -396,7 +560,7 @@ def _clip_args(what, clip_norm, write_clipped=False, total_norm=None, apply_grad
 
 
 def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None, master=None, clip_norm=None,
-                   write_clipped=False, total_norm=None):
+                   write_clipped=False, total_norm=None, loss_scale=None):
     """optim/utils.py:13-47: weight decay, momentum with dampening, optional Nesterov, then
     p -= lr * d_p (apply_grad_to_model) or d_p left as the gradient.  Missing
     state[p]["momentum_buffer"] entries are created.  fp32 / bf16 / fp16 ROCm tensors take ONE
@@ -425,21 +589,33 @@ def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None,
     (fp64 accumulation over all elements); total_norm (a tensor or a float) pins it.
     p.grad is not written unless write_clipped (apply_grad_to_model only), which stores the
     clipped gradient as torch's call leaves it.  With master the coefficient is computed in
-    fp32 and the clipped gradient is not narrowed before the update."""
-    clip = _clip_args("apply_gradient", clip_norm, write_clipped, total_norm, apply_grad_to_model)
+    fp32 and the clipped gradient is not narrowed before the update.
+
+    loss_scale (a LossScaler; apply_grad_to_model only, no total_norm): the gradients are
+    those of scaler.scale(loss).  The norm pass detects an inf / NaN from its fp64 sum of
+    squares, the update multiplies g by (clip coefficient) / scale on the load it does anyway
+    (clip_norm None: by 1 / scale), an overflowed step changes nothing -- flat_out receives the
+    unchanged parameters -- and the scale is backed off or grown on the device; write_clipped
+    (with or without clip_norm) stores the unscaled, clipped gradient.  Nothing is read on the
+    host, except while a step creates momentum buffers (the first taken step): `found` is then
+    read, and an overflowed step leaves no buffer behind.  loss_scale=None is the code path
+    above, launch for launch."""
+    clip, ls = _scale_args("apply_gradient", loss_scale, clip_norm, write_clipped, total_norm, apply_grad_to_model)
     if master is not None:
         if not apply_grad_to_model:
             raise RuntimeError("apply_gradient(master=...) updates the model: apply_grad_to_model=False has no "
                                "master variant")
         if flat_out is not None:
             raise RuntimeError("apply_gradient(master=...): the master buffer is the flat copy; flat_out has no use")
-        _sgd_master(param_groups, state, master, write=True, clip=clip)
+        _sgd_master(param_groups, state, master, write=True, clip=clip, ls=ls)
         return
     entries = [(group, p) for group in param_groups for p in group["params"]]
     flat = getattr(flat_out, "buffer", flat_out)
-    if _sgd_batched(entries, state, apply_grad_to_model, flat, write=True, clip=clip):
+    if _sgd_batched(entries, state, apply_grad_to_model, flat, write=True, clip=clip, ls=ls):
         return
-    if clip is None:
+    if ls is not None:
+        apply_gradient_scaled_loop(param_groups, state, ls[0], None, ls[1], ls[2])
+    elif clip is None:
         apply_gradient_loop(param_groups, state, apply_grad_to_model)
     else:
         _clipped_loop(param_groups, state, apply_grad_to_model, clip)
@@ -468,7 +644,8 @@ def recover_params(param_groups, param_names, rank=None, neighbor_hat_params=Non
 
 
 def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_params, neighbors_info,
-               consensus_stepsize, rank, defer_receive=False, state=None, master=None, clip_norm=None):
+               consensus_stepsize, rank, defer_receive=False, state=None, master=None, clip_norm=None,
+               loss_scale=None):
     """ParallelCHOCO_V.step after apply_gradient (parallel_choco_v.py:115-155), with the
     consensus step fused into the compressor's first pass: recover_params, then
     compress (x += gamma * (memory - x_hat_i) and d = x_new - x_hat_i in one pass), sync,
@@ -498,9 +675,16 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
 
     clip_norm (needs state; conf.rnn_clip): apply_gradient(clip_norm=...)'s global-norm
     clipping in front of the step's update.  Without state the caller has run apply_gradient
-    already and there is nothing left to clip: that raises."""
+    already and there is nothing left to clip: that raises.
+
+    loss_scale (a LossScaler; needs state): apply_gradient(loss_scale=...)'s loss-scaled
+    update.  A step whose gradients overflowed leaves x as it was and goes on: the consensus
+    step, the compressor and the exchange run on the unchanged x."""
     flatten_params = None
-    clip = _clip_args("fused_step", clip_norm)
+    clip, ls = _scale_args("fused_step", loss_scale, clip_norm)
+    if ls is not None and state is None:
+        raise RuntimeError("fused_step(loss_scale=...) unscales in the step's own apply_gradient: pass "
+                           "state=optimizer.state (without it the caller's apply_gradient has already run)")
     if clip is not None and state is None:
         raise RuntimeError("fused_step(clip_norm=...) clips in front of the step's own apply_gradient: pass "
                            "state=optimizer.state (without it the caller's apply_gradient has already run)")
@@ -509,10 +693,10 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
             raise RuntimeError("fused_step(master=...) runs apply_gradient itself: pass state=optimizer.state")
         if master.param_names != list(param_names):
             raise RuntimeError("fused_step(master=...): the master weights were built for other param_names")
-        _sgd_master(param_groups, state, master, write=False, clip=clip)
+        _sgd_master(param_groups, state, master, write=False, clip=clip, ls=ls)
         flatten_params = master.flat
     elif state is not None:
-        flatten_params = _sgd_packed(param_groups, param_names, state, clip)
+        flatten_params = _sgd_packed(param_groups, param_names, state, clip, ls)
     if defer_receive:
         if flatten_params is None:
             params, flatten_params = recover_params(param_groups, param_names, get_hat_params=False)
@@ -540,16 +724,18 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
     return sync_buffer
 
 
-def _sgd_packed(param_groups, param_names, state, clip=None):
+def _sgd_packed(param_groups, param_names, state, clip=None, ls=None):
     """fused_step(state=...): apply_gradient and the pack of the new params in one launch.
     Returns the flat TensorBuffer, or None after the per-tensor loop has updated the params
     (tensors the batched kernel does not take: recover_params packs them as before)."""
     entries = step_entries(param_groups, param_names, "fused_step(state=...)")
     dev = entries[0][1].device
     flat = torch.empty(sum(p.numel() for _, p in entries), dtype=torch.float32, device=dev)
-    if dev.type == "cuda" and _sgd_batched(entries, state, True, flat, write=False, clip=clip):
+    if dev.type == "cuda" and _sgd_batched(entries, state, True, flat, write=False, clip=clip, ls=ls):
         return TensorBuffer.from_flat(flat, [p.size() for _, p in entries])
-    if clip is None:
+    if ls is not None:
+        apply_gradient_scaled_loop(param_groups, state, ls[0], None, ls[1], ls[2])
+    elif clip is None:
         apply_gradient_loop(param_groups, state, True)
     else:
         _clipped_loop(param_groups, state, True, clip)
@@ -600,10 +786,12 @@ def weighted_sum(buffers, weights):
     return sum([b * w for b, w in zip(buffers, weights)])
 
 
-def dpsgd_step_loop(param_groups, param_names, state, aggregator, clip=None):
+def dpsgd_step_loop(param_groups, param_names, state, aggregator, clip=None, ls=None):
     """dpsgd_step as the reference's op sequence (sgd.py:94-121), one torch op per line: the path
     CPU tensors, and anything the batched kernels do not take, keep."""
-    if clip is None:
+    if ls is not None:
+        apply_gradient_scaled_loop(param_groups, state, ls[0], None, ls[1], ls[2])
+    elif clip is None:
         apply_gradient_loop(param_groups, state, True)
     else:
         _clipped_loop(param_groups, state, True, clip)
@@ -613,7 +801,8 @@ def dpsgd_step_loop(param_groups, param_names, state, aggregator, clip=None):
     return get_n_bits(flatten_params.buffer)
 
 
-def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, master=None, clip_norm=None):
+def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, master=None, clip_norm=None,
+               loss_scale=None):
     """The decentralized branch of SGD.step (sgd.py:94-121), plain D-PSGD: apply_gradient fused
     with the pack of the new params (one launch; the params themselves are not written yet),
     the exchange of the flat fp32 buffer (_agg(op="get_raw_sync_data")), and ONE mix launch
@@ -627,15 +816,19 @@ def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, mas
     swapped.
 
     clip_norm (conf.rnn_clip): apply_gradient(clip_norm=...)'s global-norm clipping in front of
-    the update."""
-    clip = _clip_args("dpsgd_step", clip_norm)
+    the update.
+
+    loss_scale (a LossScaler): apply_gradient(loss_scale=...)'s loss-scaled update.  A worker
+    whose gradients overflowed keeps its x and still exchanges and mixes it: each worker skips
+    on its own."""
+    clip, ls = _scale_args("dpsgd_step", loss_scale, clip_norm)
     entries = step_entries(param_groups, param_names, "dpsgd_step")
     params = [p for _, p in entries]
     dev = params[0].device
     if master is not None:
         if master.param_names != list(param_names):
             raise RuntimeError("dpsgd_step(master=...): the master weights were built for other param_names")
-        plan = _sgd_master(param_groups, state, master, write=False, clip=clip)
+        plan = _sgd_master(param_groups, state, master, write=False, clip=clip, ls=ls)
         flat = master.buffer
         if plan is None:  # the loop ran: the reference's op sequence on the master
             master.flat.buffer = aggregator._agg(flat, op="weighted")
@@ -649,8 +842,10 @@ def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, mas
     flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
     plan = _sgd_fill(entries, state, True, flat)
     if plan is None:
-        return dpsgd_step_loop(param_groups, param_names, state, aggregator, clip)
-    if clip is None:
+        return dpsgd_step_loop(param_groups, param_names, state, aggregator, clip, ls)
+    if ls is not None:
+        _run_scaled(plan, params, flat, False, ls)
+    elif clip is None:
         plan.run(flat, grad_mode=False, write=False)
     else:
         plan.run(flat, grad_mode=False, write=False, gclip=plan.gradnorm(clip[0]))

@@ -816,6 +816,73 @@ int choco_params_sgd_master_gclip(void* const* params, const void* const* grads,
                                   float* master, int64_t n, int32_t mode, const float* coef,
                                   void* stream);
 
+/* ------------------------------------------- dynamic loss scaling
+ * torch.amp.GradScaler's unscale_, inf/NaN check, skipped step and scale update for an fp16
+ * (or bf16) model, fused into the norm pass and the update above: no pass that rewrites the
+ * gradients, no second norm pass for the clip, no host sync.  The gradients the caller
+ * hands in are still multiplied by the loss scale.  With scale = *scale_state (DEVICE, one
+ * float), CD = coef_dtype as above (fp32 for the master update), every line one rounding:
+ *     inv   = (float)(1.0 / (double)scale)
+ *     S     = the fp64 sum of squares of the raw gradients, choco_params_gradnorm's own
+ *     found = !isfinite(S)                  S is non-finite exactly when a gradient element
+ *                                           is: squares are non-negative (no inf - inf) and an
+ *                                           fp64 sum of finite fp32 squares cannot overflow.
+ *                                           The fp32 total is NOT tested: huge is not overflow
+ *     total = rnd_CD((float)sqrt(S) * inv)  the norm of the unscaled gradient
+ *     c     = choco_params_gradnorm's lines from total and max_norm;  has_clip == 0: c = 1
+ *     gc    = c * inv                       an fp32 product, not narrowed to CD
+ *     out   = [total, gc, found ? 1.0f : 0.0f, scale]
+ * then torch's _amp_update_scale_ on the device state, in the same launch:
+ *     found:  *scale_state = (float)((double)scale * backoff);  *growth_tracker = 0
+ *     else:   k = *growth_tracker + 1;  k == interval: s = (float)((double)scale * growth),
+ *             stored if finite, and *growth_tracker = 0;  otherwise *growth_tracker = k
+ *
+ * choco_params_gradnorm_scaled: choco_params_gradnorm's arguments without total_in (a
+ *   pinned total has no norm pass to detect an overflow from), and scale_state (DEVICE
+ *   float), growth_tracker (DEVICE int32), growth, backoff, interval, has_clip (0: max_norm
+ *   is not used), out (DEVICE, FOUR floats).  The same norm pass ("param_sqnorm_kernel")
+ *   and ONE launch of "param_gradnorm_scaled_total_kernel", an instantiation of the total
+ *   kernel with the same staging and the same ordered additions: workspace and launches
+ *   are choco_params_gradnorm_workspace_size(nseg, n) and
+ *   choco_params_gradnorm_launches(nseg, 0).  norms (or NULL) receives the per-tensor norms
+ *   of the RAW gradients.  Rejected in addition to choco_params_gradnorm's unpinned list: a
+ *   NULL or misaligned scale_state or growth_tracker; growth not finite or <= 1; backoff
+ *   outside (0, 1); interval < 1; has_clip other than 0 or 1.  max_norm is checked only
+ *   with has_clip.
+ *
+ * choco_params_sgd_scaled / choco_params_sgd_master_scaled: choco_params_sgd_gclip /
+ *   choco_params_sgd_master_gclip with out (the four floats above) in place of coef.  The
+ *   kernels use gc = out[1] exactly as the gclip kernels use the clip coefficient
+ *   (g = rnd_DT(gc * g); master: g = gc * g in fp32, not narrowed; WRITE_CLIPPED stores the
+ *   product narrowed: the unscaled, clipped gradient) and read out[2] as one uniform load
+ *   per workgroup.  out[2] != 0 skips the step on the device: the master kernel returns
+ *   before it touches anything; the plain kernel treats every tensor as a NOGRAD one
+ *   (flat = p; no parameter, buffer or gradient is written) and returns at once without a
+ *   flat side.  Apply mode only: CHOCO_SGD_MODE_GRAD is rejected, as are ADD_FLAT and a
+ *   NULL or misaligned out, on top of the gclip entry points' lists.  Launches:
+ *   choco_params_sgd_launches(nseg) of "param_sgd_scaled_kernel" /
+ *   "param_sgd_master_scaled_kernel", instantiations of their own: no other kernel
+ *   carries the skip test.  CHOCO_SGD_F_FIRST is decided by the host before the launch: a
+ *   caller whose step creates momentum buffers reads out[2] first (the one host read) and
+ *   does not launch a skipped first step. */
+int choco_params_gradnorm_scaled(const void* const* grads, const int64_t* lens,
+                                 const int32_t* dtypes, const int32_t* flags, int32_t nseg,
+                                 int64_t n, double max_norm, int32_t coef_dtype, float* scale_state,
+                                 int32_t* growth_tracker, double growth, double backoff,
+                                 int32_t interval, int32_t has_clip, float* out, float* norms,
+                                 void* ws, size_t ws_bytes, void* stream);
+int choco_params_sgd_scaled(void* const* params, const void* const* grads, void* const* bufs,
+                            const int64_t* lens, const int32_t* dtypes, const double* lr,
+                            const double* weight_decay, const double* momentum,
+                            const double* dampening, const int32_t* flags, int32_t nseg, float* flat,
+                            int64_t n, int32_t mode, const float* out, void* stream);
+int choco_params_sgd_master_scaled(void* const* params, const void* const* grads, void* const* bufs,
+                                   const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                   const double* weight_decay, const double* momentum,
+                                   const double* dampening, const int32_t* flags, int32_t nseg,
+                                   float* master, int64_t n, int32_t mode, const float* out,
+                                   void* stream);
+
 /* ------------------------------------------- neighbour-weighted model mix
  * The dense line three decentralized optimizers of the reference share,
  *     sum([hat_r.buffer * neighbors_info[r] for r, hat_r in ...])
