@@ -38,6 +38,20 @@ TOPK_DIAG_BOUNDS_N = 16          # int64
 TOPK_DIAG_BOUNDS_K = 24          # int64
 TOPK_DIAG_BOUNDS_VALID = 32
 TOPK_STATUS_POLL_TIMEOUT = 1  # CHOCO_TOPK_STATUS_POLL_TIMEOUT
+# segmented workspaces (diagnostics): CHOCO_SEG_*
+SEG_WIN_STRIDE = 32           # bytes per segment window; uint32 words at the byte offsets below
+SEG_WIN_LO = 0
+SEG_WIN_SH = 4
+SEG_WIN_VALID = 8
+SEG_WIN_T_PREV = 16
+SEG_WIN_D_PREV = 20
+SEG_WIN_CAND = 24
+SEG_WIN_TRUST = 28
+SEG_INFO_STRIDE = 32          # bytes per segment info row; word indices below
+SEG_INFO_LO = 0
+SEG_INFO_SH = 1
+SEG_INFO_MODE = 6
+SEG_SHADOW_OFFSET = 64        # uint64
 
 _c_i32, _c_i64, _c_u64, _c_f32, _c_f64 = (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
                                            ctypes.c_float, ctypes.c_double)
@@ -64,6 +78,8 @@ SIGNATURES = {
     "choco_topk_segmented_plan": (_c_i64, [_p_i64, _c_i32, _c_f64, _p_i64]),
     "choco_topk_segmented_workspace_size": (_c_sz, [_p_i64, _c_i32]),
     "choco_topk_compress_segmented": (_c_i32, [_vp, _vp, _vp, _p_i64, _c_i32, _vp, _vp, _vp, _c_sz, _vp]),
+    "choco_topk_segmented_diag_layout": (_c_i32, [_p_i64, _c_i32, _p_i64, _p_i64]),
+    "choco_topk_segmented_host_state": (_c_i32, [_vp, _p_i64, _c_i32, ctypes.POINTER(_c_u64)]),
     "choco_randk_workspace_size": (_c_sz, [_c_i64]),
     "choco_randk_compress": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _c_u64, _c_u64, _c_i32, _vp, _vp, _vp, _c_sz, _vp]),
     "choco_randk_compress_segmented": (_c_i32, [_vp, _vp, _vp, _p_i64, _c_i32, _c_u64, _c_u64, _c_i32, _vp, _vp, _vp,

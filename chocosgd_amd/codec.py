@@ -1705,5 +1705,57 @@ def topk_workspace_word(off, dev=None, plan=None):
     return int(ws[off:off + 4].view(torch.int32).item())
 
 
+SEG_WIN_WORDS = ("lo", "sh", "valid", "pad", "t_prev", "d_prev", "cand", "trust")
+SEG_HOST_WORDS = ("calls", "last_flag", "cold_left", "backoff", "clean", "last_checks", "last_misses", "flag")
+
+
+def seg_diag_layout(plan):
+    """Diagnostic: byte offsets (win, info) of the per-segment windows and info rows in
+    `plan`'s workspace (include/choco_codec.h CHOCO_SEG_*).  Host only."""
+    win, info = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(lib().choco_topk_segmented_diag_layout(plan.plan_host, plan.nseg, ctypes.byref(win),
+                                                      ctypes.byref(info)), "choco_topk_segmented_diag_layout")
+    return int(win.value), int(info.value)
+
+
+def _seg_rows(plan, off, stride, dev):
+    dev = torch.device(dev) if dev is not None else torch.device("cuda", torch.cuda.current_device())
+    ws = plan.workspace(dev)
+    torch.cuda.current_stream(dev).synchronize()
+    rows = ws[off:off + stride * plan.nseg].cpu().numpy().view("<u4")
+    return rows.reshape(plan.nseg, stride // 4).copy()
+
+
+def seg_windows(plan, dev=None):
+    """Diagnostic: the (nseg, 8) uint32 array of `plan`'s warm windows, columns SEG_WIN_WORDS
+    (rows of single-tile and flat-pipeline segments stay zero).  Synchronises the stream."""
+    return _seg_rows(plan, seg_diag_layout(plan)[0], _lib.SEG_WIN_STRIDE, dev)
+
+
+def seg_info(plan, dev=None):
+    """Diagnostic: the (nseg, 8) uint32 array of `plan`'s info rows (after a warm call: word
+    _lib.SEG_INFO_LO / SEG_INFO_SH the window used, SEG_INFO_MODE how it went).  Synchronises."""
+    return _seg_rows(plan, seg_diag_layout(plan)[1], _lib.SEG_INFO_STRIDE, dev)
+
+
+def seg_shadow(plan, dev=None):
+    """Diagnostic: the cold calls' window-check counter of `plan`'s workspace as (misses,
+    checks) (CHOCO_SEG_SHADOW_OFFSET).  Synchronises."""
+    lo = topk_workspace_word(_lib.SEG_SHADOW_OFFSET, dev=dev, plan=plan) & 0xFFFFFFFF
+    hi = topk_workspace_word(_lib.SEG_SHADOW_OFFSET + 4, dev=dev, plan=plan) & 0xFFFFFFFF
+    return hi, lo
+
+
+def seg_host_state(plan, dev=None):
+    """Diagnostic: the host's warm / cold bookkeeping of `plan`'s workspace on this stream
+    as a dict over SEG_HOST_WORDS (all zeros before the first call).  Host memory only: no
+    synchronisation, no copy."""
+    dev = torch.device(dev) if dev is not None else torch.device("cuda", torch.cuda.current_device())
+    out = (ctypes.c_uint64 * 8)()
+    _lib.check(lib().choco_topk_segmented_host_state(_ptr(plan.workspace(dev)), plan.plan_host, plan.nseg, out),
+               "choco_topk_segmented_host_state")
+    return dict(zip(SEG_HOST_WORDS, (int(v) for v in out)))
+
+
 def is_pow2_minus1(s):
     return s >= 1 and (s + 1) & s == 0 and int(math.log2(s + 1)) <= 16

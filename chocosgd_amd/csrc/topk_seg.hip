@@ -110,10 +110,22 @@ CHOCO_DEV SegWin seg_win(uint32_t lo, uint32_t sh, uint32_t T, const SegWin& old
                          uint32_t trust = 0u) {
   return SegWin{lo, sh, 1u, 0u, T, (old.valid && old.tprev) ? T - old.tprev : 0u, cand, trust};
 }
+static_assert(sizeof(SegWin) == CHOCO_SEG_WIN_STRIDE, "one window per documented stride");
+static_assert(offsetof(SegWin, lo) == CHOCO_SEG_WIN_LO && offsetof(SegWin, sh) == CHOCO_SEG_WIN_SH &&
+                  offsetof(SegWin, valid) == CHOCO_SEG_WIN_VALID && offsetof(SegWin, tprev) == CHOCO_SEG_WIN_T_PREV &&
+                  offsetof(SegWin, dprev) == CHOCO_SEG_WIN_D_PREV && offsetof(SegWin, cand) == CHOCO_SEG_WIN_CAND &&
+                  offsetof(SegWin, trust) == CHOCO_SEG_WIN_TRUST,
+              "window fields at the documented offsets");
 
 // info[8 s + i]: 0 b1 (cold), 1 rank inside b1 (cold), 2 T, 3 bin of the k-th key
 // (S3a), 4 rank inside that bin, 5 ties at T to take, 6 mode (0 select, 1 window
-// missed: exact fallback in S4, 2 take every element)
+// missed: exact fallback in S4, 2 take every element).  Warm calls: 0 / 1 the window used
+// (lo, sh), 3 / 4 the k-th key's window bin and the rank inside it, 6 the SegMode.
+constexpr int kInfoWords = 8;
+constexpr int kInfoLo = 0, kInfoSh = 1, kInfoMode = 6;  // (warm calls)
+static_assert(kInfoWords * 4 == CHOCO_SEG_INFO_STRIDE && kInfoLo == CHOCO_SEG_INFO_LO && kInfoSh == CHOCO_SEG_INFO_SH &&
+                  kInfoMode == CHOCO_SEG_INFO_MODE,
+              "info words at the documented places");
 struct SegWs {
   uint32_t *hist1, *hist2, *hist3, *info, *tilecnt, *tcount;
   float* cval;
@@ -138,6 +150,7 @@ struct SegLayout {
 constexpr int kTileList = 4;  // warm: a tile's distinct keys in the k-th key's window bin kept for S4w
 
 constexpr size_t kSegShadowOffset = 64;  // in the header: the cold calls' 64-bit window-check counter
+static_assert(kSegShadowOffset == CHOCO_SEG_SHADOW_OFFSET, "shadow counter at the documented offset");
 static SegLayout seg_layout(int nseg, int64_t ntile) {
   SegLayout L{};
   size_t o = 256;  // [0, 256): the sticky status word (CHOCO_TOPK_STATUS_OFFSET) of the whole call, the
@@ -145,7 +158,7 @@ static SegLayout seg_layout(int nseg, int64_t ntile) {
   L.off_h1 = o;   o += align_up((size_t)nseg * kH * 4, 256);
   L.off_h2 = o;   o += align_up((size_t)nseg * kH * 4, 256);
   L.off_h3 = o;   o += align_up((size_t)nseg * 512 * 4, 256);
-  L.off_info = o; o += align_up((size_t)nseg * 8 * 4, 256);
+  L.off_info = o; o += align_up((size_t)nseg * kInfoWords * 4, 256);
   L.off_cnt = o;  o += align_up((size_t)ntile * 4, 256);
   L.off_out = o;  o += align_up((size_t)ntile * 8, 256);
   L.off_cval = o; o += align_up((size_t)ntile * kSegTile * 4, 256);
@@ -611,8 +624,10 @@ __global__ __launch_bounds__(kS3Threads) void seg_fine_kernel(
 // over hist[kH] of bins of 2^shb keys from `base`, with `above` keys above the
 // range, the keys at count levels k + delta and k - delta (delta = 0.03 k +
 // 4 sqrt(k) + 8: the k-th key of a small segment moves by many ranks from one
-// call to the next), bin-rounded outward; a window wider than 2048 << kWinShMax
-// keys is centred on T instead.
+// call to the next), bin-rounded outward and never past the histogram's own range
+// (a level outside it lands on the range's edge).  A window wider than 2048 <<
+// kWinShMax keys would be centred on T instead: a guard only, both edges come from one
+// histogram of 2048 bins of at most 2^kWinShMax keys (tests/_seg_controller.py).
 constexpr int kWinPer = kH / kS3Threads;  // hist bins per thread of seg_next_window
 CHOCO_DEV void seg_next_window_v(const uint32_t (&hv)[kWinPer], uint32_t base, uint32_t shb, uint32_t above,
                                  uint32_t k, uint32_t T, const SegWin& old, SegWin* __restrict__ out,
@@ -675,7 +690,7 @@ CHOCO_DEV void seg_next_window_v(const uint32_t (&hv)[kWinPer], uint32_t base, u
 // previous call prepared (still in win[s]) would have held this call's T_s, and adds
 // (miss << 32) | 1 to a 64-bit device counter; S4 copies it to pinned host memory once per
 // call (a system-scope atomic per segment took S3b 5 -> 49 us); the host ends a cold run
-// once two calls' worth of checks came without a miss.
+// once kSegShadowExit (one) cold call's worth of checks came without a miss.
 __global__ __launch_bounds__(kS3Threads) void seg_count_kernel(
     const int64_t* __restrict__ trows, int nseg, uint32_t* __restrict__ hist2, const uint32_t* __restrict__ hist3,
     uint32_t* __restrict__ info, const uint32_t* __restrict__ tilecnt, const float* __restrict__ cval,
@@ -785,11 +800,11 @@ __global__ __launch_bounds__(kS3Threads) void seg_bin_kernel(
   else if (!w.valid || bc[2] < rank) mode = kSegMissed;  // T below the window (or none)
   else if (b2 == (uint32_t)(kH - 1)) mode = kSegMissedHigh;  // T in the window's clamped top bin
   if (c.j == 0 && tid == 0) {
-    info[8 * c.s + 0] = lo;
-    info[8 * c.s + 1] = sh;
+    info[8 * c.s + kInfoLo] = lo;
+    info[8 * c.s + kInfoSh] = sh;
     info[8 * c.s + 3] = b2;
     info[8 * c.s + 4] = bc[1];  // rank of the k-th key inside bin b2
-    info[8 * c.s + 6] = mode;
+    info[8 * c.s + kInfoMode] = mode;
   }
   uint32_t gt = 0, nin = 0;
   if (mode == kSegSelect) {  // workgroup-uniform
@@ -1013,8 +1028,8 @@ __global__ __launch_bounds__(kS4Threads, 7) void seg_emit_w_kernel(
   // ---- one round trip: the segment's info, every tile's counts and kept keys, this
   // tile's count and first 256 candidates
   const uint32_t* I = info + 8 * c.s;
-  const uint32_t mode = I[6];
-  const uint32_t lo = I[0], sh = I[1], b2 = I[3], rb = I[4];
+  const uint32_t mode = I[kInfoMode];
+  const uint32_t lo = I[kInfoLo], sh = I[kInfoSh], b2 = I[3], rb = I[4];
   uint32_t tg[kS4Per], tn[kS4Per];
   uint2 kk[kS4Per][kTileList];  // {key, count}
 #pragma unroll
@@ -1524,6 +1539,37 @@ CHOCO_API int64_t choco_topk_segmented_plan(const int64_t* seg_off_host, int32_t
     }
   }
   return out;
+}
+
+// Diagnostics (read-only): where win[] and info[] lie in the plan's workspace.
+CHOCO_API int choco_topk_segmented_diag_layout(const int64_t* plan_host, int32_t nseg, int64_t* win_off,
+                                               int64_t* info_off) {
+  CHOCO_REQUIRE(plan_host && nseg > 0 && win_off && info_off, "null pointer argument");
+  const SegLayout L = seg_layout(nseg, plan_tiles(plan_host));
+  *win_off = (int64_t)L.off_win;
+  *info_off = (int64_t)L.off_info;
+  return CHOCO_OK;
+}
+
+// Diagnostics (read-only, host memory only): the warm / cold bookkeeping of workspace `ws`.
+CHOCO_API int choco_topk_segmented_host_state(const void* ws, const int64_t* plan_host, int32_t nseg,
+                                              uint64_t out[8]) {
+  CHOCO_REQUIRE(ws && plan_host && nseg > 0 && out, "null pointer argument");
+  for (int i = 0; i < 8; ++i) out[i] = 0u;
+  const SegLayout L = seg_layout(nseg, plan_tiles(plan_host));
+  std::lock_guard<std::mutex> g(g_seg_mu);
+  const auto it = g_seg.find(static_cast<const char*>(ws) + L.off_win);  // (seg_claim_warm's key)
+  if (it == g_seg.end()) return CHOCO_OK;
+  const SegState& S = it->second;
+  out[0] = S.calls;
+  out[1] = S.last_flag;
+  out[2] = S.cold_left;
+  out[3] = S.backoff;
+  out[4] = S.clean;
+  out[5] = S.last_checks;
+  out[6] = S.last_misses;
+  out[7] = S.flag ? __atomic_load_n(S.flag, __ATOMIC_ACQUIRE) : 0u;
+  return CHOCO_OK;
 }
 
 static int64_t rk_base_of(const int64_t* plan_host, int32_t nseg) {

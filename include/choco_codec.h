@@ -164,7 +164,9 @@ int choco_topk_compress_accumulate(const float* x, const float* xhat, int64_t n,
  * segment order, indices GLOBAL (segment offset added in integer arithmetic --
  * the reference adds it in fp32, sparsification.py:76).  Every segment of up to
  * 16M elements is cut into 16K-element tiles and ALL of them are selected in the
- * same five launches (topk_seg.hip); longer segments run the flat pipeline.
+ * same launches (topk_seg.hip): five on a cold call, which reads the input twice (a
+ * workspace's first call, and the calls of a cold run), three on a warm call, which reads
+ * it once inside the windows the previous call left; longer segments run the flat pipeline.
  * choco_topk_segmented_plan fills a HOST int64 plan of
  * choco_topk_segmented_plan_len(seg_off, nseg) entries from the HOST table
  * seg_off[nseg+1]: nseg rows of 8 {off, len, k_s, out_off, first tile, tiles, ., .}
@@ -185,6 +187,48 @@ int choco_topk_compress_segmented(const float* x, const float* xhat, const int64
                                   const int64_t* plan_host, int32_t nseg,
                                   float* out_val, int32_t* out_idx,
                                   void* ws, size_t ws_bytes, void* stream);
+/* Segmented workspaces, diagnostics (read-only; nothing here is on the hot path).  Each
+ * multi-tile batched segment s carries a warm window of CHOCO_SEG_WIN_STRIDE bytes at
+ * win_off + CHOCO_SEG_WIN_STRIDE s, uint32 words at the CHOCO_SEG_WIN_* byte offsets:
+ *   LO / SH   next call's candidates are the keys >= LO, binned by (key - LO) >> SH (SH <= 9);
+ *   VALID     0 until a call has written the window;
+ *   T_PREV    the exact k_s-th key of the call that wrote it (0 after a take-all call), D_PREV
+ *             its move against the call before (int32 bits);
+ *   CAND      the drift that call proposed (int32 bits), TRUST the calls in a row whose proposed
+ *             drift predicted the k-th key better than the previous key did (at most 15; from
+ *             2 on the window is moved by the drift).
+ * and a row of CHOCO_SEG_INFO_STRIDE bytes at info_off + CHOCO_SEG_INFO_STRIDE s, uint32 words:
+ * after a warm call, word CHOCO_SEG_INFO_LO / _SH hold the window the call used and word
+ * CHOCO_SEG_INFO_MODE how it went (0 selected inside the window, 1 the k-th key was below
+ * the window, 3 above it -- both selected exactly and counted at CHOCO_TOPK_FALLBACKS_OFFSET --
+ * 2 every element taken).  CHOCO_SEG_SHADOW_OFFSET: a uint64 in the workspace header, added
+ * to by every cold call, per multi-tile segment, (1 << 32 if the window the previous call
+ * left would not have held this call's k-th key) + 1.
+ * choco_topk_segmented_diag_layout returns win_off and info_off of the plan's workspace.
+ * choco_topk_segmented_host_state copies the host's warm / cold bookkeeping of the
+ * workspace `ws` (the base pointer passed to the compress calls) into out[8]: calls made,
+ * the call at which the miss flag was last seen, cold calls left in the run, the backoff
+ * (length of the last cold run as exits have halved it), clean (cold calls' checks without
+ * a miss), the shadow counter's checks and misses when last read, and the pinned miss-flag
+ * word as it stands (1: a warm call's window missed and no later call has seen it yet).
+ * All zeros for a workspace no call was made on; it creates no record and touches no GPU. */
+#define CHOCO_SEG_WIN_STRIDE 32
+#define CHOCO_SEG_WIN_LO 0
+#define CHOCO_SEG_WIN_SH 4
+#define CHOCO_SEG_WIN_VALID 8
+#define CHOCO_SEG_WIN_T_PREV 16
+#define CHOCO_SEG_WIN_D_PREV 20
+#define CHOCO_SEG_WIN_CAND 24
+#define CHOCO_SEG_WIN_TRUST 28
+#define CHOCO_SEG_INFO_STRIDE 32
+#define CHOCO_SEG_INFO_LO 0
+#define CHOCO_SEG_INFO_SH 1
+#define CHOCO_SEG_INFO_MODE 6
+#define CHOCO_SEG_SHADOW_OFFSET 64
+int choco_topk_segmented_diag_layout(const int64_t* plan_host, int32_t nseg, int64_t* win_off,
+                                     int64_t* info_off);
+int choco_topk_segmented_host_state(const void* ws, const int64_t* plan_host, int32_t nseg,
+                                    uint64_t out[8]);
 
 /* ------------------------------------------------------------- random-k
  * Replaces SparsificationCompressor.get_random_k (sparsification.py:40-54).

@@ -1,6 +1,8 @@
 """Warm-path state of the segmented top-k after a few calls (csrc/topk_seg.hip): per
-segment the mode S3a set (0 select, 1 window missed -> exact fallback, 2 every
-element) and the window (lo, sh).  python tools/seg_windows.py [--layout resnet50_imagenet]"""
+multi-tile segment the mode the last warm call took (0 select, 1 / 3 window missed below /
+above -> shared exact select, 2 every element), its window and drift words, and the host's
+warm / cold bookkeeping.  Read through codec.seg_windows / seg_info / seg_host_state
+(include/choco_codec.h CHOCO_SEG_*).  python tools/seg_windows.py [--layout resnet50_imagenet]"""
 import argparse
 import json
 import os
@@ -11,11 +13,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from chocosgd_amd import codec  # noqa: E402
-
-
-def align(v, a=256):
-    return (v + a - 1) // a * a
+from chocosgd_amd import _lib, codec  # noqa: E402
 
 
 def main():
@@ -31,20 +29,20 @@ def main():
     ds = [torch.randn(sum(lens), generator=g, device=dev) for _ in range(4)]
     for i in range(a.calls):
         codec.topk_segmented(ds[i % 4], plan)
-    torch.cuda.synchronize()
-    ws = plan.workspace(dev).cpu().numpy()
-    nseg, ntile = plan.nseg, plan.ntile
-    o = 256
-    o += align(nseg * 2048 * 4) * 2 + align(nseg * 512 * 4)
-    info = ws[o:o + nseg * 32].view(np.uint32).reshape(nseg, 8)
-    o += align(nseg * 32) + align(ntile * 4) + align(ntile * 8) + 2 * align(ntile * 16384 * 4)
-    win = ws[o:o + nseg * 16].view(np.uint32).reshape(nseg, 4)
-    modes = info[:, 6]
-    print(f"{nseg} segments, modes: select {int((modes == 0).sum())} missed {int((modes == 1).sum())} "
+    win = codec.seg_windows(plan)   # (synchronises)
+    info = codec.seg_info(plan)
+    multi = np.nonzero(win[:, codec.SEG_WIN_WORDS.index("valid")])[0]
+    modes = info[multi, _lib.SEG_INFO_MODE]
+    print(f"{plan.nseg} segments, {multi.size} with a window; modes of the last warm call: "
+          f"select {int((modes == 0).sum())} missed {int(((modes == 1) | (modes == 3)).sum())} "
           f"all {int((modes == 2).sum())}")
-    for s in np.nonzero(modes == 1)[0][:20]:
-        print(f"  missed seg {s}: len {lens[s]} k {plan.k_per_seg[s]} window lo {win[s, 0]:#x} sh {win[s, 1]}")
-    print("window sh histogram:", np.bincount(win[:, 1], minlength=10).tolist())
+    col = {w: i for i, w in enumerate(codec.SEG_WIN_WORDS)}
+    for s in multi[(modes == 1) | (modes == 3)][:20]:
+        print(f"  missed seg {s}: len {lens[s]} k {plan.k_per_seg[s]} used lo {info[s, _lib.SEG_INFO_LO]:#x} "
+              f"sh {info[s, _lib.SEG_INFO_SH]}, next lo {win[s, col['lo']]:#x} sh {win[s, col['sh']]}")
+    print("window sh histogram:", np.bincount(win[multi, col["sh"]], minlength=10).tolist())
+    print("trust histogram:", np.bincount(win[multi, col["trust"]], minlength=16).tolist())
+    print("host:", codec.seg_host_state(plan), "shadow (misses, checks):", codec.seg_shadow(plan))
 
 
 if __name__ == "__main__":
