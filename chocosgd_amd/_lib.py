@@ -156,6 +156,15 @@ SIGNATURES = {
                                          _vp, _c_i64, _c_i32, _vp, _vp]),
     "choco_params_sgd_master_scaled": (_c_i32, [_pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64, _p_i32,
                                                 _c_i32, _vp, _c_i64, _c_i32, _vp, _vp]),
+    "choco_params_gradnorm_scaled_local": (_c_i32, [_pp, _p_i64, _p_i32, _p_i32, _c_i32, _c_i64, _c_f64, _c_i32, _vp,
+                                                    _vp, _c_f64, _c_f64, _c_i32, _c_i32, _vp, _vp, _vp, _c_sz, _vp]),
+    "choco_params_pack_scaled": (_c_i32, [_pp, _p_i64, _p_i32, _c_i32, _vp, _c_i64, _vp, _vp, _c_i32, _vp]),
+    "choco_loss_scale_update": (_c_i32, [_vp, _vp, _vp, _c_f64, _c_f64, _c_i32, _vp, _vp]),
+    "choco_params_sgd_flatgrad_scaled": (_c_i32, [_pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64,
+                                                  _p_i32, _c_i32, _vp, _c_i64, _c_f64, _c_i32, _vp]),
+    "choco_params_sgd_master_flatgrad_scaled": (_c_i32, [_pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64,
+                                                         _p_f64, _p_i32, _c_i32, _vp, _vp, _c_i64, _c_f64, _c_i32,
+                                                         _vp]),
     "choco_params_mask_launches": (_c_i32, [_c_i32]),
     "choco_params_mask": (_c_i32, [_pp, _p_i64, _p_i32, _p_i64, _c_i32, _vp, _vp, _c_i64, _vp, _c_i64, _vp]),
     "choco_params_mix_launches": (_c_i32, [_c_i32, _c_i32]),

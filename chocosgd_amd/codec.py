@@ -1170,7 +1170,7 @@ class ParamSgdPlan:
                    "choco_params_gradnorm")
         return self._gn_out
 
-    def gradnorm_scaled(self, scaler, max_norm=None, coef_dtype=None, norms=None):
+    def gradnorm_scaled(self, scaler, max_norm=None, coef_dtype=None, norms=None, update_state=True):
         """One choco_params_gradnorm_scaled over the gradient pointers and flags as they stand,
         the gradients still multiplied by the loss scale: gradnorm()'s norm pass, then ONE
         launch that tests the fp64 sum of squares for an inf / NaN, unscales the total, computes
@@ -1180,7 +1180,11 @@ class ParamSgdPlan:
         own four-element fp32 tensor [total, coefficient / scale, found, scale], overwritten by
         the next call: hand it to run(scaled=...) / run_master(scaled=...).  Nothing is read on
         the host.  There is no pinned total: it would have no norm pass to detect an overflow
-        from."""
+        from.
+
+        update_state=False: choco_params_gradnorm_scaled_local -- the same four floats, the
+        scaler's state read and left as it is (the all-reduce step: the ranks agree on `found`
+        first, then loss_scale_update moves the state)."""
         L = lib()
         if coef_dtype is None:
             coef_dtype = common_grad_dtype(dt for dt, fl in zip(self.dtypes, self.flags) if not fl & SGD_F_NOGRAD)
@@ -1201,14 +1205,37 @@ class ParamSgdPlan:
             _require(norms, torch.float32, "norms")
             if norms.device != self.device or norms.numel() != self.nseg:
                 raise RuntimeError(f"norms must hold {self.nseg} elements on {self.device}")
-        _lib.check(L.choco_params_gradnorm_scaled(self.grad_ptrs, self.lens, self.dts, self.flags, self.nseg, self.n,
-                                                  0.0 if max_norm is None else float(max_norm), cd, _ptr(scale),
-                                                  _ptr(tracker), float(scaler.growth_factor),
-                                                  float(scaler.backoff_factor), int(scaler.growth_interval),
-                                                  0 if max_norm is None else 1, _ptr(self._ls_out), _ptr(norms),
-                                                  _ptr(self._gn_ws), self._gn_ws.numel(), _stream(self.device)),
-                   "choco_params_gradnorm_scaled")
+        name = "choco_params_gradnorm_scaled" if update_state else "choco_params_gradnorm_scaled_local"
+        _lib.check(getattr(L, name)(self.grad_ptrs, self.lens, self.dts, self.flags, self.nseg, self.n,
+                                    0.0 if max_norm is None else float(max_norm), cd, _ptr(scale), _ptr(tracker),
+                                    float(scaler.growth_factor), float(scaler.backoff_factor),
+                                    int(scaler.growth_interval), 0 if max_norm is None else 1, _ptr(self._ls_out),
+                                    _ptr(norms), _ptr(self._gn_ws), self._gn_ws.numel(), _stream(self.device)), name)
         return self._ls_out
+
+    def loss_scale_update(self, scaler, gsum):
+        """One choco_loss_scale_update: `gsum` (fp32, n + 1 elements) is the flat buffer after
+        the all-reduce, its last element the sum of the ranks' overflow flags.  scaler.last
+        (gradnorm_scaled(update_state=False)'s tensor) receives the common flag in its third
+        element, and the scaler's device state is backed off or grown as
+        torch._amp_update_scale_ does.  One launch; nothing is read on the host."""
+        _require(gsum, torch.float32, "gsum")
+        if gsum.device != self.device or gsum.numel() != self.n + 1:
+            raise RuntimeError(f"gsum must hold {self.n + 1} elements on {self.device}")
+        out, scale, tracker = scaler.last, scaler._scale, scaler._growth_tracker
+        if out is None:
+            raise RuntimeError("loss_scale_update needs scaler.last, gradnorm_scaled(update_state=False)'s tensor")
+        _require(out, torch.float32, "scaler.last")
+        _require(scale, torch.float32, "the loss scale")
+        _require(tracker, torch.int32, "the growth tracker")
+        if any(t.device != self.device for t in (out, scale, tracker)) or out.numel() != 4 or scale.numel() != 1 \
+                or tracker.numel() != 1:
+            raise RuntimeError(f"the loss scaler's state and `last` must be tensors of 1, 1 and 4 elements on "
+                               f"{self.device}")
+        _lib.check(lib().choco_loss_scale_update(gsum.data_ptr() + 4 * self.n, _ptr(scale), _ptr(tracker),
+                                                 float(scaler.growth_factor), float(scaler.backoff_factor),
+                                                 int(scaler.growth_interval), _ptr(out), _stream(self.device)),
+                   "choco_loss_scale_update")
 
     def _scaled_ptr(self, scaled, others):
         """scaled (gradnorm_scaled()'s tensor) as a pointer; `others`: whether a keyword it does
@@ -1345,38 +1372,68 @@ class ParamSgdPlan:
                                                  SGD_MODE_WRITE_PARAMS if write else 0, _stream(self.device)),
                    "choco_params_sgd_master")
 
-    def pack_grads(self, flat):
+    def pack_grads(self, flat, coef=None, found=None, round=True):
         """One choco_params_pack of the gradients behind `grad_ptrs` as they stand into `flat`
         (fp32, n elements), widening 16-bit gradients (exact): TensorBuffer(grads) of
-        sgd.py:71-74 with no table built per step."""
-        _require(flat, torch.float32, "flat")
-        if flat.device != self.device or flat.numel() != self.n:
-            raise RuntimeError(f"flat must hold {self.n} elements on {self.device}")
-        _lib.check(lib().choco_params_pack(self.grad_ptrs, self.lens, self.dts, self.nseg, _ptr(flat), self.n,
-                                           _stream(self.device)), "choco_params_pack")
+        sgd.py:71-74 with no table built per step.
 
-    def run_flatgrad(self, gsum, divisor, write=True, write_grads=True, master=None):
+        coef (gradnorm()'s two-element or gradnorm_scaled()'s four-element tensor):
+        choco_params_pack_scaled -- every gradient is multiplied by its second element on the
+        load; round (default) narrows the product once to the gradient's dtype, as the gclip /
+        scaled update kernels do, round=False leaves the fp32 product (the master path).
+        found (gradnorm_scaled()'s tensor; needs coef): flat holds n + 1 elements and the last
+        receives 1.0 where its third element is not zero, else 0.0."""
+        _require(flat, torch.float32, "flat")
+        if found is not None and coef is None:
+            raise RuntimeError("pack_grads: found needs coef")
+        want = self.n + (0 if found is None else 1)
+        if flat.device != self.device or flat.numel() != want:
+            raise RuntimeError(f"flat must hold {want} elements on {self.device}")
+        if coef is None:
+            _lib.check(lib().choco_params_pack(self.grad_ptrs, self.lens, self.dts, self.nseg, _ptr(flat), self.n,
+                                               _stream(self.device)), "choco_params_pack")
+            return
+        _require(coef, torch.float32, "coef")
+        if coef.device != self.device or coef.numel() not in (2, 4):
+            raise RuntimeError(f"coef must be gradnorm()'s or gradnorm_scaled()'s tensor on {self.device}")
+        f_ptr = None
+        if found is not None:
+            _require(found, torch.float32, "found")
+            if found.device != self.device or found.numel() != 4:
+                raise RuntimeError(f"found must be gradnorm_scaled()'s four-element tensor on {self.device}")
+            f_ptr = found.data_ptr() + 8
+        _lib.check(lib().choco_params_pack_scaled(self.grad_ptrs, self.lens, self.dts, self.nseg, _ptr(flat), self.n,
+                                                  coef.data_ptr() + 4, f_ptr, 1 if round else 0,
+                                                  _stream(self.device)), "choco_params_pack_scaled")
+
+    def run_flatgrad(self, gsum, divisor, write=True, write_grads=True, master=None, found_slot=False):
         """One choco_params_sgd_flatgrad (master: choco_params_sgd_master_flatgrad) over the
         tables as they stand: the update whose gradient is gsum / divisor, gsum the flat fp32
         buffer of the all-reduced gradient sum (n elements).  write -> the params are written;
         write_grads -> the averaged gradient goes into the storage behind `grad_ptrs`, narrowed
         to the tensor's dtype.  master (flat fp32, n elements): the update runs on it in place
-        with fp32 momentum buffers and the unrounded average."""
+        with fp32 momentum buffers and the unrounded average.
+
+        found_slot: choco_params_sgd[_master]_flatgrad_scaled -- gsum holds n + 1 elements, and
+        where the last (the all-reduced sum of the ranks' overflow flags) is not zero the step
+        is skipped on the device: nothing is written."""
         _require(gsum, torch.float32, "gsum")
-        if gsum.device != self.device or gsum.numel() != self.n:
-            raise RuntimeError(f"gsum must hold {self.n} elements on {self.device}")
+        want = self.n + (1 if found_slot else 0)
+        if gsum.device != self.device or gsum.numel() != want:
+            raise RuntimeError(f"gsum must hold {want} elements on {self.device}")
+        tail = "_scaled" if found_slot else ""
         mode = (SGD_MODE_WRITE_PARAMS if write else 0) | (SGD_MODE_WRITE_GRADS if write_grads else 0)
         head = (self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts, self.lr, self.weight_decay,
                 self.momentum, self.dampening, self.flags, self.nseg, _ptr(gsum))
         if master is None:
-            _lib.check(lib().choco_params_sgd_flatgrad(*head, self.n, float(divisor), mode, _stream(self.device)),
-                       "choco_params_sgd_flatgrad")
+            name = "choco_params_sgd_flatgrad" + tail
+            _lib.check(getattr(lib(), name)(*head, self.n, float(divisor), mode, _stream(self.device)), name)
             return
         _require(master, torch.float32, "master")
         if master.device != self.device or master.numel() != self.n:
             raise RuntimeError(f"master must hold {self.n} elements on {self.device}")
-        _lib.check(lib().choco_params_sgd_master_flatgrad(*head, _ptr(master), self.n, float(divisor), mode,
-                                                          _stream(self.device)), "choco_params_sgd_master_flatgrad")
+        name = "choco_params_sgd_master_flatgrad" + tail
+        _lib.check(getattr(lib(), name)(*head, _ptr(master), self.n, float(divisor), mode, _stream(self.device)), name)
 
     def mix(self, srcs, weights, lr=0.0, mode=0, ext_a=0.0, ext_b=0.0, flat_out=None, x_out=None):
         """One choco_params_mix over the plan's parameter and gradient pointers as they stand
@@ -1542,20 +1599,23 @@ def params_sgd_flatgrad_launches(nseg):
 
 
 def params_sgd_flatgrad(params, grads, bufs, gsum, divisor, lr, weight_decay=0.0, momentum=0.0, dampening=0.0,
-                        nesterov=False, first=False, master=None, write=True, write_grads=True, plan=None):
+                        nesterov=False, first=False, master=None, write=True, write_grads=True, plan=None,
+                        found_slot=False):
     """The all-reduce SGD update (sgd.py:82-89; include/choco_codec.h, choco_params_sgd_flatgrad
     and choco_params_sgd_master_flatgrad): params_sgd's arguments in apply mode, except that the
     gradient is gsum / divisor -- gsum the flat fp32 buffer of the summed gradients, the tensors
     back to back -- narrowed to each tensor's dtype, and grads[s] is where that averaged gradient
     is written (write_grads; otherwise grads may be None).  master (flat fp32): the update runs
-    on it in place with fp32 bufs and the average is not narrowed.  Returns the plan (pass it
-    back in to reuse its tables)."""
+    on it in place with fp32 bufs and the average is not narrowed.  found_slot: gsum holds one
+    more element, the all-reduced overflow flag, and anything but zero there skips the step on
+    the device (the _scaled entry points).  Returns the plan (pass it back in to reuse its
+    tables)."""
     plan = _sgd_tables(params, grads, bufs, lr, weight_decay, momentum, dampening, nesterov, first, plan,
                        master is not None)
     if not write_grads:  # the grads are outputs here: none written, none needed
         for i in range(plan.nseg):
             plan.flags[i] &= ~SGD_F_NOGRAD
-    plan.run_flatgrad(gsum, divisor, write, write_grads, master)
+    plan.run_flatgrad(gsum, divisor, write, write_grads, master, found_slot)
     return plan
 
 

@@ -36,6 +36,17 @@ CHOCO_DEV unsigned short narrow16(float f) {
   return DT == CHOCO_DT_BF16 ? bf16_narrow(f) : f16_narrow(f);
 }
 
+// The value as the storage dtype holds it.  v is the fp32 result of its line and is narrowed
+// from there (two roundings, as a torch op on a 16-bit tensor has): the empty asm keeps the
+// compiler from merging an fma and the conversion into one v_fma_mixlo_f16, which rounds the
+// exact sum straight to fp16.
+template <int DT>
+CHOCO_DEV float rnd(float v) {
+  if (DT == CHOCO_DT_F32) return v;
+  asm("" : "+v"(v));
+  return widen16<DT>(narrow16<DT>(v));
+}
+
 CHOCO_DEV void st_nt4(float* p, float4 v) {
   choco_f32x4 f;
   f.x = v.x; f.y = v.y; f.z = v.z; f.w = v.w;

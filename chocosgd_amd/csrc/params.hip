@@ -157,6 +157,84 @@ __global__ __launch_bounds__(kPbThreads) void param_unpack_kernel(const ParamTab
   param_tile<false>(tb, flat, tile0, flat16);
 }
 
+// ------------------------------------------------------------------ the scaled pack
+// choco_params_pack_scaled ("param_pack_scaled_kernel"): the pack of the all-reduce SGD step with
+// the global-norm clip coefficient and 1 / loss scale on the load it does anyway,
+//     RND:   flat[i] = (float)rnd_DT(c * g)   the product the gclip / scaled update kernels form
+//     !RND:  flat[i] = c * (float)g           fp32, not narrowed: the master path
+// c = *coef, one uniform load per workgroup.  Same tiles, search and alignment rule as
+// param_pack_kernel, which carries none of this.  found != nullptr (the FIRST launch of a layout
+// alone gets it): thread 0 of workgroup 0 stores flat[n] = (*found != 0) ? 1 : 0, the slot that
+// rides through the all-reduce behind the gradient.
+template <int DT, bool RND>
+CHOCO_DEV float pack_scaled1(float c, float g) {
+  const float v = __fmul_rn(c, g);
+  return RND ? rnd<DT>(v) : v;
+}
+
+// Flat elements [a, b) of tensor s (flat offset o0, base p), a < b inside this workgroup's tile.
+template <int DT, bool RND>
+CHOCO_DEV void pack_scaled_span(const void* p, float* flat, float c, int64_t o0, int64_t a, int64_t b, bool vec) {
+  const int tid = threadIdx.x;
+  if (!vec) {
+    for (int64_t i = a + tid; i < b; i += kPbThreads) flat[i] = pack_scaled1<DT, RND>(c, ld1<DT>(p, i - o0));
+    return;
+  }
+  const int64_t g0 = a >> 3, g1 = (b - 1) >> 3;  // groups at absolute flat offsets, inclusive
+  for (int64_t gb = g0; gb <= g1; gb += (int64_t)kPbThreads * kPbU) {
+    bool full[kPbU];
+    Raw8 r[kPbU];
+    // every load of the thread's kPbU groups is issued before the first store
+#pragma unroll
+    for (int u = 0; u < kPbU; ++u) {
+      const int64_t e = (gb + u * kPbThreads + tid) * kPbGroup;
+      full[u] = e >= a && e + kPbGroup <= b;
+      if (full[u]) ld8<DT>(r[u], p, e - o0);
+    }
+#pragma unroll
+    for (int u = 0; u < kPbU; ++u) {
+      const int64_t e = (gb + u * kPbThreads + tid) * kPbGroup;
+      if (full[u]) {
+        float v[8];
+        widen8<DT>(r[u], v);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = pack_scaled1<DT, RND>(c, v[k]);
+        st8<CHOCO_DT_F32>(flat, e, v);
+      } else {
+        // a group cut by the tensor's start or end (or past the span): its own elements only
+        const int64_t ea = e > a ? e : a, eb = e + kPbGroup < b ? e + kPbGroup : b;
+        for (int64_t i = ea; i < eb; ++i) flat[i] = pack_scaled1<DT, RND>(c, ld1<DT>(p, i - o0));
+      }
+    }
+  }
+}
+
+template <bool RND>
+__global__ __launch_bounds__(kPbThreads) void param_pack_scaled_kernel(const ParamTable tb, float* flat, int64_t tile0,
+                                                                       int flat16, const float* coef,
+                                                                       const float* found, int64_t n) {
+  const float c = *coef;  // a uniform load
+  if (found != nullptr && blockIdx.x == 0 && threadIdx.x == 0) flat[n] = *found != 0.0f ? 1.0f : 0.0f;
+  const int nt = tb.nt;
+  int64_t tlo, thi;
+  const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
+  if (s0 < 0) return;
+  for (int s = s0; s < nt; ++s) {
+    const int64_t o0 = tb.off[s];
+    if (o0 >= thi) break;
+    const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);
+    if (a >= b) continue;  // zero-length tensor
+    const void* p = tb.ptr[s];
+    const int dt = tb.dt[s];
+    // the alignment rule of param_tile
+    const uintptr_t esz = dt == CHOCO_DT_F32 ? 4u : 2u;
+    const bool vec = flat16 && ((reinterpret_cast<uintptr_t>(p) - esz * (uintptr_t)o0) & 15u) == 0;
+    if (dt == CHOCO_DT_F32) pack_scaled_span<CHOCO_DT_F32, RND>(p, flat, c, o0, a, b, vec);
+    else if (dt == CHOCO_DT_BF16) pack_scaled_span<CHOCO_DT_BF16, RND>(p, flat, c, o0, a, b, vec);
+    else pack_scaled_span<CHOCO_DT_F16, RND>(p, flat, c, o0, a, b, vec);
+  }
+}
+
 static int params_launches(int32_t nseg) { return nseg <= 0 ? 0 : (nseg + kParamCap - 1) / kParamCap; }
 
 // Every argument is checked before the first launch, with no HIP call.
@@ -183,11 +261,24 @@ static int params_check(const void* const* ptrs, const int64_t* lens, const int3
   return CHOCO_OK;
 }
 
+// choco_params_pack_scaled's three arguments; found: flat holds n + 1 elements
+struct PackScale {
+  const float* coef;
+  const float* found;
+  int32_t round;
+};
+
 template <bool PACK>
 static int params_run(const void* const* ptrs, const int64_t* lens, const int32_t* dtypes, int32_t nseg,
-                      float* flat, int64_t n, hipStream_t st) {
+                      float* flat, int64_t n, hipStream_t st, const PackScale* sc = nullptr) {
   const int rc = params_check(ptrs, lens, dtypes, nseg, flat, n);
   if (rc) return rc;
+  if (sc) {
+    CHOCO_REQUIRE(sc->coef && aligned4(sc->coef), "coef must be a 4-byte aligned device pointer");
+    CHOCO_REQUIRE(aligned4(sc->found), "found must be 4-byte aligned");
+    CHOCO_REQUIRE(sc->round == 0 || sc->round == 1, "round must be 0 or 1, got %d", (int)sc->round);
+    CHOCO_REQUIRE(flat || !sc->found, "null flat buffer with a found slot to write");
+  }
   const char* name = PACK ? "param_pack_kernel" : "param_unpack_kernel";
   const int flat16 = aligned16(flat) ? 1 : 0;
   ParamTable tb;
@@ -206,6 +297,14 @@ static int params_run(const void* const* ptrs, const int64_t* lens, const int32_
     // the tiles the chunk [off[0], off[nt]) touches; an empty chunk still takes its launch
     const int64_t tile0 = tb.off[0] / kPbTile;
     const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
+    if (sc) {
+      // the slot behind the gradient is the first launch's: written once however many chunks follow
+      const float* found = s0 == 0 ? sc->found : nullptr;
+      CHOCO_TRY(CHOCO_LAUNCH("param_pack_scaled_kernel", "param_pack_scaled_kernel",
+                             sc->round ? param_pack_scaled_kernel<true> : param_pack_scaled_kernel<false>,
+                             dim3((unsigned)tiles), dim3(kPbThreads), st, tb, flat, tile0, flat16, sc->coef, found, n));
+      continue;
+    }
     CHOCO_TRY(CHOCO_LAUNCH(name, name, PACK ? param_pack_kernel : param_unpack_kernel, dim3((unsigned)tiles),
                            dim3(kPbThreads), st, tb, flat, tile0, flat16));
   }
@@ -221,6 +320,13 @@ CHOCO_API int choco_params_launches(int32_t nseg) { return params_launches(nseg)
 CHOCO_API int choco_params_pack(const void* const* ptrs, const int64_t* lens, const int32_t* dtypes, int32_t nseg,
                                 float* flat, int64_t n, void* stream) {
   return params_run<true>(ptrs, lens, dtypes, nseg, flat, n, as_stream(stream));
+}
+
+CHOCO_API int choco_params_pack_scaled(const void* const* ptrs, const int64_t* lens, const int32_t* dtypes,
+                                       int32_t nseg, float* flat, int64_t n, const float* coef,
+                                       const float* found_or_null, int32_t round, void* stream) {
+  const PackScale sc{coef, found_or_null, round};
+  return params_run<true>(ptrs, lens, dtypes, nseg, flat, n, as_stream(stream), &sc);
 }
 
 CHOCO_API int choco_params_unpack(void* const* ptrs, const int64_t* lens, const int32_t* dtypes, int32_t nseg,

@@ -72,16 +72,7 @@ struct SgdTensor {
   float gc;                // ... and the global clip coefficient, *coef
 };
 
-// The value as the storage dtype holds it.  v is the fp32 result of its line and is narrowed
-// from there (two roundings, as a torch op on a 16-bit tensor has): the empty asm keeps the
-// compiler from merging an fma and the conversion into one v_fma_mixlo_f16, which rounds the
-// exact sum straight to fp16.
-template <int DT>
-CHOCO_DEV float rnd(float v) {
-  if (DT == CHOCO_DT_F32) return v;
-  asm("" : "+v"(v));
-  return widen16<DT>(narrow16<DT>(v));
-}
+// rnd<DT>(v), the value as the storage dtype holds it: param_common.h
 
 // one element; out = what goes to params / grads and to flat
 template <int DT>
@@ -498,14 +489,26 @@ CHOCO_DEV void flatgrad_span(const SgdTensor& t, const float* gsum, float* maste
 }
 
 // al16: bit 0 gsum, bit 1 master 16-byte aligned
-template <bool MASTER>
+// SLOT: no argument at all (param_sgd_flatgrad_kernel / param_sgd_master_flatgrad_kernel, the
+// argument list they always had), or one FoundSlot ("param_sgd_flatgrad_scaled_kernel" /
+// "param_sgd_master_flatgrad_scaled_kernel", choco_params_sgd[_master]_flatgrad_scaled): the
+// address of gsum[n], the all-reduced sum of the ranks' overflow flags -- one uniform load per
+// workgroup, and anything but zero (a NaN included) makes the workgroup return before it touches
+// a parameter, a momentum buffer, a gradient or the master copy.
+struct FoundSlot {
+  const float* p;
+};
+CHOCO_DEV bool found_of(FoundSlot f) { return *f.p != 0.0f; }
+
+template <bool MASTER, typename... SLOT>
 __global__ __launch_bounds__(kPbThreads) void param_sgd_flatgrad_kernel(const SgdTable tb, const float* gsum,
                                                                         float* master, int64_t tile0, float div,
-                                                                        int32_t al16, int32_t mode) {
+                                                                        int32_t al16, int32_t mode, SLOT... slot) {
   const int nt = tb.nt;
   int64_t tlo, thi;
   const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
   if (s0 < 0) return;
+  if ((found_of(slot) || ...)) return;  // in the scaled instantiations alone
   for (int s = s0; s < nt; ++s) {
     const int64_t o0 = tb.off[s];
     if (o0 >= thi) break;
@@ -572,6 +575,7 @@ struct SgdArgs {
   const float* coef;     // device, the global-norm clip coefficient (choco_params_gradnorm's out + 1)
   bool scaled;           // choco_params_sgd[_master]_scaled (gclip with it): coef is choco_params_gradnorm_scaled's
                          // out, four floats, and the step is skipped on the device where out[2] != 0
+  bool found_slot;       // choco_params_sgd[_master]_flatgrad_scaled: gsum holds n + 1 elements, the last the flag
 };
 
 static bool elem_aligned(const void* p, uintptr_t esz) { return (reinterpret_cast<uintptr_t>(p) & (esz - 1)) == 0; }
@@ -618,7 +622,7 @@ static int flatgrad_check(const SgdArgs& a) {
     CHOCO_REQUIRE(a.bufs[s] || a.mom[s] == 0.0, "tensor %d: null momentum buffer with momentum != 0", i);
   }
   CHOCO_REQUIRE(sum == a.n, "the lengths add up to %lld, n is %lld", (long long)sum, (long long)a.n);
-  CHOCO_REQUIRE(a.n == 0 || a.gsum, "gsum is null");
+  CHOCO_REQUIRE((a.n == 0 && !a.found_slot) || a.gsum, "gsum is null");
   return CHOCO_OK;
 }
 
@@ -730,7 +734,16 @@ static int sgd_run(const SgdArgs& a, hipStream_t st) {
     const float* norms = a.norms ? a.norms + s0 : nullptr;
     const float thr = (float)a.clip_threshold;
     const int32_t al16 = (aligned16(a.gsum) ? 1 : 0) | (a.master ? 2 * flat16 : 0);
-    if (a.flatgrad && a.master)
+    if (a.flatgrad && a.found_slot && a.master)
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_master_flatgrad_scaled_kernel", "param_sgd_master_flatgrad_scaled_kernel",
+                             param_sgd_flatgrad_kernel<true, FoundSlot>, dim3((unsigned)tiles), dim3(kPbThreads), st,
+                             tb, a.gsum, a.flat, tile0, (float)a.divisor, al16, a.mode, FoundSlot{a.gsum + a.n}));
+    else if (a.flatgrad && a.found_slot)
+      CHOCO_TRY(CHOCO_LAUNCH("param_sgd_flatgrad_scaled_kernel", "param_sgd_flatgrad_scaled_kernel",
+                             param_sgd_flatgrad_kernel<false, FoundSlot>, dim3((unsigned)tiles), dim3(kPbThreads), st,
+                             tb, a.gsum, (float*)nullptr, tile0, (float)a.divisor, al16, a.mode,
+                             FoundSlot{a.gsum + a.n}));
+    else if (a.flatgrad && a.master)
       CHOCO_TRY(CHOCO_LAUNCH("param_sgd_master_flatgrad_kernel", "param_sgd_master_flatgrad_kernel",
                              param_sgd_flatgrad_kernel<true>, dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.gsum,
                              a.flat, tile0, (float)a.divisor, al16, a.mode));
@@ -1027,23 +1040,10 @@ struct LossScale {
   int32_t interval, has_clip;
 };
 
-// the one lane that writes out[]: sum = the fp64 sum of squares, root = (float)sqrt(sum)
-CHOCO_DEV void scaled_finish(double sum, float root, float max_norm, int32_t cd, float* out, const LossScale& ls) {
-  const float scale = *ls.scale;
-  const float inv = (float)(1.0 / (double)scale);
-  const bool found = !__builtin_isfinite(sum);
-  const float total = rnd_as(__fmul_rn(root, inv), cd);
-  float c = 1.0f;
-  if (ls.has_clip) {
-    const float t = rnd_as(__fadd_rn(total, 1e-6f), cd);
-    const float r = rnd_as(__fdiv_rn(1.0f, t), cd);
-    c = rnd_as(__fmul_rn(r, max_norm), cd);
-    c = c > 1.0f ? 1.0f : c;
-  }
-  out[0] = total;
-  out[1] = __fmul_rn(c, inv);
-  out[2] = found ? 1.0f : 0.0f;
-  out[3] = scale;
+// torch's _amp_update_scale_ on the device state, from the scale the step ran with: plain stores
+// by one lane.  loss_scale_update_kernel's copy of the lines scaled_out<true> ends with: that
+// instantiation keeps the instruction stream it had.
+CHOCO_DEV void amp_update_scale(float scale, bool found, const LossScale& ls) {
   if (found) {
     *ls.scale = (float)((double)scale * ls.backoff);
     *ls.tracker = 0;
@@ -1059,12 +1059,69 @@ CHOCO_DEV void scaled_finish(double sum, float root, float max_norm, int32_t cd,
   }
 }
 
+// the one lane that writes out[]: sum = the fp64 sum of squares, root = (float)sqrt(sum).
+// UPDATE false (choco_params_gradnorm_scaled_local): the state is read, never written -- the
+// ranks of an all-reduce step agree on `found` first (choco_loss_scale_update).
+template <bool UPDATE>
+CHOCO_DEV void scaled_out(double sum, float root, float max_norm, int32_t cd, float* out, const LossScale& ls) {
+  const float scale = *ls.scale;
+  const float inv = (float)(1.0 / (double)scale);
+  const bool found = !__builtin_isfinite(sum);
+  const float total = rnd_as(__fmul_rn(root, inv), cd);
+  float c = 1.0f;
+  if (ls.has_clip) {
+    const float t = rnd_as(__fadd_rn(total, 1e-6f), cd);
+    const float r = rnd_as(__fdiv_rn(1.0f, t), cd);
+    c = rnd_as(__fmul_rn(r, max_norm), cd);
+    c = c > 1.0f ? 1.0f : c;
+  }
+  out[0] = total;
+  out[1] = __fmul_rn(c, inv);
+  out[2] = found ? 1.0f : 0.0f;
+  out[3] = scale;
+  if (!UPDATE) return;
+  if (found) {
+    *ls.scale = (float)((double)scale * ls.backoff);
+    *ls.tracker = 0;
+  } else {
+    const int32_t ok = *ls.tracker + 1;
+    if (ok == ls.interval) {
+      const float s = (float)((double)scale * ls.growth);
+      if (__builtin_isfinite(s)) *ls.scale = s;
+      *ls.tracker = 0;
+    } else {
+      *ls.tracker = ok;
+    }
+  }
+}
+
+struct LossScaleLocal {
+  LossScale ls;
+};
+CHOCO_DEV void scaled_finish(double sum, float root, float max_norm, int32_t cd, float* out, const LossScale& ls) {
+  scaled_out<true>(sum, root, max_norm, cd, out, ls);
+}
+CHOCO_DEV void scaled_finish(double sum, float root, float max_norm, int32_t cd, float* out, const LossScaleLocal& l) {
+  scaled_out<false>(sum, root, max_norm, cd, out, l.ls);
+}
+
+// choco_loss_scale_update: the state update alone, from the all-reduced flag.  One lane of one
+// small workgroup; out is choco_params_gradnorm_scaled_local's, whose third float becomes the
+// ranks' common flag.
+__global__ __launch_bounds__(64) void loss_scale_update_kernel(const float* found_sum, const LossScale ls, float* out) {
+  if (threadIdx.x != 0) return;
+  const bool found = *found_sum != 0.0f;
+  out[2] = found ? 1.0f : 0.0f;
+  amp_update_scale(*ls.scale, found, ls);
+}
+
 constexpr int kTotalThreads = 1024;
 constexpr int kTotalStageSlots = 5120;  // 40 KB of fp64 slots, 8 KB of meta words and 8 KB of sums in LDS
 constexpr int kTotalStageSegs = 1024;
 // LS: no argument at all (param_gradnorm_total_kernel, the argument list it always had), or one
 // LossScale ("param_gradnorm_scaled_total_kernel"; total_in is then null: a pinned total has no
-// norm pass to detect an overflow from).
+// norm pass to detect an overflow from), or one LossScaleLocal
+// ("param_gradnorm_scaled_local_total_kernel": the same without the state update).
 template <typename... LS>
 __global__ __launch_bounds__(kTotalThreads) void param_gradnorm_total_kernel(const double* slots, int32_t nslots,
                                                                              const int32_t* meta, double* sums,
@@ -1240,7 +1297,18 @@ struct GradnormArgs {
   size_t ws_bytes;
   bool scaled;   // choco_params_gradnorm_scaled: out holds four floats and ls is the loss-scale state
   LossScale ls;
+  bool local;    // choco_params_gradnorm_scaled_local: the state is not updated
 };
+
+// the loss-scale state arguments (choco_params_gradnorm_scaled[_local], choco_loss_scale_update)
+static int loss_scale_check(const LossScale& ls) {
+  CHOCO_REQUIRE(ls.scale && aligned4(ls.scale), "scale_state must be a 4-byte aligned device pointer");
+  CHOCO_REQUIRE(ls.tracker && aligned4(ls.tracker), "growth_tracker must be a 4-byte aligned device pointer");
+  CHOCO_REQUIRE(ls.growth > 1.0 && std::isfinite(ls.growth), "growth must be finite and > 1, got %g", ls.growth);
+  CHOCO_REQUIRE(ls.backoff > 0.0 && ls.backoff < 1.0, "backoff must be in (0, 1), got %g", ls.backoff);
+  CHOCO_REQUIRE(ls.interval >= 1, "interval must be >= 1, got %d", (int)ls.interval);
+  return CHOCO_OK;
+}
 
 static int gradnorm_check(const GradnormArgs& a) {
   CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
@@ -1250,12 +1318,8 @@ static int gradnorm_check(const GradnormArgs& a) {
     CHOCO_REQUIRE(a.max_norm >= 0.0 && a.max_norm <= 3.4028234663852886e38,
                   "max_norm must be >= 0 and finite as an fp32 value, got %g", a.max_norm);
   if (a.scaled) {
-    CHOCO_REQUIRE(a.ls.scale && aligned4(a.ls.scale), "scale_state must be a 4-byte aligned device pointer");
-    CHOCO_REQUIRE(a.ls.tracker && aligned4(a.ls.tracker), "growth_tracker must be a 4-byte aligned device pointer");
-    CHOCO_REQUIRE(a.ls.growth > 1.0 && std::isfinite(a.ls.growth), "growth must be finite and > 1, got %g",
-                  a.ls.growth);
-    CHOCO_REQUIRE(a.ls.backoff > 0.0 && a.ls.backoff < 1.0, "backoff must be in (0, 1), got %g", a.ls.backoff);
-    CHOCO_REQUIRE(a.ls.interval >= 1, "interval must be >= 1, got %d", (int)a.ls.interval);
+    const int rc = loss_scale_check(a.ls);
+    if (rc) return rc;
     CHOCO_REQUIRE(a.ls.has_clip == 0 || a.ls.has_clip == 1, "has_clip must be 0 or 1, got %d", (int)a.ls.has_clip);
   }
   CHOCO_REQUIRE(a.coef_dtype >= CHOCO_DT_F32 && a.coef_dtype <= CHOCO_DT_F16, "unknown coef_dtype code %d",
@@ -1303,6 +1367,14 @@ static int gradnorm_run(const GradnormArgs& a, hipStream_t st) {
     meta = reinterpret_cast<int32_t*>(sums + a.nseg);
     const NormArgs pass{nullptr, a.grads, a.lens, a.dtypes, nullptr, a.flags, a.nseg, a.n, nullptr, a.ws, a.ws_bytes};
     CHOCO_TRY(norm_pass(pass, slots, meta, st));
+  }
+  if (a.scaled && a.local) {
+    CHOCO_TRY(CHOCO_LAUNCH("param_gradnorm_scaled_local_total_kernel", "param_gradnorm_scaled_local_total_kernel",
+                           param_gradnorm_total_kernel<LossScaleLocal>, dim3(1), dim3(kTotalThreads), st,
+                           (const double*)slots, (int32_t)norm_slots(a.nseg, a.n), (const int32_t*)meta, sums, a.norms,
+                           a.nseg, (const float*)nullptr, (float)(a.ls.has_clip ? a.max_norm : 0.0), a.coef_dtype,
+                           a.out, LossScaleLocal{a.ls}));
+    return CHOCO_OK;
   }
   if (a.scaled) {
     CHOCO_TRY(CHOCO_LAUNCH("param_gradnorm_scaled_total_kernel", "param_gradnorm_scaled_total_kernel",
@@ -1404,6 +1476,60 @@ CHOCO_API int choco_params_gradnorm_scaled(const void* const* grads, const int64
   const GradnormArgs a{grads, lens, dtypes, flags, nseg, n, max_norm, coef_dtype, nullptr, out, norms, ws, ws_bytes,
                        true, LossScale{scale_state, growth_tracker, growth, backoff, interval, has_clip}};
   return gradnorm_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_gradnorm_scaled_local(const void* const* grads, const int64_t* lens, const int32_t* dtypes,
+                                                 const int32_t* flags, int32_t nseg, int64_t n, double max_norm,
+                                                 int32_t coef_dtype, const float* scale_state,
+                                                 const int32_t* growth_tracker, double growth, double backoff,
+                                                 int32_t interval, int32_t has_clip, float* out, float* norms,
+                                                 void* ws, size_t ws_bytes, void* stream) {
+  const GradnormArgs a{grads, lens, dtypes, flags, nseg, n, max_norm, coef_dtype, nullptr, out, norms, ws, ws_bytes,
+                       true,
+                       LossScale{const_cast<float*>(scale_state), const_cast<int32_t*>(growth_tracker), growth, backoff,
+                                 interval, has_clip},
+                       true};
+  return gradnorm_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_loss_scale_update(const float* found_sum, float* scale_state, int32_t* growth_tracker,
+                                      double growth, double backoff, int32_t interval, float* out, void* stream) {
+  const LossScale ls{scale_state, growth_tracker, growth, backoff, interval, 0};
+  CHOCO_REQUIRE(found_sum && aligned4(found_sum), "found_sum must be a 4-byte aligned device pointer");
+  const int rc = loss_scale_check(ls);
+  if (rc) return rc;
+  CHOCO_REQUIRE(out && aligned4(out), "out must be a 4-byte aligned device pointer");
+  CHOCO_TRY(CHOCO_LAUNCH("loss_scale_update_kernel", "loss_scale_update_kernel", loss_scale_update_kernel, dim3(1),
+                         dim3(64), as_stream(stream), found_sum, ls, out));
+  return CHOCO_OK;
+}
+
+CHOCO_API int choco_params_sgd_flatgrad_scaled(void* const* params, void* const* grads, void* const* bufs,
+                                               const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                               const double* weight_decay, const double* momentum,
+                                               const double* dampening, const int32_t* flags, int32_t nseg,
+                                               const float* gsum, int64_t n, double divisor, int32_t mode,
+                                               void* stream) {
+  SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, nullptr, n, mode,
+            false, nullptr, 0.0, false};
+  a.gsum = gsum;
+  a.divisor = divisor;
+  a.flatgrad = a.found_slot = true;
+  return sgd_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_sgd_master_flatgrad_scaled(void* const* params, void* const* grads, void* const* bufs,
+                                                      const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                                      const double* weight_decay, const double* momentum,
+                                                      const double* dampening, const int32_t* flags, int32_t nseg,
+                                                      const float* gsum, float* master, int64_t n, double divisor,
+                                                      int32_t mode, void* stream) {
+  SgdArgs a{params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening, flags, nseg, master, n, mode,
+            false, nullptr, 0.0, true};
+  a.gsum = gsum;
+  a.divisor = divisor;
+  a.flatgrad = a.found_slot = true;
+  return sgd_run(a, as_stream(stream));
 }
 
 CHOCO_API int choco_params_sgd_gclip(void* const* params, const void* const* grads, void* const* bufs,

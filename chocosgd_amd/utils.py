@@ -893,8 +893,55 @@ def _apply_averaged_loop(entries, state, grads):
         p.data.copy_(p.data.float().add(d_p.float(), alpha=-group["lr"]).to(dt))
 
 
+def _allreduce_scaled_loop(entries, param_groups, state, aggregator, distributed, write_grads, master, clip, ls):
+    """allreduce_sgd_step_loop with clip_norm and / or loss_scale: the kernels' lines
+    (include/choco_codec.h, clip and loss scale in the pack), one torch op each."""
+    grads = [p.grad.data for _, p in entries]
+    dev = grads[0].device
+    cd = torch.float32 if master is not None else codec.common_grad_dtype(g.dtype for g in grads)
+    found = None
+    if ls is not None:
+        scaler, clip_norm = ls[0], ls[1]
+        scale = scaler._scale.reshape(()).clone()
+        inv = scale.double().reciprocal().float()
+        ssq = torch.stack([g.detach().double().pow(2).sum().to(dev) for g in grads]).sum()
+        found = (~torch.isfinite(ssq)).float()
+        total = (ssq.sqrt().float() * inv).to(cd)
+        c = torch.ones((), dtype=cd, device=dev) if clip_norm is None else _clip_coef32(total, clip_norm)
+        gc = c.float() * inv
+        out = scaler.last = torch.stack([total.float(), gc, found, scale])
+    else:
+        gc = _clip_coef32(_total_norm(grads, clip[2], cd), clip[0]).float()
+    # the pack: one fp32 product per element, narrowed once to the gradient's dtype unless master
+    packed = [g.float() * gc if master is not None else (g.float() * gc).to(g.dtype).float() for g in grads]
+    n = sum(g.numel() for g in grads)
+    flat = torch.cat([x.reshape(-1) for x in packed] + ([] if found is None else [found.reshape(1)]))
+    flat = aggregator._agg(flat, op="sum", distributed=distributed)
+    n_bits = get_n_bits(flat)
+    if ls is not None:
+        found = (flat[n:] != 0).float()
+        out[2] = found[0]
+        torch._amp_update_scale_(scaler._scale, scaler._growth_tracker, found, scaler.growth_factor,
+                                 scaler.backoff_factor, scaler.growth_interval)
+        if bool(found):
+            return n_bits
+    divisor = float(aggregator.world_size) if distributed else 1.0
+    avg = flat[:n].div(torch.full((), divisor, dtype=flat.dtype, device=flat.device))
+    flatten_grads = TensorBuffer.from_flat(avg, [g.shape for g in grads])
+    if master is not None:
+        apply_gradient_master_loop(param_groups, state, master, write=True,
+                                   grads32=[flatten_grads[i] for i in range(len(entries))])
+        if write_grads:
+            flatten_grads.unpack(grads)
+    else:
+        avg = grads if write_grads else [torch.empty_like(g) for g in grads]  # p.grad keeps its values
+        flatten_grads.unpack(avg)
+        _apply_averaged_loop(entries, state, avg)
+    return n_bits
+
+
 def allreduce_sgd_step_loop(param_groups, param_names, state, aggregator, distributed=True, write_grads=True,
-                            master=None):
+                            master=None, clip_norm=None, total_norm=None, loss_scale=None):
     """allreduce_sgd_step as the reference's op sequence (sgd.py:69-92), one torch op per line:
     TensorBuffer(grads) in fp32, the all-reduce, the division by the world size, the unpack into
     the grads, apply_gradient_loop's lines (_apply_averaged_loop: for fp32 tensors the same ops;
@@ -904,10 +951,20 @@ def allreduce_sgd_step_loop(param_groups, param_names, state, aggregator, distri
     division too (torch multiplies a device tensor by the reciprocal of a Python scalar).
 
     master: the division's fp32 result is the gradient of apply_gradient_master_loop's lines,
-    unrounded, and is then narrowed into p.grad (write_grads)."""
+    unrounded, and is then narrowed into p.grad (write_grads).
+
+    clip_norm / total_norm / loss_scale: allreduce_sgd_step's, with the kernels' lines -- the
+    coefficient (_clip_coef32) and, with loss_scale, apply_gradient_scaled_loop's inv / found /
+    total / gc lines on the local gradients, one fp32 product per element in the pack, the
+    local flag as element n of the flat buffer, torch._amp_update_scale_ on the summed flag
+    and a host branch for the skip."""
+    clip, ls = _scale_args("allreduce_sgd_step", loss_scale, clip_norm, False, total_norm)
     entries = _allreduce_entries(param_groups, param_names, master)
     if master is not None:
         _master_bufs_are_fp32(entries, state)
+    if clip is not None or ls is not None:
+        return _allreduce_scaled_loop(entries, param_groups, state, aggregator, distributed, write_grads, master,
+                                      clip, ls)
     grads = [p.grad.data for _, p in entries]
     floating = all(g.dtype in codec.PARAM_DTYPES for g in grads)
     flatten_grads = TensorBuffer(grads, dtype=torch.float32 if floating else None)
@@ -927,7 +984,8 @@ def allreduce_sgd_step_loop(param_groups, param_names, state, aggregator, distri
     return get_n_bits(flatten_grads.buffer)
 
 
-def allreduce_sgd_step(param_groups, param_names, state, aggregator, distributed=True, write_grads=True, master=None):
+def allreduce_sgd_step(param_groups, param_names, state, aggregator, distributed=True, write_grads=True, master=None,
+                       clip_norm=None, total_norm=None, loss_scale=None):
     """The centralized branch of SGD.step (sgd.py:68-92), plain all-reduce data-parallel SGD, end
     to end: ONE pack launch per chunk of the gradients into a flat fp32 buffer (16-bit
     gradients are widened, which is exact), aggregator._agg(flat, op="sum",
@@ -948,16 +1006,60 @@ def allreduce_sgd_step(param_groups, param_names, state, aggregator, distributed
     master (a MasterWeights of this model): the update runs in fp32 on the master copy in place,
     on the unrounded average, with fp32 momentum buffers (created as such; one of another dtype
     raises), and the parameters receive the new master values narrowed
-    (codec.params_sgd_flatgrad(master=...)); p.grad receives the average narrowed."""
+    (codec.params_sgd_flatgrad(master=...)); p.grad receives the average narrowed.
+
+    clip_norm (conf.rnn_clip): torch.nn.utils.clip_grad_norm_(params, clip_norm) on the LOCAL
+    gradients in front of the step (distributed_running_nlp.py:96, each rank by its own norm),
+    fused: one norm pass (codec ParamSgdPlan.gradnorm; total_norm pins the total), and the
+    pack multiplies by the coefficient on the load it does anyway, narrowing the product once
+    to the gradient's dtype (with master: the fp32 coefficient and the fp32 product, not
+    narrowed).  No pass rewrites the gradients.
+
+    loss_scale (a LossScaler; no total_norm): the gradients are those of
+    scaler.scale(loss).  The norm pass finds this rank's inf / NaN without touching the
+    scaler's state, the pack multiplies by (clip coefficient) / scale and puts the local flag
+    into ONE extra fp32 slot behind the flat gradient, the same all-reduce sums it, one small
+    launch (codec ParamSgdPlan.loss_scale_update) turns the sum into the ranks' common flag
+    (scaler.last[2]) and backs the scale off or grows it, and the update skips the step on the
+    device where the flag is set: every rank skips together and every scale stays in step.
+    On a taken step p.grad (write_grads) receives the averaged, unscaled, clipped gradient; on
+    a skipped one nothing is written but the scaler's state and `last`.  n_bits counts the
+    n + 1 elements sent.  Nothing is read on the host, except while a step creates momentum
+    buffers (the first taken step): the summed flag is then read after the all-reduce, and
+    an overflowed step leaves no buffer behind and launches no update.
+
+    With all three None this is the code path above, launch for launch."""
+    clip, ls = _scale_args("allreduce_sgd_step", loss_scale, clip_norm, False, total_norm)
     entries = _allreduce_entries(param_groups, param_names, master)
     plan = _sgd_fill(entries, state, True, None if master is None else master.buffer, master=master is not None)
     if plan is None:
-        return allreduce_sgd_step_loop(param_groups, param_names, state, aggregator, distributed, write_grads, master)
+        return allreduce_sgd_step_loop(param_groups, param_names, state, aggregator, distributed, write_grads, master,
+                                       clip_norm, total_norm, loss_scale)
+    divisor = float(aggregator.world_size) if distributed else 1.0
+    mbuf = None if master is None else master.buffer
+    cd = None if master is None else torch.float32
+    if ls is not None:
+        scaler = ls[0]
+        out = scaler.last = plan.gradnorm_scaled(scaler, ls[1], coef_dtype=cd, update_state=False)
+        flat = torch.empty(plan.n + 1, dtype=torch.float32, device=plan.device)
+        plan.pack_grads(flat, coef=out, found=out, round=master is None)
+        flat = aggregator._agg(flat, op="sum", distributed=distributed)
+        plan.loss_scale_update(scaler, flat)
+        # SGD_F_FIRST is a host decision (_first_step_overflow): the one sync, gone from the first taken step on
+        if plan.created and bool(flat[plan.n] != 0):
+            for param_state in plan.created:
+                del param_state["momentum_buffer"]
+            plan.created = []
+        else:
+            plan.run_flatgrad(flat, divisor, write=True, write_grads=write_grads, master=mbuf, found_slot=True)
+        return get_n_bits(flat)
     flat = torch.empty(plan.n, dtype=torch.float32, device=plan.device)
-    plan.pack_grads(flat)
+    if clip is None:
+        plan.pack_grads(flat)
+    else:
+        plan.pack_grads(flat, coef=plan.gradnorm(clip[0], coef_dtype=cd, total_norm=clip[2]), round=master is None)
     flat = aggregator._agg(flat, op="sum", distributed=distributed)
-    plan.run_flatgrad(flat, float(aggregator.world_size) if distributed else 1.0, write=True, write_grads=write_grads,
-                      master=None if master is None else master.buffer)
+    plan.run_flatgrad(flat, divisor, write=True, write_grads=write_grads, master=mbuf)
     return get_n_bits(flat)
 
 

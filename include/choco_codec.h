@@ -927,6 +927,101 @@ int choco_params_sgd_master_scaled(void* const* params, const void* const* grads
                                    float* master, int64_t n, int32_t mode, const float* out,
                                    void* stream);
 
+/* ------------------------------------------- all-reduce SGD: clip and loss scale in the pack
+ * clip_grad_norm_ (pcode/distributed_running_nlp.py:96) and dynamic loss scaling in front of
+ * the centralized branch of SGD.step (pcode/optim/sgd.py:68-92), on passes that step does
+ * anyway: the pack multiplies by the coefficient on its one load of the gradients, the
+ * ranks' overflow flags ride through the all-reduce in ONE extra fp32 slot behind the flat
+ * gradient, and the update skips the step on the device where their sum is not zero.  A
+ * step is
+ *     choco_params_gradnorm_scaled_local      out = [total, gc, found_local, scale]
+ *     choco_params_pack_scaled                flat[0..n) = gc * g;  flat[n] = found_local
+ *     all-reduce SUM of n + 1 floats          (the caller's)
+ *     choco_loss_scale_update                 found = flat[n] != 0; out[2]; the scale update
+ *     choco_params_sgd[_master]_flatgrad_scaled   the update, or nothing where found
+ * and a clip without loss scaling is choco_params_gradnorm, choco_params_pack_scaled with
+ * found_or_null == NULL, the all-reduce of n floats and choco_params_sgd[_master]_flatgrad.
+ *
+ * choco_params_gradnorm_scaled_local: choco_params_gradnorm_scaled without the
+ *   _amp_update_scale_ tail -- the same arguments, checks, norm pass, ordered fp64
+ *   additions, workspace and launch count (choco_params_gradnorm_launches(nseg, 0)), the
+ *   same four floats in out, every line with the rounding documented there; *scale_state
+ *   is read, *growth_tracker is not even read, neither is written: the state must not move
+ *   on one rank's local flag, or the ranks would drift apart.  The last launch is
+ *   "param_gradnorm_scaled_local_total_kernel", an instantiation of its own.
+ *
+ * choco_params_pack_scaled: choco_params_pack's arguments, and coef (DEVICE, one float,
+ *   4-byte aligned: out + 1 of either gradnorm entry point), found_or_null (DEVICE, one
+ *   float, or NULL: out + 2) and round.  c = *coef is one uniform load per workgroup.
+ *   Per element, DT the tensor's dtype:
+ *     round == 1:  flat[i] = (float)rnd_DT(c * g)   one fp32 multiply of c and the widened g,
+ *                                                   narrowed once round-to-nearest-even to DT
+ *                                                   and widened: the product the gclip /
+ *                                                   scaled update kernels form
+ *     round == 0:  flat[i] = c * (float)g           the fp32 product, not narrowed: the
+ *                                                   master path (choco_params_sgd_master_gclip)
+ *   (for an fp32 tensor the two are the same).  inf and NaN gradients keep their kind (an
+ *   inf times c == 0 is a NaN, as in IEEE): a rank that overflowed still packs.  With
+ *   found_or_null != NULL flat holds n + 1 floats and exactly one thread of the layout's
+ *   FIRST launch stores flat[n] = (*found_or_null != 0) ? 1.0f : 0.0f; with NULL flat holds
+ *   n floats and nothing past them is written.  Everything else is choco_params_pack: the
+ *   same tiles at absolute flat offsets, 16-byte vectors only where both sides of a group
+ *   of 8 elements allow them, zero-length tensors, only the layout's own bytes written, no
+ *   device-side table.  Rejected in addition to choco_params_pack's list: coef NULL or
+ *   misaligned; a misaligned found_or_null, or one with a NULL flat; round other than 0 or
+ *   1.  Launches: choco_params_launches(nseg) of "param_pack_scaled_kernel".
+ *
+ * choco_loss_scale_update: found_sum (DEVICE, one float: the address of gsum[n] after the
+ *   all-reduce), the state arguments of choco_params_gradnorm_scaled, out (DEVICE, four
+ *   floats, 4-byte aligned: choco_params_gradnorm_scaled_local's).  ONE launch of one
+ *   64-thread workgroup, "loss_scale_update_kernel", one lane of which runs
+ *     found  = *found_sum != 0              a NaN counts as found
+ *     out[2] = found ? 1.0f : 0.0f          the ranks' common flag
+ *     scale  = *scale_state, then the _amp_update_scale_ lines documented above for
+ *              choco_params_gradnorm_scaled, bit for bit, with plain stores
+ *   Rejected: a NULL or misaligned found_sum, out, scale_state or growth_tracker; growth
+ *   not finite or <= 1; backoff outside (0, 1); interval < 1.
+ *
+ * choco_params_sgd_flatgrad_scaled / choco_params_sgd_master_flatgrad_scaled:
+ *   choco_params_sgd_flatgrad / choco_params_sgd_master_flatgrad with gsum of n + 1 floats
+ *   (never NULL).  gsum[n] is one uniform load per workgroup; gsum[n] != 0 (a NaN included)
+ *   skips the step on the device: the workgroup returns before it touches a parameter, a
+ *   momentum buffer, a gradient or the master copy.  Otherwise exactly the lines of the
+ *   unscaled entry points on gsum[0..n), with their roundings, their argument checks and
+ *   their launch count, choco_params_sgd_flatgrad_launches(nseg), of
+ *   "param_sgd_flatgrad_scaled_kernel" / "param_sgd_master_flatgrad_scaled_kernel",
+ *   instantiations of their own: the unscaled kernels carry neither the pointer nor the
+ *   test.  CHOCO_SGD_F_FIRST stays a host decision: a caller whose step creates momentum
+ *   buffers reads gsum[n] after the all-reduce (the one host read) and does not launch a
+ *   skipped first step. */
+int choco_params_gradnorm_scaled_local(const void* const* grads, const int64_t* lens,
+                                       const int32_t* dtypes, const int32_t* flags, int32_t nseg,
+                                       int64_t n, double max_norm, int32_t coef_dtype,
+                                       const float* scale_state, const int32_t* growth_tracker,
+                                       double growth, double backoff, int32_t interval,
+                                       int32_t has_clip, float* out, float* norms, void* ws,
+                                       size_t ws_bytes, void* stream);
+int choco_params_pack_scaled(const void* const* ptrs, const int64_t* lens, const int32_t* dtypes,
+                             int32_t nseg, float* flat, int64_t n, const float* coef,
+                             const float* found_or_null, int32_t round, void* stream);
+int choco_loss_scale_update(const float* found_sum, float* scale_state, int32_t* growth_tracker,
+                            double growth, double backoff, int32_t interval, float* out,
+                            void* stream);
+/* pcode/optim/sgd.py:68-92 behind pcode/distributed_running_nlp.py:96 */
+int choco_params_sgd_flatgrad_scaled(void* const* params, void* const* grads, void* const* bufs,
+                                     const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                     const double* weight_decay, const double* momentum,
+                                     const double* dampening, const int32_t* flags, int32_t nseg,
+                                     const float* gsum, int64_t n, double divisor, int32_t mode,
+                                     void* stream);
+int choco_params_sgd_master_flatgrad_scaled(void* const* params, void* const* grads,
+                                            void* const* bufs, const int64_t* lens,
+                                            const int32_t* dtypes, const double* lr,
+                                            const double* weight_decay, const double* momentum,
+                                            const double* dampening, const int32_t* flags,
+                                            int32_t nseg, const float* gsum, float* master,
+                                            int64_t n, double divisor, int32_t mode, void* stream);
+
 /* ------------------------------------------- neighbour-weighted model mix
  * The dense line three decentralized optimizers of the reference share,
  *     sum([hat_r.buffer * neighbors_info[r] for r, hat_r in ...])

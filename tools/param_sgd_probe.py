@@ -32,6 +32,21 @@ centralized SGD step with a loopback aggregator (_agg returns the buffer, world 
   kernel_us_step: pack + update; kernel_us_parent: pack + unpack + the SGD kernel, dispatch
   attached, plus div_gpu_us, the torch divide alone between two device events.
 
+Clip / loss-scale rows of the all-reduce step (--rows allreduce_scaled only; ResNet-50 in fp32
+with clip_norm, in fp16 with loss_scale + clip_norm, and that with master weights; the same
+loopback aggregator), both columns in the same process:
+  step_*     utils.allreduce_sgd_step(clip_norm=, loss_scale=): the norm pass, the scaled pack
+             with the flag slot, one small launch for the scale, the update
+  parent_*   what runs without it: torch._amp_foreach_non_finite_check_and_unscale_, a loopback
+             "all-reduce" of found_inf and its .item(), utils.clip_grad_norm_, today's
+             allreduce_sgd_step, torch._amp_update_scale_ (the fp32 row: the clip and the step)
+  kernel_us_step / kernel_us_parent: this library's kernels of one step, dispatch attached and
+             summed, plus torch_gpu_us, torch's two _amp_* ops alone between two device events;
+  kernel_ratio, host_ratio: step / parent; beats_parent_*: whether the ratio is under 0.9, the
+             box-to-box spread of about 10 %.
+The loss scale is 1.0 with growth switched off and the gradients are rewritten by every step
+(the averaged gradient), so the values settle; the time does not depend on them.
+
 Parity rows: elements of p, buf and flat on which three steps of the kernel differ from the
 same three steps of torch's own op sequence on the device, per dtype, on the fixture layout
 (tests/golden/sgd_inputs.npz) and on one tensor of 2^20 elements.
@@ -255,6 +270,77 @@ def measure_allreduce(name, lens, dtype, master, steps, reps):
     return row
 
 
+def measure_allreduce_scaled(name, lens, dtype, master, scaled, steps, reps, max_norm=0.4):
+    n = sum(lens)
+    agg = _Loopback()
+    pa, ga, na = model(lens, dtype)
+    sa = collections.defaultdict(dict)
+    mwa = utils.MasterWeights(ga, na) if master else None
+    scaler = utils.LossScaler(DEV, init_scale=1.0, growth_interval=1 << 30) if scaled else None
+
+    def new_step():
+        utils.allreduce_sgd_step(ga, na, sa, agg, master=mwa, clip_norm=max_norm, loss_scale=scaler)
+
+    pb, gb, nb = model(lens, dtype)
+    sb = collections.defaultdict(dict)
+    mwb = utils.MasterWeights(gb, nb) if master else None
+    grads = [p.grad for p in pb]
+    scale_b, tracker_b = torch.ones(1, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
+    found = torch.zeros(1, device=DEV)
+
+    def torch_ops():
+        found.zero_()
+        torch._amp_foreach_non_finite_check_and_unscale_(grads, found, scale_b.double().reciprocal().float())
+        torch._amp_update_scale_(scale_b, tracker_b, found, 2.0, 0.5, 1 << 30)
+
+    def parent_step():
+        skip = False
+        if scaled:
+            found.zero_()
+            torch._amp_foreach_non_finite_check_and_unscale_(grads, found, scale_b.double().reciprocal().float())
+            skip = bool(agg._agg(found, op="sum").item())  # the second collective and its host sync
+        if not skip:
+            utils.clip_grad_norm_(pb, max_norm)
+            utils.allreduce_sgd_step(gb, nb, sb, agg, master=mwb)
+        if scaled:
+            torch._amp_update_scale_(scale_b, tracker_b, found, 2.0, 0.5, 1 << 30)
+
+    step_host, step_gpu = median_of(new_step, steps, reps)
+    parent_host, parent_gpu = median_of(parent_step, steps, reps)
+    torch_gpu = median_of(torch_ops, steps, reps)[1] if scaled else 0.0
+    tail = "_scaled_kernel" if scaled else "_kernel"
+    upd = "param_sgd_master_flatgrad" if master else "param_sgd_flatgrad"
+    new_names = ["param_sqnorm_kernel", "param_gradnorm_scaled_local_total_kernel" if scaled
+                 else "param_gradnorm_total_kernel", "param_pack_scaled_kernel", upd + tail]
+    new_names += ["loss_scale_update_kernel"] if scaled else []
+    old_names = ["param_sqnorm_kernel", "param_gradnorm_total_kernel", "param_sgd_gclip_kernel", "param_pack_kernel",
+                 upd + "_kernel"]
+    k_new = {nm: kernel_time(new_step, nm)[0] for nm in new_names}
+    k_old = {nm: kernel_time(parent_step, nm)[0] for nm in old_names}
+    row = {"allreduce_scaled": name, "tensors": len(lens), "elements": n, "param_dtype": str(dtype).split(".")[-1],
+           "master": master, "loss_scale": scaled, "clip_norm": max_norm, "steps": steps, "reps": reps,
+           "step_host_us": round(step_host, 1), "step_gpu_us": round(step_gpu, 1),
+           "step_launches": count_launches(new_step),
+           "parent_host_us": round(parent_host, 1), "parent_gpu_us": round(parent_gpu, 1),
+           "parent_launches": count_launches(parent_step), "torch_gpu_us": round(torch_gpu, 2),
+           "host_ratio": round(step_host / parent_host, 3), "beats_parent_host": step_host < 0.9 * parent_host,
+           "kernels_step": {nm: None if t is None else round(t, 2) for nm, t in k_new.items()},
+           "kernels_parent": {nm: None if t is None else round(t, 2) for nm, t in k_old.items()}}
+    if all(k_new.values()) and all(k_old.values()):
+        ks, kp = sum(k_new.values()), sum(k_old.values()) + torch_gpu
+        row.update(kernel_us_step=round(ks, 2), kernel_us_parent=round(kp, 2), kernel_ratio=round(ks / kp, 3),
+                   beats_parent_kernels=ks < 0.9 * kp)
+    return row
+
+
+def allreduce_scaled_layouts():
+    with open(os.path.join(ROOT, "tests", "golden", "layouts.json")) as f:
+        r50 = json.load(f)["resnet50_imagenet"]
+    return [("resnet50_fp32_clip", r50, torch.float32, False, False),
+            ("resnet50_fp16_scaled", r50, torch.float16, False, True),
+            ("resnet50_fp16_scaled_master", r50, torch.float16, True, True)]
+
+
 def allreduce_layouts():
     with open(os.path.join(ROOT, "tests", "golden", "layouts.json")) as f:
         r50 = json.load(f)["resnet50_imagenet"]
@@ -321,16 +407,19 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--rows", choices=["all", "allreduce"], default="all")
+    ap.add_argument("--rows", choices=["all", "allreduce", "allreduce_scaled"], default="all")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "the probe needs a ROCm device"
     rows = []
-    for name, lens, dtype in layouts():
+    for name, lens, dtype, master, scaled in (allreduce_scaled_layouts() if args.rows == "allreduce_scaled" else []):
+        rows.append(measure_allreduce_scaled(name, lens, dtype, master, scaled, args.steps, args.reps))
+        print(json.dumps(rows[-1]), flush=True)
+    for name, lens, dtype in (layouts() if args.rows != "allreduce_scaled" else []):
         # the fp32 ResNet-50 row stays in an all-reduce run: its kernel_tbps_sgd is the yardstick
         if args.rows == "all" or name == "resnet50_fp32":
             rows.append(measure(name, lens, dtype, args.steps, args.reps))
             print(json.dumps(rows[-1]), flush=True)
-    for name, lens, dtype, master in allreduce_layouts():
+    for name, lens, dtype, master in (allreduce_layouts() if args.rows != "allreduce_scaled" else []):
         rows.append(measure_allreduce(name, lens, dtype, master, args.steps, args.reps))
         print(json.dumps(rows[-1]), flush=True)
     for row in (parity_rows() if args.rows == "all" else []):
