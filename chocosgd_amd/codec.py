@@ -1104,6 +1104,7 @@ class ParamSgdPlan:
         self._norms = self._norm_ws = None  # sqnorm()'s output and workspace, allocated on first use
         self._gn_out = self._gn_ws = None   # gradnorm()'s
         self._ls_out = None                 # gradnorm_scaled()'s
+        self._cons_out = self._cons_ws = None  # consensus()'s
         self._refs = [weakref.ref(p) for p in params]
 
     def holds(self, params):
@@ -1445,6 +1446,87 @@ class ParamSgdPlan:
         """One choco_params_ef over the plan's parameter pointers as they stand (params_ef
         describes the arguments)."""
         _ef_call(self.param_ptrs, self.lens, self.dts, self.nseg, self.n, self.device, flat, mode, lr, divisor)
+
+    def consensus(self, xsum, divisor, avg_out=None, master=None, dists=None, want_dist=True):
+        """One choco_params_consensus over the plan's parameter pointers as they stand
+        (params_consensus describes the arguments).  The workspace and the two-element fp32
+        output are the plan's own, allocated on first use; returns that output (overwritten by
+        the next call), or None without want_dist."""
+        L = lib()
+        for name, t in (("xsum", xsum), ("master", master)):
+            if t is None and name == "master":
+                continue
+            _require(t, torch.float32, name)
+            if t.device != self.device or t.numel() != self.n:
+                raise RuntimeError(f"{name} must hold {self.n} elements on {self.device}")
+        mode = (CONS_DIST if want_dist else 0) | (CONS_WRITE_AVG if avg_out is not None else 0)
+        if not mode:
+            raise RuntimeError("params_consensus: nothing to do without want_dist and avg_out")
+        avg_ptrs = None
+        if avg_out is not None:
+            avg_out = list(avg_out)
+            if len(avg_out) != self.nseg:
+                raise RuntimeError(f"avg_out: {len(avg_out)} tensors for {self.nseg} parameters")
+            avg_ptrs = (ctypes.c_void_p * self.nseg)()
+            for i, t in enumerate(avg_out):
+                if not isinstance(t, torch.Tensor) or not self.fits(i, t):
+                    raise RuntimeError(f"avg_out {i} must match its parameter's dtype, device and size, and be "
+                                       "contiguous")
+                avg_ptrs[i] = t.data_ptr()
+        out = ws = None
+        if want_dist:
+            if self._cons_out is None:
+                self._cons_out = torch.empty(2, dtype=torch.float32, device=self.device)
+                self._cons_ws = torch.empty(int(L.choco_params_consensus_workspace_size(self.nseg, self.n)),
+                                            dtype=torch.uint8, device=self.device)
+            out, ws = self._cons_out, self._cons_ws
+            if dists is not None:
+                _require(dists, torch.float32, "dists")
+                if dists.device != self.device or dists.numel() != self.nseg:
+                    raise RuntimeError(f"dists must hold {self.nseg} elements on {self.device}")
+        elif dists is not None:
+            raise RuntimeError("dists without want_dist")
+        _lib.check(L.choco_params_consensus(self.param_ptrs, avg_ptrs, self.lens, self.dts, self.nseg, _ptr(xsum),
+                                            _ptr(master), self.n, float(divisor), mode, _ptr(out), _ptr(dists),
+                                            _ptr(ws), 0 if ws is None else ws.numel(), _stream(self.device)),
+                   "choco_params_consensus")
+        return out
+
+
+# ----------------------------------------------------------------------------- consensus evaluation
+CONS_DIST, CONS_WRITE_AVG = 1, 2  # CHOCO_CONS_*
+
+
+def params_consensus_launches(nseg, want_dist=True):
+    """Launches one params_consensus over `nseg` tensors takes: one per chunk of tensors and,
+    with want_dist, the total launch (writing the averaged model adds none)."""
+    return int(lib().choco_params_consensus_launches(int(nseg), CONS_DIST if want_dist else CONS_WRITE_AVG))
+
+
+def params_consensus(params, xsum, divisor, avg_out=None, master=None, dists=None, want_dist=True, plan=None):
+    """The averaged model and this worker's distance to it from the all-reduced SUM of the packed
+    parameters, one batched launch per chunk of tensors plus one total launch
+    (include/choco_codec.h, choco_params_consensus): per element a = xsum / divisor (a true
+    division), d = a - x with x the parameter widened (or master's value: master is the flat fp32
+    copy of the parameters), and
+        want_dist: out = [sqrt(sum d^2), sqrt(sum a^2)], fp64 sums in a fixed order, rounded once;
+                   dists (fp32 device tensor of nseg) receives the per-tensor sqrt(sum d^2);
+        avg_out:   a list of tensors matching the parameters; avg_out[s] = a narrowed to its
+                   dtype.  It may hold the parameters themselves (agg_model in place): the
+                   distance is then that of the values from before the call.
+    params: tensors laid out back to back in xsum.  Returns (out, plan): out the plan's own
+    two-element device tensor, overwritten by the plan's next call (None without want_dist);
+    pass the plan back in to reuse its tables, workspace and output."""
+    params = list(params)
+    if plan is None:
+        plan = ParamSgdPlan(params)
+    elif not plan.holds(params):
+        raise RuntimeError("the plan was built for another parameter list")
+    for i, p in enumerate(params):
+        if not p.is_contiguous():
+            raise RuntimeError(f"param {i} must be contiguous")
+        plan.param_ptrs[i] = p.data_ptr()
+    return plan.consensus(xsum, divisor, avg_out, master, dists, want_dist), plan
 
 
 # ----------------------------------------------------------------------------- neighbour-weighted mix

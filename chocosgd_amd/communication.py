@@ -154,6 +154,31 @@ class CentralizedAggregation(object):
             return (gathered, req) if async_op else gathered
         raise NotImplementedError
 
+    def agg_model(self, model, op):
+        """Aggregate a model's parameters over the workers (communication.py:114-122), op "avg" or
+        "sum" (anything else raises NotImplementedError, as _agg does): ONE pack, ONE all-reduce of
+        the flat fp32 buffer and one launch per chunk of tensors that writes sum / world_size
+        (or the sum) back, narrowed once to each tensor's dtype (auxiliary.agg_tensors).
+        Differences from the reference, by design: `param.data` is written in place and is not
+        rebound, and the sum over the workers is taken on the values widened to fp32 (the
+        reference all-reduces a 16-bit model in 16 bits).  Tensors of other dtypes go per
+        tensor through _agg."""
+        from . import auxiliary
+        auxiliary.agg_tensors(self, list(model.parameters()), op)
+
+    def agg_grad(self, model, op):
+        """agg_model on the parameters' gradients (communication.py:124-133).  Nothing is
+        skipped: a parameter without a gradient raises, as the reference's attribute access
+        would."""
+        from . import auxiliary
+        if op not in ("avg", "sum"):
+            raise NotImplementedError("op {} is not supported yet.".format(op))
+        grads = []
+        for param in model.parameters():
+            param.grad.data  # no gradient: AttributeError, the reference's
+            grads.append(param.grad)
+        auxiliary.agg_tensors(self, grads, op)
+
     def complete_wait(self, req):
         req.wait()
 

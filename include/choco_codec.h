@@ -1119,6 +1119,70 @@ int choco_params_ef_launches(int32_t nseg);
 int choco_params_ef(void* const* params, const int64_t* lens, const int32_t* dtypes, int32_t nseg,
                     float* flat, int64_t n, int32_t mode, double lr, double divisor, void* stream);
 
+/* ------------------------------------------- consensus evaluation
+ * The reference's --evaluate_consensus (pcode/distributed_running_cv.py:110-115, :239-243):
+ * the model averaged over the workers (agg_model(copy, op="avg"),
+ * pcode/utils/communication.py:114-122) and the L2 distance of this worker's model to it
+ * (get_model_difference, pcode/utils/auxiliary.py:18-34), as ONE launch per chunk of tensors
+ * plus one total launch, straight from the flat fp32 buffer that the all-reduce SUM of the
+ * packed parameters left (no copy of the model, no per-tensor division, subtraction,
+ * concatenation or norm).
+ * The tensor tables are those of choco_params_sgd: tensor s holds lens[s] elements of dtype
+ * dtypes[s] in params[s] (and in avg_out[s]) and owns flat elements [sum(lens[0..s)), +
+ * lens[s]).  xsum is laid out as choco_params_pack lays it out and is read only; master, if
+ * given, is the flat fp32 master copy of the parameters (choco_params_sgd_master) and is read
+ * in their place.  Per element (flat index i, element j of tensor s), every line with exactly
+ * one rounding:
+ *     a = xsum[i] / (float)divisor                  a correctly rounded IEEE division (the one
+ *                                                   of choco_params_sgd_flatgrad), never a
+ *                                                   reciprocal multiply
+ *     x = master ? master[i] : (float)params[s][j]  widening is exact
+ *     d = a - x                                     in fp32: weights2 - weights1
+ *     CHOCO_CONS_DIST:       ssd_s += (double)d * d,  ssa += (double)a * a
+ *     CHOCO_CONS_WRITE_AVG:  avg_out[s][j] = a narrowed round-to-nearest-even to dtypes[s]
+ * avg_out[s] may be params[s] itself (agg_model in place): each element is read before the same
+ * thread writes it, so with both bits set the distance is to the values from before the call.
+ * The sums are fp64, taken in one fixed order that depends on the layout alone (not on the
+ * pointers' alignment nor on how the tensors fall into launches), with no floating-point
+ * atomics: per (8192-element tile, tensor) pair one partial -- a span of at most 1024
+ * elements by one wave (lane l adds elements l, l + 64, ... of the span, the lanes are joined
+ * by the xor butterfly 32, 16, ..., 1), a longer one by the workgroup (the 8-element group at
+ * absolute flat offset 8 g belongs to thread (g - first group of the span) mod 256; groups and
+ * their elements in ascending order; the butterfly per wave, then ((w0 + w1) + w2) + w3) --
+ * then a tensor's partials in ascending tile order, then the tensors in ascending order.
+ *     out[0]   = (float)sqrt(sum_s ssd_s)     the distance to the average
+ *     out[1]   = (float)sqrt(ssa)             the norm of the average (a relative distance
+ *                                             costs nothing more)
+ *     dists[s] = (float)sqrt(ssd_s)           if dists != NULL: which layer has drifted
+ * A zero-length tensor contributes 0.  NaN and inf propagate.  WRITE_AVG alone reads neither
+ * params nor master, needs neither out nor ws and launches no total kernel.  ws holds
+ * choco_params_consensus_workspace_size(nseg, n) bytes (0 for nseg <= 0 or n < 0), 8-byte
+ * aligned; every word of it that is read is written by the same call.  Nothing is allocated or
+ * synchronised.  Pointers need their element's alignment only (16-byte vectors are used where
+ * xsum, master and a tensor's sides allow them).  Every argument is checked before the first
+ * launch without a HIP call -- unknown mode bits or none, a divisor that is zero or not finite
+ * as a float, null lens / dtypes, nseg <= 0, negative lengths or lengths that do not sum to n,
+ * unknown dtype codes, a NULL or misaligned xsum, a misaligned master, out or dists, DIST
+ * with a NULL out, with a NULL, misaligned or too small ws or, without master, a NULL params
+ * table or entry of a non-empty tensor, WRITE_AVG with a NULL avg_out table or entry of a
+ * non-empty tensor, dists without DIST, element pointers off their element's alignment --
+ * and a bad one returns CHOCO_ERR_INVALID and launches nothing.
+ * A call takes choco_params_consensus_launches(nseg, mode) launches (0 for nseg <= 0 or a
+ * bad mode): ceil(nseg / 128) of "param_consensus_kernel" -- 128 tensors' table of two
+ * pointers, an offset and a dtype each fits the 4 KB of kernel arguments -- and, under
+ * DIST, one of "param_consensus_total_kernel". */
+#define CHOCO_CONS_DIST 1
+#define CHOCO_CONS_WRITE_AVG 2
+int choco_params_consensus_launches(int32_t nseg, int32_t mode);
+size_t choco_params_consensus_workspace_size(int32_t nseg, int64_t n);
+/* pcode/utils/communication.py:114-122, pcode/utils/auxiliary.py:18-34 */
+int choco_params_consensus(const void* const* params, void* const* avg_out,
+                           const int64_t* lens, const int32_t* dtypes, int32_t nseg,
+                           const float* xsum, const float* master /* or NULL */, int64_t n,
+                           double divisor, int32_t mode,
+                           float* out /* 2 floats */, float* dists /* nseg or NULL */,
+                           void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------- fused gossip step + compress
  * ParallelCHOCO_V.step's update_params_from_neighbor -> compress sequence
  * (pcode/optim/parallel_choco_v.py:116-142 -> :229-240, optim/utils.py:67-72) in
