@@ -1255,6 +1255,14 @@ class ParamSgdPlan:
             raise RuntimeError(f"gclip must be gradnorm()'s two-element tensor on {self.device}")
         return gclip.data_ptr() + 4
 
+    def _sgd(self, variant, *tail):
+        """One call of the entry point choco_params_sgd<variant>: the eleven table arguments as
+        they stand, then `tail`, then the stream."""
+        name = "choco_params_sgd" + variant
+        _lib.check(getattr(lib(), name)(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts, self.lr,
+                                        self.weight_decay, self.momentum, self.dampening, self.flags, self.nseg,
+                                        *tail, _stream(self.device)), name)
+
     def run(self, flat=None, grad_mode=False, write=True, norms=None, clip_threshold=None, add_flat=False,
             gclip=None, write_clipped=False, scaled=None):
         """One choco_params_sgd over the tables as they stand.  apply mode (grad_mode False):
@@ -1282,15 +1290,11 @@ class ParamSgdPlan:
                 raise RuntimeError(f"flat must hold {self.n} elements on {self.device}")
         mode = (SGD_MODE_GRAD | (SGD_MODE_WRITE_GRADS if write else 0)) if grad_mode else \
             (SGD_MODE_WRITE_PARAMS if write else 0)
+        clipped = SGD_MODE_WRITE_CLIPPED if write_clipped else 0
         if scaled is not None:
             out = self._scaled_ptr(scaled, gclip is not None or norms is not None or clip_threshold is not None
                                    or add_flat or grad_mode)
-            _lib.check(lib().choco_params_sgd_scaled(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens,
-                                                     self.dts, self.lr, self.weight_decay, self.momentum,
-                                                     self.dampening, self.flags, self.nseg, _ptr(flat), self.n,
-                                                     mode | (SGD_MODE_WRITE_CLIPPED if write_clipped else 0), out,
-                                                     _stream(self.device)), "choco_params_sgd_scaled")
-            return
+            return self._sgd("_scaled", _ptr(flat), self.n, mode | clipped, out)
         if gclip is None and write_clipped:
             raise RuntimeError("write_clipped needs gclip (gradnorm()'s tensor)")
         if gclip is not None:
@@ -1299,13 +1303,7 @@ class ParamSgdPlan:
                                    "add_flat (DGC's per-tensor clipping)")
             if write_clipped and grad_mode:
                 raise RuntimeError("write_clipped is for apply mode: grad mode writes d_p into the grads")
-            _lib.check(lib().choco_params_sgd_gclip(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts,
-                                                    self.lr, self.weight_decay, self.momentum, self.dampening,
-                                                    self.flags, self.nseg, _ptr(flat), self.n,
-                                                    mode | (SGD_MODE_WRITE_CLIPPED if write_clipped else 0),
-                                                    self._coef_ptr(gclip), _stream(self.device)),
-                       "choco_params_sgd_gclip")
-            return
+            return self._sgd("_gclip", _ptr(flat), self.n, mode | clipped, self._coef_ptr(gclip))
         if clip_threshold is not None and norms is None:
             raise RuntimeError("clip_threshold needs norms (sqnorm()'s, or recorded ones): nothing would be clipped")
         if norms is not None or add_flat:
@@ -1315,16 +1313,9 @@ class ParamSgdPlan:
                     raise RuntimeError(f"norms must hold {self.nseg} elements on {self.device}")
                 if clip_threshold is None:
                     raise RuntimeError("norms needs a clip_threshold")
-            _lib.check(lib().choco_params_sgd_clip(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts,
-                                                   self.lr, self.weight_decay, self.momentum, self.dampening,
-                                                   self.flags, self.nseg, _ptr(flat), self.n,
-                                                   mode | (SGD_MODE_ADD_FLAT if add_flat else 0), _ptr(norms),
-                                                   float(clip_threshold) if norms is not None else 0.0,
-                                                   _stream(self.device)), "choco_params_sgd_clip")
-            return
-        _lib.check(lib().choco_params_sgd(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts, self.lr,
-                                          self.weight_decay, self.momentum, self.dampening, self.flags, self.nseg,
-                                          _ptr(flat), self.n, mode, _stream(self.device)), "choco_params_sgd")
+            return self._sgd("_clip", _ptr(flat), self.n, mode | (SGD_MODE_ADD_FLAT if add_flat else 0), _ptr(norms),
+                             float(clip_threshold) if norms is not None else 0.0)
+        self._sgd("", _ptr(flat), self.n, mode)
 
     def fits_master_buf(self, i, t):
         """Whether tensor t can stand as the fp32 momentum buffer of parameter i in a master
@@ -1348,30 +1339,14 @@ class ParamSgdPlan:
         _require(master, torch.float32, "master")
         if master.device != self.device or master.numel() != self.n:
             raise RuntimeError(f"master must hold {self.n} elements on {self.device}")
+        mode = (SGD_MODE_WRITE_PARAMS if write else 0) | (SGD_MODE_WRITE_CLIPPED if write_clipped else 0)
         if scaled is not None:
-            out = self._scaled_ptr(scaled, gclip is not None)
-            mode = (SGD_MODE_WRITE_PARAMS if write else 0) | (SGD_MODE_WRITE_CLIPPED if write_clipped else 0)
-            _lib.check(lib().choco_params_sgd_master_scaled(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens,
-                                                            self.dts, self.lr, self.weight_decay, self.momentum,
-                                                            self.dampening, self.flags, self.nseg, _ptr(master),
-                                                            self.n, mode, out, _stream(self.device)),
-                       "choco_params_sgd_master_scaled")
-            return
+            return self._sgd("_master_scaled", _ptr(master), self.n, mode, self._scaled_ptr(scaled, gclip is not None))
         if gclip is None and write_clipped:
             raise RuntimeError("write_clipped needs gclip (gradnorm()'s tensor)")
         if gclip is not None:
-            mode = (SGD_MODE_WRITE_PARAMS if write else 0) | (SGD_MODE_WRITE_CLIPPED if write_clipped else 0)
-            _lib.check(lib().choco_params_sgd_master_gclip(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens,
-                                                           self.dts, self.lr, self.weight_decay, self.momentum,
-                                                           self.dampening, self.flags, self.nseg, _ptr(master), self.n,
-                                                           mode, self._coef_ptr(gclip), _stream(self.device)),
-                       "choco_params_sgd_master_gclip")
-            return
-        _lib.check(lib().choco_params_sgd_master(self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts,
-                                                 self.lr, self.weight_decay, self.momentum, self.dampening,
-                                                 self.flags, self.nseg, _ptr(master), self.n,
-                                                 SGD_MODE_WRITE_PARAMS if write else 0, _stream(self.device)),
-                   "choco_params_sgd_master")
+            return self._sgd("_master_gclip", _ptr(master), self.n, mode, self._coef_ptr(gclip))
+        self._sgd("_master", _ptr(master), self.n, mode)
 
     def pack_grads(self, flat, coef=None, found=None, round=True):
         """One choco_params_pack of the gradients behind `grad_ptrs` as they stand into `flat`
@@ -1424,17 +1399,12 @@ class ParamSgdPlan:
             raise RuntimeError(f"gsum must hold {want} elements on {self.device}")
         tail = "_scaled" if found_slot else ""
         mode = (SGD_MODE_WRITE_PARAMS if write else 0) | (SGD_MODE_WRITE_GRADS if write_grads else 0)
-        head = (self.param_ptrs, self.grad_ptrs, self.buf_ptrs, self.lens, self.dts, self.lr, self.weight_decay,
-                self.momentum, self.dampening, self.flags, self.nseg, _ptr(gsum))
         if master is None:
-            name = "choco_params_sgd_flatgrad" + tail
-            _lib.check(getattr(lib(), name)(*head, self.n, float(divisor), mode, _stream(self.device)), name)
-            return
+            return self._sgd("_flatgrad" + tail, _ptr(gsum), self.n, float(divisor), mode)
         _require(master, torch.float32, "master")
         if master.device != self.device or master.numel() != self.n:
             raise RuntimeError(f"master must hold {self.n} elements on {self.device}")
-        name = "choco_params_sgd_master_flatgrad" + tail
-        _lib.check(getattr(lib(), name)(*head, _ptr(master), self.n, float(divisor), mode, _stream(self.device)), name)
+        self._sgd("_master_flatgrad" + tail, _ptr(gsum), _ptr(master), self.n, float(divisor), mode)
 
     def mix(self, srcs, weights, lr=0.0, mode=0, ext_a=0.0, ext_b=0.0, flat_out=None, x_out=None):
         """One choco_params_mix over the plan's parameter and gradient pointers as they stand

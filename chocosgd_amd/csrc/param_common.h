@@ -1,6 +1,7 @@
 // Helpers shared by the kernels that walk a table of parameter tensors in the kernel
-// arguments (params.hip: pack / unpack; sgd.hip: the SGD update fused with the pack; mix.hip:
-// the neighbour-weighted model mix): the tile geometry, the 16-bit conversions, the 16-byte
+// arguments (params.hip: pack / unpack; sgd.hip: the SGD update fused with the pack;
+// gradnorm.hip: the gradient norms beside it; mix.hip: the neighbour-weighted model mix): the
+// tile geometry, the SGD table's flag bits, the 16-bit conversions, the 16-byte
 // non-temporal store, the element / group moves and the tile walk's search.
 #pragma once
 
@@ -11,6 +12,10 @@ namespace choco {
 constexpr int kPbThreads = 256;
 constexpr int kPbGroup = 8;                                          // elements per group
 constexpr int64_t kPbTile = (int64_t)kPbThreads * 4 * kPbGroup;      // 8192 flat elements per workgroup
+
+// flags of the SGD and norm tables (sgd.hip, gradnorm.hip): the ABI's three CHOCO_SGD_F_* bits,
+// then what the host derives from the doubles
+constexpr uint32_t kSgdHasWd = 8u, kSgdHasMom = 16u;
 
 typedef unsigned short choco_u16x8 __attribute__((ext_vector_type(8)));
 

@@ -1,7 +1,8 @@
 """The all-reduce SGD step with a global-norm clip and dynamic loss scaling on the device: the
 scaled pack (csrc/params.hip, param_pack_scaled_kernel), the norm launch that leaves the
 loss-scale state alone, the flat-gradient kernels that skip on the all-reduced flag
-(csrc/sgd.hip), loss_scale_update_kernel, and utils.allreduce_sgd_step(clip_norm=, loss_scale=).
+(csrc/sgd.hip), loss_scale_update_kernel (csrc/gradnorm.hip), and
+utils.allreduce_sgd_step(clip_norm=, loss_scale=).
 
 Everything is compared bit for bit against the numpy model (tests/_allreduce_scaled_oracle.py),
 the torch loop, torch's own _amp_* ops and the reference's recorded steps.  Whole storages are
