@@ -38,7 +38,6 @@
 // the parameters are read only.
 #include "param_common.h"
 
-#include <algorithm>
 #include <cmath>
 
 namespace choco {
@@ -89,6 +88,9 @@ CHOCO_DEV void cons_elem(const ConsOp& o, int64_t i, int64_t j, double& sd, doub
 // Flat elements [a, b) of a tensor at flat offset o0, a < b inside this workgroup's tile, by the
 // whole workgroup: thread tid owns groups (a >> 3) + tid, + 256, ...
 // vec: every side the tensor touches is 16-byte aligned at every whole group's start.
+// Not the shared span_walk: off the 16-byte grid that walk hands a thread elements a + tid,
+// a + tid + 256, ..., so which values a thread adds, and in what order, would depend on the
+// pointers' alignment; here the group's owner takes it either way and the fp64 order stays fixed.
 template <int DT, bool DIST>
 CHOCO_DEV void cons_span(const ConsOp& o, int64_t o0, int64_t a, int64_t b, bool vec, double& sd, double& sa) {
   const int tid = threadIdx.x;
@@ -154,21 +156,15 @@ __global__ __launch_bounds__(kPbThreads) void param_consensus_kernel(const ConsT
     }
   }
   const int64_t tile = tile0 + blockIdx.x;
-  int64_t tlo, thi;
-  const int s0 = tile_first_tensor(tb.off, nt, tile, tlo, thi);
-  if (s0 < 0) return;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   ConsOp o;
   o.xsum = xsum; o.master = master; o.div = div;
   o.wr = (mode & CHOCO_CONS_WRITE_AVG) != 0;
   const bool rd_p = DIST && master == nullptr;
   int nshort = 0;
-  for (int s = s0; s < nt; ++s) {
-    const int64_t o0 = tb.off[s];
-    if (o0 >= thi) break;
-    const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);
-    if (a >= b) continue;  // zero-length tensor
+  tile_walk(tb.off, nt, tile, [&](int s, int64_t a, int64_t b) {
     const int dt = tb.dt[s];
+    const int64_t o0 = tb.off[s];
     o.p = tb.p[s];
     o.q = tb.q[s];
     double sd = 0.0, sa = 0.0;
@@ -176,28 +172,22 @@ __global__ __launch_bounds__(kPbThreads) void param_consensus_kernel(const ConsT
       // short spans are taken by the waves in turn, with no barrier
       const bool mine = (nshort & 3) == wave;
       ++nshort;
-      if (!mine) continue;
-      if (dt == CHOCO_DT_F32) cons_wave<CHOCO_DT_F32, DIST>(o, o0, a, b, lane, sd, sa);
-      else if (dt == CHOCO_DT_BF16) cons_wave<CHOCO_DT_BF16, DIST>(o, o0, a, b, lane, sd, sa);
-      else cons_wave<CHOCO_DT_F16, DIST>(o, o0, a, b, lane, sd, sa);
+      if (!mine) return;
+      for_dtype(dt, [&](auto DT) { cons_wave<DT, DIST>(o, o0, a, b, lane, sd, sa); });
       sd = wave_sum(sd);
       sa = wave_sum(sa);
       if (lane == 0) {
         slots_d[tile + seg0 + s] = sd;
         slots_a[tile + seg0 + s] = sa;
       }
-      continue;
+      return;
     }
-    // xsum + 4 e (and master + 4 e) is 16-byte aligned at every group start e (a multiple of 8)
-    // when xsum is; a tensor's side r + esz (e - o0) is when r - esz o0 is
-    const uintptr_t esz = dt == CHOCO_DT_F32 ? 4u : 2u, back = esz * (uintptr_t)o0;
+    const uintptr_t esz = dtype_size(dt);
     uintptr_t mis = 0;
-    if (rd_p) mis |= reinterpret_cast<uintptr_t>(o.p) - back;
-    if (o.wr) mis |= reinterpret_cast<uintptr_t>(o.q) - back;
-    const bool vec = al16 == 3 && (mis & 15u) == 0;
-    if (dt == CHOCO_DT_F32) cons_span<CHOCO_DT_F32, DIST>(o, o0, a, b, vec, sd, sa);
-    else if (dt == CHOCO_DT_BF16) cons_span<CHOCO_DT_BF16, DIST>(o, o0, a, b, vec, sd, sa);
-    else cons_span<CHOCO_DT_F16, DIST>(o, o0, a, b, vec, sd, sa);
+    if (rd_p) mis |= mis16(o.p, esz, o0);
+    if (o.wr) mis |= mis16(o.q, esz, o0);
+    const bool vec = al16 == 3 && on_grid16(mis);
+    for_dtype(dt, [&](auto DT) { cons_span<DT, DIST>(o, o0, a, b, vec, sd, sa); });
     if (DIST) {
       sd = wave_sum(sd);
       sa = wave_sum(sa);
@@ -212,7 +202,7 @@ __global__ __launch_bounds__(kPbThreads) void param_consensus_kernel(const ConsT
       }
       __syncthreads();  // red is reused by the next long span
     }
-  }
+  });
 }
 
 // d = vd[0] + vd[1] + ... + vd[cnt - 1] and a = va[0] + ... + va[cnt - 1], each added in that order
@@ -297,7 +287,7 @@ constexpr int32_t kConsModes = CHOCO_CONS_DIST | CHOCO_CONS_WRITE_AVG;
 
 static int cons_launches(int32_t nseg, int32_t mode) {
   if (nseg <= 0 || (mode & ~kConsModes) != 0 || (mode & kConsModes) == 0) return 0;
-  return (nseg + kConsCap - 1) / kConsCap + ((mode & CHOCO_CONS_DIST) ? 1 : 0);
+  return chunk_launches(nseg, kConsCap) + ((mode & CHOCO_CONS_DIST) ? 1 : 0);
 }
 // two partials per (tile, tensor) pair, two fp64 sums per tensor, the meta words
 static size_t cons_slots(int32_t nseg, int64_t n) { return (size_t)(n / kPbTile + 1) + (size_t)nseg; }
@@ -331,45 +321,41 @@ static int cons_check(const ConsArgs& a) {
   const bool dist = (a.mode & CHOCO_CONS_DIST) != 0, wr = (a.mode & CHOCO_CONS_WRITE_AVG) != 0;
   const bool rd_p = dist && !a.master;
   CHOCO_REQUIRE(a.lens && a.dtypes, "null table argument: lens / dtypes");
-  CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
-  CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
-  CHOCO_REQUIRE(a.params || !rd_p, "DIST without a master copy needs the params table");
-  CHOCO_REQUIRE(a.avg_out || !wr, "WRITE_AVG with a null avg_out table");
-  // tested as the kernel divides: by the fp32 value
-  CHOCO_REQUIRE(std::isfinite(a.divisor) && (float)a.divisor != 0.0f && std::isfinite((float)a.divisor),
-                "divisor must be finite and nonzero as an fp32 value, got %g", a.divisor);
-  CHOCO_REQUIRE(a.xsum || a.n == 0, "xsum is null");
-  CHOCO_REQUIRE(aligned4(a.xsum), "xsum must be 4-byte aligned");
-  CHOCO_REQUIRE(aligned4(a.master), "master must be 4-byte aligned");
-  CHOCO_REQUIRE(aligned4(a.dists), "dists must be 4-byte aligned");
-  if (dist) {
-    CHOCO_REQUIRE(a.out && aligned4(a.out), "out must be a 4-byte aligned device pointer");
-    CHOCO_REQUIRE(a.ws && (reinterpret_cast<uintptr_t>(a.ws) & 7u) == 0,
-                  "the workspace (ws) must be an 8-byte aligned device pointer");
-    CHOCO_REQUIRE(a.ws_bytes >= cons_ws_bytes(a.nseg, a.n), "workspace (ws) too small: %zu bytes, need %zu",
-                  a.ws_bytes, cons_ws_bytes(a.nseg, a.n));
-  } else {
-    CHOCO_REQUIRE(!a.dists, "dists without CHOCO_CONS_DIST");
-  }
-  int64_t sum = 0;
-  for (int32_t s = 0; s < a.nseg; ++s) {
-    const int i = (int)s;
-    CHOCO_REQUIRE(a.lens[s] >= 0, "tensor %d: negative length", i);
-    CHOCO_REQUIRE(a.dtypes[s] >= CHOCO_DT_F32 && a.dtypes[s] <= CHOCO_DT_F16, "tensor %d: unknown dtype code %d", i,
-                  (int)a.dtypes[s]);
-    CHOCO_REQUIRE(a.lens[s] <= a.n - sum, "the lengths (lens) add up to more than n = %lld", (long long)a.n);
-    sum += a.lens[s];
-    const uintptr_t esz = a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u;
-    CHOCO_REQUIRE(!a.params || (reinterpret_cast<uintptr_t>(a.params[s]) & (esz - 1)) == 0,
-                  "tensor %d: params pointer not aligned to its element size", i);
-    CHOCO_REQUIRE(!a.avg_out || (reinterpret_cast<uintptr_t>(a.avg_out[s]) & (esz - 1)) == 0,
-                  "tensor %d: avg_out pointer not aligned to its element size", i);
-    if (a.lens[s] == 0) continue;
-    CHOCO_REQUIRE(!rd_p || a.params[s], "tensor %d: null params pointer", i);
-    CHOCO_REQUIRE(!wr || a.avg_out[s], "tensor %d: null avg_out pointer with WRITE_AVG", i);
-  }
-  CHOCO_REQUIRE(sum == a.n, "the lengths (lens) add up to %lld, n is %lld", (long long)sum, (long long)a.n);
-  return CHOCO_OK;
+  return layout_check(
+      a.lens, a.dtypes, a.nseg, a.n,
+      [&]() -> int {
+        CHOCO_REQUIRE(a.params || !rd_p, "DIST without a master copy needs the params table");
+        CHOCO_REQUIRE(a.avg_out || !wr, "WRITE_AVG with a null avg_out table");
+        // tested as the kernel divides: by the fp32 value
+        CHOCO_REQUIRE(std::isfinite(a.divisor) && (float)a.divisor != 0.0f && std::isfinite((float)a.divisor),
+                      "divisor must be finite and nonzero as an fp32 value, got %g", a.divisor);
+        CHOCO_REQUIRE(a.xsum || a.n == 0, "xsum is null");
+        CHOCO_REQUIRE(aligned4(a.xsum), "xsum must be 4-byte aligned");
+        CHOCO_REQUIRE(aligned4(a.master), "master must be 4-byte aligned");
+        CHOCO_REQUIRE(aligned4(a.dists), "dists must be 4-byte aligned");
+        if (dist) {
+          CHOCO_REQUIRE(a.out && aligned4(a.out), "out must be a 4-byte aligned device pointer");
+          CHOCO_REQUIRE(a.ws && (reinterpret_cast<uintptr_t>(a.ws) & 7u) == 0,
+                        "the workspace (ws) must be an 8-byte aligned device pointer");
+          CHOCO_REQUIRE(a.ws_bytes >= cons_ws_bytes(a.nseg, a.n), "workspace (ws) too small: %zu bytes, need %zu",
+                        a.ws_bytes, cons_ws_bytes(a.nseg, a.n));
+        } else {
+          CHOCO_REQUIRE(!a.dists, "dists without CHOCO_CONS_DIST");
+        }
+        return CHOCO_OK;
+      },
+      [&](int32_t s, uintptr_t esz) -> int {
+        const int i = (int)s;
+        CHOCO_REQUIRE(!a.params || elem_aligned(a.params[s], esz),
+                      "tensor %d: params pointer not aligned to its element size", i);
+        CHOCO_REQUIRE(!a.avg_out || elem_aligned(a.avg_out[s], esz),
+                      "tensor %d: avg_out pointer not aligned to its element size", i);
+        if (a.lens[s] == 0) return CHOCO_OK;
+        CHOCO_REQUIRE(!rd_p || a.params[s], "tensor %d: null params pointer", i);
+        CHOCO_REQUIRE(!wr || a.avg_out[s], "tensor %d: null avg_out pointer with WRITE_AVG", i);
+        return CHOCO_OK;
+      },
+      "lengths (lens)");
 }
 
 static int cons_run(const ConsArgs& a, hipStream_t st) {
@@ -394,32 +380,22 @@ static int cons_run(const ConsArgs& a, hipStream_t st) {
   const int32_t al16 = (aligned16(a.xsum) ? 1 : 0) | (!a.master || !dist || aligned16(a.master) ? 2 : 0);
   const float* master = dist ? a.master : nullptr;  // WRITE_AVG alone reads neither master nor params
   ConsTable tb;
-  int64_t base = 0;
-  for (int32_t s0 = 0; s0 < a.nseg; s0 += kConsCap) {
-    const int nt = std::min<int32_t>(kConsCap, a.nseg - s0);
-    tb.nt = nt;
-    tb.off[0] = base;
+  CHOCO_TRY(for_chunks<kConsCap>(a.lens, a.nseg, tb.off, [&](const Chunk& c) -> int {
+    tb.nt = c.nt;
     for (int i = 0; i < kConsCap; ++i) {
-      const bool in = i < nt;
-      const int32_t s = s0 + i;
-      tb.p[i] = in && rd_p ? a.params[s] : nullptr;
-      tb.q[i] = in && wr ? a.avg_out[s] : nullptr;
-      tb.dt[i] = in ? (uint8_t)a.dtypes[s] : (uint8_t)0;
-      base += in ? a.lens[s] : 0;
-      tb.off[i + 1] = base;
+      const bool in = i < c.nt;
+      tb.p[i] = in && rd_p ? a.params[c.s0 + i] : nullptr;
+      tb.q[i] = in && wr ? a.avg_out[c.s0 + i] : nullptr;
+      tb.dt[i] = in ? (uint8_t)a.dtypes[c.s0 + i] : (uint8_t)0;
     }
-    // the tiles the chunk [off[0], off[nt]) touches; an empty chunk still takes its launch
-    const int64_t tile0 = tb.off[0] / kPbTile;
-    const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
     if (dist)
-      CHOCO_TRY(CHOCO_LAUNCH("param_consensus_kernel", "param_consensus_kernel", param_consensus_kernel<true>,
-                             dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.xsum, master, slots_d, slots_a,
-                             meta + 2 * (size_t)s0, tile0, s0, div, a.mode, al16));
-    else
-      CHOCO_TRY(CHOCO_LAUNCH("param_consensus_kernel", "param_consensus_kernel<write>", param_consensus_kernel<false>,
-                             dim3((unsigned)tiles), dim3(kPbThreads), st, tb, a.xsum, master, slots_d, slots_a, meta,
-                             tile0, s0, div, a.mode, al16));
-  }
+      return CHOCO_LAUNCH("param_consensus_kernel", "param_consensus_kernel", param_consensus_kernel<true>,
+                          dim3((unsigned)c.tiles), dim3(kPbThreads), st, tb, a.xsum, master, slots_d, slots_a,
+                          meta + 2 * (size_t)c.s0, c.tile0, c.s0, div, a.mode, al16);
+    return CHOCO_LAUNCH("param_consensus_kernel", "param_consensus_kernel<write>", param_consensus_kernel<false>,
+                        dim3((unsigned)c.tiles), dim3(kPbThreads), st, tb, a.xsum, master, slots_d, slots_a, meta,
+                        c.tile0, c.s0, div, a.mode, al16);
+  }));
   if (dist)
     CHOCO_TRY(CHOCO_LAUNCH("param_consensus_total_kernel", "param_consensus_total_kernel",
                            param_consensus_total_kernel, dim3(1), dim3(kConsTotalThreads), st,

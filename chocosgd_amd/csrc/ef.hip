@@ -28,7 +28,6 @@
 // written.
 #include "param_common.h"
 
-#include <algorithm>
 #include <cmath>
 
 namespace choco {
@@ -81,6 +80,12 @@ CHOCO_DEV void ef_elem(const EfOp& o, void* p, int64_t i, int64_t j) {
 
 // Flat elements [a, b) of a tensor at flat offset o0, a < b inside this workgroup's tile.
 // vec: flat and the tensor's side are 16-byte aligned at every whole group's start.
+// The lines of param_common.h's span_walk, kept as a function of this kernel's own: with
+// ef_elem and the group step as a body for span_walk (the same loads, stores and arithmetic in
+// another schedule) the fp32 ResNet-50 APPLY launch took 82.4 to 83.9 us against the 75.9 to
+// 78.3 of this form, alternated in one visit -- and ACCUM 68.9 to 70.5 against 76.3 to 76.6,
+// APPLY | DIV | SCALE 102.7 to 109.5 against 112.0 to 118.2; bf16 the same either way.  One
+// kernel holds the three modes, so the form that slows none of them stays.
 template <int DT>
 CHOCO_DEV void ef_span(const EfOp& o, void* p, int64_t o0, int64_t a, int64_t b, bool vec) {
   const int tid = threadIdx.x;
@@ -114,34 +119,19 @@ CHOCO_DEV void ef_span(const EfOp& o, void* p, int64_t o0, int64_t a, int64_t b,
 // flat16: flat is 16-byte aligned
 __global__ __launch_bounds__(kPbThreads) void param_ef_kernel(const EfTable tb, float* flat, int64_t tile0, float nlr,
                                                               float div, int32_t mode, int32_t flat16) {
-  const int nt = tb.nt;
-  int64_t tlo, thi;
-  const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
-  if (s0 < 0) return;
   EfOp o;
   o.flat = flat; o.nlr = nlr; o.div = div;
   o.accum = (mode & CHOCO_EF_ACCUM) != 0;
   o.do_div = (mode & CHOCO_EF_DIV) != 0;
   o.scale = (mode & CHOCO_EF_SCALE) != 0;
-  for (int s = s0; s < nt; ++s) {
-    const int64_t o0 = tb.off[s];
-    if (o0 >= thi) break;
-    const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);
-    if (a >= b) continue;  // zero-length tensor
+  tile_walk(tb.off, tb.nt, tile0 + blockIdx.x, [&](int s, int64_t a, int64_t b) {
     const int dt = tb.dt[s];
     void* p = tb.p[s];
-    // the tensor's side q + esz (e - o0) is 16-byte aligned at every group start e (a multiple
-    // of 8) when q - esz o0 is, esz e being a multiple of 16
-    const uintptr_t esz = dt == CHOCO_DT_F32 ? 4u : 2u;
-    const uintptr_t mis = reinterpret_cast<uintptr_t>(p) - esz * (uintptr_t)o0;
-    const bool vec = flat16 && (mis & 15u) == 0;
-    if (dt == CHOCO_DT_F32) ef_span<CHOCO_DT_F32>(o, p, o0, a, b, vec);
-    else if (dt == CHOCO_DT_BF16) ef_span<CHOCO_DT_BF16>(o, p, o0, a, b, vec);
-    else ef_span<CHOCO_DT_F16>(o, p, o0, a, b, vec);
-  }
+    const int64_t o0 = tb.off[s];
+    const bool vec = flat16 && on_grid16(mis16(p, dtype_size(dt), o0));
+    for_dtype(dt, [&](auto DT) { ef_span<DT>(o, p, o0, a, b, vec); });
+  });
 }
-
-static int ef_launches(int32_t nseg) { return nseg <= 0 ? 0 : (nseg + kEfCap - 1) / kEfCap; }
 
 struct EfArgs {
   void* const* params;
@@ -157,34 +147,27 @@ struct EfArgs {
 // Every argument is checked before the first launch, with no HIP call.
 static int ef_check(const EfArgs& a) {
   CHOCO_REQUIRE(a.params && a.lens && a.dtypes, "null table argument");
-  CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
-  CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
-  constexpr int32_t kModes = CHOCO_EF_ACCUM | CHOCO_EF_APPLY | CHOCO_EF_DIV | CHOCO_EF_SCALE;
-  CHOCO_REQUIRE((a.mode & ~kModes) == 0, "unknown mode bits 0x%x", (unsigned)a.mode);
-  const bool accum = (a.mode & CHOCO_EF_ACCUM) != 0, apply = (a.mode & CHOCO_EF_APPLY) != 0;
-  CHOCO_REQUIRE(accum != apply, "exactly one of ACCUM and APPLY, got mode 0x%x", (unsigned)a.mode);
-  CHOCO_REQUIRE(apply || !(a.mode & (CHOCO_EF_DIV | CHOCO_EF_SCALE)), "DIV and SCALE belong to APPLY");
-  CHOCO_REQUIRE(a.flat, "flat is null");
-  CHOCO_REQUIRE(aligned4(a.flat), "flat must be 4-byte aligned");
-  if (a.mode & CHOCO_EF_DIV)
-    CHOCO_REQUIRE(std::isfinite(a.divisor) && (float)a.divisor != 0.0f && std::isfinite((float)a.divisor),
-                  "divisor must be finite and nonzero, got %g", a.divisor);
-  if (a.mode & CHOCO_EF_SCALE) CHOCO_REQUIRE(std::isfinite(a.lr), "lr must be finite, got %g", a.lr);
-  int64_t sum = 0;
-  for (int32_t s = 0; s < a.nseg; ++s) {
-    const int i = (int)s;
-    CHOCO_REQUIRE(a.lens[s] >= 0, "tensor %d: negative length", i);
-    CHOCO_REQUIRE(a.dtypes[s] >= CHOCO_DT_F32 && a.dtypes[s] <= CHOCO_DT_F16, "tensor %d: unknown dtype code %d", i,
-                  (int)a.dtypes[s]);
-    CHOCO_REQUIRE(a.lens[s] <= a.n - sum, "the lengths add up to more than n = %lld", (long long)a.n);
-    sum += a.lens[s];
-    const uintptr_t esz = a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u;
-    CHOCO_REQUIRE((reinterpret_cast<uintptr_t>(a.params[s]) & (esz - 1)) == 0,
-                  "tensor %d: pointer not aligned to its element size", i);
-    CHOCO_REQUIRE(a.lens[s] == 0 || a.params[s], "tensor %d: null param pointer", i);
-  }
-  CHOCO_REQUIRE(sum == a.n, "the lengths add up to %lld, n is %lld", (long long)sum, (long long)a.n);
-  return CHOCO_OK;
+  return layout_check(
+      a.lens, a.dtypes, a.nseg, a.n,
+      [&]() -> int {
+        constexpr int32_t kModes = CHOCO_EF_ACCUM | CHOCO_EF_APPLY | CHOCO_EF_DIV | CHOCO_EF_SCALE;
+        CHOCO_REQUIRE((a.mode & ~kModes) == 0, "unknown mode bits 0x%x", (unsigned)a.mode);
+        const bool accum = (a.mode & CHOCO_EF_ACCUM) != 0, apply = (a.mode & CHOCO_EF_APPLY) != 0;
+        CHOCO_REQUIRE(accum != apply, "exactly one of ACCUM and APPLY, got mode 0x%x", (unsigned)a.mode);
+        CHOCO_REQUIRE(apply || !(a.mode & (CHOCO_EF_DIV | CHOCO_EF_SCALE)), "DIV and SCALE belong to APPLY");
+        CHOCO_REQUIRE(a.flat, "flat is null");
+        CHOCO_REQUIRE(aligned4(a.flat), "flat must be 4-byte aligned");
+        if (a.mode & CHOCO_EF_DIV)
+          CHOCO_REQUIRE(std::isfinite(a.divisor) && (float)a.divisor != 0.0f && std::isfinite((float)a.divisor),
+                        "divisor must be finite and nonzero, got %g", a.divisor);
+        if (a.mode & CHOCO_EF_SCALE) CHOCO_REQUIRE(std::isfinite(a.lr), "lr must be finite, got %g", a.lr);
+        return CHOCO_OK;
+      },
+      [&](int32_t s, uintptr_t esz) -> int {
+        CHOCO_REQUIRE(elem_aligned(a.params[s], esz), "tensor %d: pointer not aligned to its element size", (int)s);
+        CHOCO_REQUIRE(a.lens[s] == 0 || a.params[s], "tensor %d: null param pointer", (int)s);
+        return CHOCO_OK;
+      });
 }
 
 static int ef_run(const EfArgs& a, hipStream_t st) {
@@ -194,33 +177,23 @@ static int ef_run(const EfArgs& a, hipStream_t st) {
   const float nlr = (float)(-a.lr), div = (float)a.divisor;
   const int32_t flat16 = aligned16(a.flat) ? 1 : 0;
   EfTable tb;
-  int64_t base = 0;
-  for (int32_t s0 = 0; s0 < a.nseg; s0 += kEfCap) {
-    const int nt = std::min<int32_t>(kEfCap, a.nseg - s0);
-    tb.nt = nt;
-    tb.off[0] = base;
+  return for_chunks<kEfCap>(a.lens, a.nseg, tb.off, [&](const Chunk& c) -> int {
+    tb.nt = c.nt;
     for (int i = 0; i < kEfCap; ++i) {
-      const bool in = i < nt;
-      const int32_t s = s0 + i;
-      tb.p[i] = in ? a.params[s] : nullptr;
-      tb.dt[i] = in ? (uint8_t)a.dtypes[s] : (uint8_t)0;
-      base += in ? a.lens[s] : 0;
-      tb.off[i + 1] = base;
+      const bool in = i < c.nt;
+      tb.p[i] = in ? a.params[c.s0 + i] : nullptr;
+      tb.dt[i] = in ? (uint8_t)a.dtypes[c.s0 + i] : (uint8_t)0;
     }
-    // the tiles the chunk [off[0], off[nt]) touches; an empty chunk still takes its launch
-    const int64_t tile0 = tb.off[0] / kPbTile;
-    const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
-    CHOCO_TRY(CHOCO_LAUNCH("param_ef_kernel", "param_ef_kernel", param_ef_kernel, dim3((unsigned)tiles),
-                           dim3(kPbThreads), st, tb, a.flat, tile0, nlr, div, a.mode, flat16));
-  }
-  return CHOCO_OK;
+    return CHOCO_LAUNCH("param_ef_kernel", "param_ef_kernel", param_ef_kernel, dim3((unsigned)c.tiles),
+                        dim3(kPbThreads), st, tb, a.flat, c.tile0, nlr, div, a.mode, flat16);
+  });
 }
 
 }  // namespace choco
 
 using namespace choco;
 
-CHOCO_API int choco_params_ef_launches(int32_t nseg) { return ef_launches(nseg); }
+CHOCO_API int choco_params_ef_launches(int32_t nseg) { return chunk_launches(nseg, kEfCap); }
 
 CHOCO_API int choco_params_ef(void* const* params, const int64_t* lens, const int32_t* dtypes, int32_t nseg,
                               float* flat, int64_t n, int32_t mode, double lr, double divisor, void* stream) {

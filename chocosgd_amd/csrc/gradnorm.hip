@@ -3,7 +3,7 @@
 // sum.  The tile geometry, the table walk and the flag bits are the update's (param_common.h).
 #include "param_common.h"
 
-#include <algorithm>
+#include <cmath>
 
 namespace choco {
 
@@ -74,7 +74,9 @@ CHOCO_DEV double norm_scalar(const void* p, const void* g, bool has_wd, float wd
   return acc;
 }
 
-// ... the workgroup taking whole groups as 16-byte vectors
+// ... the workgroup taking whole groups as 16-byte vectors, kNormU groups in flight per thread.
+// A loop of its own, not param_common.h's span_walk: there is nothing to store, the loads are
+// default-policy (ld8n) and all of a round's are issued ahead of the first square.
 template <int DT>
 CHOCO_DEV double norm_vector(const void* p, const void* g, bool has_wd, float wd, int64_t o0, int64_t a, int64_t b) {
   const int tid = threadIdx.x;
@@ -128,55 +130,48 @@ __global__ __launch_bounds__(kPbThreads) void param_sqnorm_kernel(const NormTabl
     }
   }
   const int64_t tile = tile0 + blockIdx.x;
-  int64_t tlo, thi;
-  const int s0 = tile_first_tensor(tb.off, nt, tile, tlo, thi);
-  if (s0 < 0) return;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   int nshort = 0;
-  for (int s = s0; s < nt; ++s) {
-    const int64_t o0 = tb.off[s];
-    if (o0 >= thi) break;
-    const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);
+  tile_walk(tb.off, nt, tile, [&](int s, int64_t a, int64_t b) {
     const uint32_t fl = tb.fl[s];
-    if (a >= b || (fl & CHOCO_SGD_F_NOGRAD)) continue;
+    if (fl & CHOCO_SGD_F_NOGRAD) return;
     const int dt = tb.dt[s];
+    const int64_t o0 = tb.off[s];
     const bool has_wd = (fl & kSgdHasWd) != 0;
     const float wd = tb.wd[s];
     const void* p = tb.p[s];
     const void* g = tb.g[s];
     double* slot = slots + (tile + seg0 + s);
+    double acc;
     if (b - a <= kNormWaveMax) {
       const bool mine = (nshort & 3) == wave;
       ++nshort;
-      if (!mine) continue;
-      double acc;
-      if (dt == CHOCO_DT_F32) acc = norm_scalar<CHOCO_DT_F32>(p, g, has_wd, wd, o0, a, b, lane, 64);
-      else if (dt == CHOCO_DT_BF16) acc = norm_scalar<CHOCO_DT_BF16>(p, g, has_wd, wd, o0, a, b, lane, 64);
-      else acc = norm_scalar<CHOCO_DT_F16>(p, g, has_wd, wd, o0, a, b, lane, 64);
+      if (!mine) return;
+      for_dtype(dt, [&](auto DT) { acc = norm_scalar<DT>(p, g, has_wd, wd, o0, a, b, lane, 64); });
       acc = wave_sum(acc);
       if (lane == 0) *slot = acc;
-      continue;
+      return;
     }
-    const uintptr_t esz = dt == CHOCO_DT_F32 ? 4u : 2u, back = esz * (uintptr_t)o0;
-    uintptr_t mis = reinterpret_cast<uintptr_t>(g) - back;
-    if (has_wd) mis |= reinterpret_cast<uintptr_t>(p) - back;
-    const bool vec = (mis & 15u) == 0;
-    double acc;
-    if (dt == CHOCO_DT_F32)
-      acc = vec ? norm_vector<CHOCO_DT_F32>(p, g, has_wd, wd, o0, a, b)
-                : norm_scalar<CHOCO_DT_F32>(p, g, has_wd, wd, o0, a, b, tid, kPbThreads);
-    else if (dt == CHOCO_DT_BF16)
-      acc = vec ? norm_vector<CHOCO_DT_BF16>(p, g, has_wd, wd, o0, a, b)
-                : norm_scalar<CHOCO_DT_BF16>(p, g, has_wd, wd, o0, a, b, tid, kPbThreads);
-    else
-      acc = vec ? norm_vector<CHOCO_DT_F16>(p, g, has_wd, wd, o0, a, b)
-                : norm_scalar<CHOCO_DT_F16>(p, g, has_wd, wd, o0, a, b, tid, kPbThreads);
+    const uintptr_t esz = dtype_size(dt);
+    uintptr_t mis = mis16(g, esz, o0);
+    if (has_wd) mis |= mis16(p, esz, o0);
+    const bool vec = on_grid16(mis);
+    for_dtype(dt, [&](auto DT) {
+      acc = vec ? norm_vector<DT>(p, g, has_wd, wd, o0, a, b)
+                : norm_scalar<DT>(p, g, has_wd, wd, o0, a, b, tid, kPbThreads);
+    });
     acc = wave_sum(acc);
     if (lane == 0) red[wave] = acc;
     __syncthreads();
     if (tid == 0) *slot = ((red[0] + red[1]) + red[2]) + red[3];
     __syncthreads();  // red is reused by the next long span
-  }
+  });
+}
+
+// v as dtype dt (a CHOCO_DT_* code) holds it
+CHOCO_DEV float rnd_as(float v, int dt) {
+  for_dtype(dt, [&](auto DT) { v = rnd<DT>(v); });
+  return v;
 }
 
 // one wave per tensor: its slots added in ascending order (64 at a time are loaded by the lanes
@@ -199,10 +194,7 @@ __global__ __launch_bounds__(kPbThreads) void param_sqnorm_finish_kernel(const d
     const int32_t m = cnt - base < 64 ? cnt - base : 64;
     for (int32_t l = 0; l < m; ++l) acc += __shfl(v, l);
   }
-  float r = (float)sqrt(acc);
-  if (dt == CHOCO_DT_BF16) r = rnd<CHOCO_DT_BF16>(r);
-  else if (dt == CHOCO_DT_F16) r = rnd<CHOCO_DT_F16>(r);
-  if (lane == 0) norms[s] = r;
+  if (lane == 0) norms[s] = rnd_as((float)sqrt(acc), dt);
 }
 
 // ------------------------------------------------------------------ the global gradient norm and its clip coefficient
@@ -235,13 +227,6 @@ CHOCO_DEV double wave_ordered_sum(const double* v, int32_t cnt, int lane) {
       acc += __hiloint2double(__builtin_amdgcn_readlane(hi, l), __builtin_amdgcn_readlane(lo, l));
   }
   return acc;
-}
-
-// v as dtype dt (a CHOCO_DT_* code) holds it
-CHOCO_DEV float rnd_as(float v, int dt) {
-  if (dt == CHOCO_DT_BF16) return rnd<CHOCO_DT_BF16>(v);
-  if (dt == CHOCO_DT_F16) return rnd<CHOCO_DT_F16>(v);
-  return v;
 }
 
 //
@@ -403,7 +388,7 @@ __global__ __launch_bounds__(kTotalThreads) void param_gradnorm_total_kernel(con
 }
 
 
-static int norm_launches(int32_t nseg) { return nseg <= 0 ? 0 : (nseg + kNormCap - 1) / kNormCap + 1; }
+static int norm_launches(int32_t nseg) { return nseg <= 0 ? 0 : chunk_launches(nseg, kNormCap) + 1; }
 static size_t norm_slots(int32_t nseg, int64_t n) { return (size_t)(n / kPbTile + 1) + (size_t)nseg; }
 static size_t norm_ws_bytes(int32_t nseg, int64_t n) {
   if (nseg <= 0 || n < 0) return 0;
@@ -424,47 +409,43 @@ struct NormArgs {
   size_t ws_bytes;
 };
 
+// tensor s of a norm call (params / wd null: choco_params_gradnorm, the raw gradients alone)
+static int norm_tensor_check(const void* const* params, const void* const* grads, const int64_t* lens,
+                             const double* wd, const int32_t* flags, int32_t s, uintptr_t esz) {
+  const int i = (int)s;
+  constexpr int32_t kFlags = CHOCO_SGD_F_NESTEROV | CHOCO_SGD_F_FIRST | CHOCO_SGD_F_NOGRAD;
+  CHOCO_REQUIRE((flags[s] & ~kFlags) == 0, "tensor %d: unknown flag bits 0x%x", i, (unsigned)flags[s]);
+  CHOCO_REQUIRE((!params || elem_aligned(params[s], esz)) && elem_aligned(grads[s], esz),
+                "tensor %d: pointer not aligned to its element size", i);
+  if (lens[s] == 0 || (flags[s] & CHOCO_SGD_F_NOGRAD)) return CHOCO_OK;
+  CHOCO_REQUIRE(grads[s], "tensor %d: null grad pointer without the no-grad flag", i);
+  CHOCO_REQUIRE(!params || params[s] || wd[s] == 0.0, "tensor %d: null param pointer with weight decay != 0", i);
+  return CHOCO_OK;
+}
+
 static int norm_check(const NormArgs& a) {
   CHOCO_REQUIRE(a.params && a.grads && a.lens && a.dtypes && a.wd && a.flags, "null table argument");
-  CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
-  CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
-  CHOCO_REQUIRE(a.norms && aligned4(a.norms), "norms must be a 4-byte aligned device pointer");
-  CHOCO_REQUIRE(a.ws && (reinterpret_cast<uintptr_t>(a.ws) & 7u) == 0, "the workspace must be 8-byte aligned");
-  if (a.ws_bytes < norm_ws_bytes(a.nseg, a.n))
-    return fail(CHOCO_ERR_WORKSPACE, "workspace too small: %zu bytes, need %zu", a.ws_bytes,
-                norm_ws_bytes(a.nseg, a.n));
-  int64_t sum = 0;
-  for (int32_t s = 0; s < a.nseg; ++s) {
-    const int i = (int)s;
-    CHOCO_REQUIRE(a.lens[s] >= 0, "tensor %d: negative length", i);
-    CHOCO_REQUIRE(a.dtypes[s] >= CHOCO_DT_F32 && a.dtypes[s] <= CHOCO_DT_F16, "tensor %d: unknown dtype code %d", i,
-                  (int)a.dtypes[s]);
-    CHOCO_REQUIRE(a.lens[s] <= a.n - sum, "the lengths add up to more than n = %lld", (long long)a.n);
-    sum += a.lens[s];
-    constexpr int32_t kFlags = CHOCO_SGD_F_NESTEROV | CHOCO_SGD_F_FIRST | CHOCO_SGD_F_NOGRAD;
-    CHOCO_REQUIRE((a.flags[s] & ~kFlags) == 0, "tensor %d: unknown flag bits 0x%x", i, (unsigned)a.flags[s]);
-    const uintptr_t esz = a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u;
-    CHOCO_REQUIRE(elem_aligned(a.params[s], esz) && elem_aligned(a.grads[s], esz),
-                  "tensor %d: pointer not aligned to its element size", i);
-    if (a.lens[s] == 0 || (a.flags[s] & CHOCO_SGD_F_NOGRAD)) continue;
-    CHOCO_REQUIRE(a.grads[s], "tensor %d: null grad pointer without the no-grad flag", i);
-    CHOCO_REQUIRE(a.params[s] || a.wd[s] == 0.0, "tensor %d: null param pointer with weight decay != 0", i);
-  }
-  CHOCO_REQUIRE(sum == a.n, "the lengths add up to %lld, n is %lld", (long long)sum, (long long)a.n);
-  return CHOCO_OK;
+  return layout_check(
+      a.lens, a.dtypes, a.nseg, a.n,
+      [&]() -> int {
+        CHOCO_REQUIRE(a.norms && aligned4(a.norms), "norms must be a 4-byte aligned device pointer");
+        CHOCO_REQUIRE(a.ws && (reinterpret_cast<uintptr_t>(a.ws) & 7u) == 0, "the workspace must be 8-byte aligned");
+        if (a.ws_bytes < norm_ws_bytes(a.nseg, a.n))
+          return fail(CHOCO_ERR_WORKSPACE, "workspace too small: %zu bytes, need %zu", a.ws_bytes,
+                      norm_ws_bytes(a.nseg, a.n));
+        return CHOCO_OK;
+      },
+      [&](int32_t s, uintptr_t esz) -> int { return norm_tensor_check(a.params, a.grads, a.lens, a.wd, a.flags, s, esz); });
 }
 
 // the norm pass: one param_sqnorm_kernel launch per chunk (a.params / a.wd null: raw gradients)
 static int norm_pass(const NormArgs& a, double* slots, int32_t* meta, hipStream_t st) {
   NormTable tb;
-  int64_t base = 0;
-  for (int32_t s0 = 0; s0 < a.nseg; s0 += kNormCap) {
-    const int nt = std::min<int32_t>(kNormCap, a.nseg - s0);
-    tb.nt = nt;
-    tb.off[0] = base;
+  return for_chunks<kNormCap>(a.lens, a.nseg, tb.off, [&](const Chunk& c) -> int {
+    tb.nt = c.nt;
     for (int i = 0; i < kNormCap; ++i) {
-      const bool in = i < nt;
-      const int32_t s = s0 + i;
+      const bool in = i < c.nt;
+      const int32_t s = c.s0 + i;
       const bool upd = in && !(a.flags[s] & CHOCO_SGD_F_NOGRAD);
       tb.p[i] = upd && a.params ? a.params[s] : nullptr;
       tb.g[i] = upd ? a.grads[s] : nullptr;
@@ -473,15 +454,10 @@ static int norm_pass(const NormArgs& a, double* slots, int32_t* meta, hipStream_
       uint32_t fl = in ? (uint32_t)(a.flags[s] & CHOCO_SGD_F_NOGRAD) : 0u;
       if (upd && a.wd && a.wd[s] != 0.0) fl |= kSgdHasWd;
       tb.fl[i] = (uint8_t)fl;
-      base += in ? a.lens[s] : 0;
-      tb.off[i + 1] = base;
     }
-    const int64_t tile0 = tb.off[0] / kPbTile;
-    const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
-    CHOCO_TRY(CHOCO_LAUNCH("param_sqnorm_kernel", "param_sqnorm_kernel", param_sqnorm_kernel, dim3((unsigned)tiles),
-                           dim3(kPbThreads), st, tb, slots, meta + 2 * (size_t)s0, tile0, s0));
-  }
-  return CHOCO_OK;
+    return CHOCO_LAUNCH("param_sqnorm_kernel", "param_sqnorm_kernel", param_sqnorm_kernel, dim3((unsigned)c.tiles),
+                        dim3(kPbThreads), st, tb, slots, meta + 2 * (size_t)c.s0, c.tile0, c.s0);
+  });
 }
 
 static int norm_run(const NormArgs& a, hipStream_t st) {
@@ -500,7 +476,7 @@ static int norm_run(const NormArgs& a, hipStream_t st) {
 // choco_params_gradnorm: the norm pass and param_gradnorm_total_kernel, or that launch alone from
 // a pinned total.  Workspace: the sqnorm slots, one fp64 sum per tensor, the meta words.
 static int gradnorm_launches(int32_t nseg, int32_t pinned) {
-  return nseg <= 0 ? 0 : pinned ? 1 : (nseg + kNormCap - 1) / kNormCap + 1;
+  return nseg <= 0 ? 0 : pinned ? 1 : chunk_launches(nseg, kNormCap) + 1;
 }
 static size_t gradnorm_ws_bytes(int32_t nseg, int64_t n) {
   if (nseg <= 0 || n < 0) return 0;
@@ -537,48 +513,39 @@ static int loss_scale_check(const LossScale& ls) {
 }
 
 static int gradnorm_check(const GradnormArgs& a) {
-  CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
-  CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
-  // tested as the kernel uses it: the fp32 value (a scaled call without a clip does not use it)
-  if (!a.scaled || a.ls.has_clip)
-    CHOCO_REQUIRE(a.max_norm >= 0.0 && a.max_norm <= 3.4028234663852886e38,
-                  "max_norm must be >= 0 and finite as an fp32 value, got %g", a.max_norm);
-  if (a.scaled) {
-    const int rc = loss_scale_check(a.ls);
-    if (rc) return rc;
-    CHOCO_REQUIRE(a.ls.has_clip == 0 || a.ls.has_clip == 1, "has_clip must be 0 or 1, got %d", (int)a.ls.has_clip);
-  }
-  CHOCO_REQUIRE(a.coef_dtype >= CHOCO_DT_F32 && a.coef_dtype <= CHOCO_DT_F16, "unknown coef_dtype code %d",
-                (int)a.coef_dtype);
-  CHOCO_REQUIRE(a.out && aligned4(a.out), "out must be a 4-byte aligned device pointer");
-  CHOCO_REQUIRE(aligned4(a.norms), "norms must be 4-byte aligned");
-  if (a.total_in) {  // parity mode: nothing of the layout is read
-    CHOCO_REQUIRE(aligned4(a.total_in), "total_in must be 4-byte aligned");
-    CHOCO_REQUIRE(!a.norms, "norms with a pinned total: there is no norm pass to take them from");
+  // the arguments beside the layout; a pinned total (parity mode) reads nothing of the layout
+  const auto own = [&]() -> int {
+    // tested as the kernel uses it: the fp32 value (a scaled call without a clip does not use it)
+    if (!a.scaled || a.ls.has_clip)
+      CHOCO_REQUIRE(a.max_norm >= 0.0 && a.max_norm <= 3.4028234663852886e38,
+                    "max_norm must be >= 0 and finite as an fp32 value, got %g", a.max_norm);
+    if (a.scaled) {
+      CHOCO_TRY(loss_scale_check(a.ls));
+      CHOCO_REQUIRE(a.ls.has_clip == 0 || a.ls.has_clip == 1, "has_clip must be 0 or 1, got %d", (int)a.ls.has_clip);
+    }
+    CHOCO_REQUIRE(a.coef_dtype >= CHOCO_DT_F32 && a.coef_dtype <= CHOCO_DT_F16, "unknown coef_dtype code %d",
+                  (int)a.coef_dtype);
+    CHOCO_REQUIRE(a.out && aligned4(a.out), "out must be a 4-byte aligned device pointer");
+    CHOCO_REQUIRE(aligned4(a.norms), "norms must be 4-byte aligned");
+    if (a.total_in) {
+      CHOCO_REQUIRE(aligned4(a.total_in), "total_in must be 4-byte aligned");
+      CHOCO_REQUIRE(!a.norms, "norms with a pinned total: there is no norm pass to take them from");
+      return CHOCO_OK;
+    }
+    CHOCO_REQUIRE(a.grads && a.lens && a.dtypes && a.flags, "null table argument");
+    CHOCO_REQUIRE(a.ws && (reinterpret_cast<uintptr_t>(a.ws) & 7u) == 0, "the workspace must be 8-byte aligned");
+    if (a.ws_bytes < gradnorm_ws_bytes(a.nseg, a.n))
+      return fail(CHOCO_ERR_WORKSPACE, "workspace too small: %zu bytes, need %zu", a.ws_bytes,
+                  gradnorm_ws_bytes(a.nseg, a.n));
     return CHOCO_OK;
+  };
+  if (a.total_in) {
+    CHOCO_TRY(layout_head(a.nseg, a.n));
+    return own();
   }
-  CHOCO_REQUIRE(a.grads && a.lens && a.dtypes && a.flags, "null table argument");
-  CHOCO_REQUIRE(a.ws && (reinterpret_cast<uintptr_t>(a.ws) & 7u) == 0, "the workspace must be 8-byte aligned");
-  if (a.ws_bytes < gradnorm_ws_bytes(a.nseg, a.n))
-    return fail(CHOCO_ERR_WORKSPACE, "workspace too small: %zu bytes, need %zu", a.ws_bytes,
-                gradnorm_ws_bytes(a.nseg, a.n));
-  int64_t sum = 0;
-  for (int32_t s = 0; s < a.nseg; ++s) {
-    const int i = (int)s;
-    CHOCO_REQUIRE(a.lens[s] >= 0, "tensor %d: negative length", i);
-    CHOCO_REQUIRE(a.dtypes[s] >= CHOCO_DT_F32 && a.dtypes[s] <= CHOCO_DT_F16, "tensor %d: unknown dtype code %d", i,
-                  (int)a.dtypes[s]);
-    CHOCO_REQUIRE(a.lens[s] <= a.n - sum, "the lengths add up to more than n = %lld", (long long)a.n);
-    sum += a.lens[s];
-    constexpr int32_t kFlags = CHOCO_SGD_F_NESTEROV | CHOCO_SGD_F_FIRST | CHOCO_SGD_F_NOGRAD;
-    CHOCO_REQUIRE((a.flags[s] & ~kFlags) == 0, "tensor %d: unknown flag bits 0x%x", i, (unsigned)a.flags[s]);
-    CHOCO_REQUIRE(elem_aligned(a.grads[s], a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u),
-                  "tensor %d: pointer not aligned to its element size", i);
-    if (a.lens[s] == 0 || (a.flags[s] & CHOCO_SGD_F_NOGRAD)) continue;
-    CHOCO_REQUIRE(a.grads[s], "tensor %d: null grad pointer without the no-grad flag", i);
-  }
-  CHOCO_REQUIRE(sum == a.n, "the lengths add up to %lld, n is %lld", (long long)sum, (long long)a.n);
-  return CHOCO_OK;
+  return layout_check(a.lens, a.dtypes, a.nseg, a.n, own, [&](int32_t s, uintptr_t esz) -> int {
+    return norm_tensor_check(nullptr, a.grads, a.lens, nullptr, a.flags, s, esz);
+  });
 }
 
 static int gradnorm_run(const GradnormArgs& a, hipStream_t st) {

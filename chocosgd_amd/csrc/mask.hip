@@ -18,8 +18,6 @@
 // layout at ratio 0.9 has 10 slots per tensor) or, past kMaskWaveMax slots, by the workgroup.
 #include "param_common.h"
 
-#include <algorithm>
-
 namespace choco {
 
 constexpr int kMaskCap = 128;         // tensors per launch
@@ -40,19 +38,7 @@ CHOCO_DEV void mask_slot(void* buf, int dt, int64_t o0, int64_t o1, const float*
                          const int32_t* __restrict__ indices, float* memory, int64_t j) {
   const int64_t i = indices[j];
   if (i < o0 || i >= o1) return;
-  if (buf) {
-    const int64_t e = i - o0;
-    if (dt == CHOCO_DT_F32) {
-      float* b = reinterpret_cast<float*>(buf);
-      b[e] = __fmul_rn(b[e], 0.0f);
-    } else if (dt == CHOCO_DT_BF16) {
-      unsigned short* b = reinterpret_cast<unsigned short*>(buf);
-      b[e] = bf16_narrow(__fmul_rn(bf16_widen(b[e]), 0.0f));
-    } else {
-      unsigned short* b = reinterpret_cast<unsigned short*>(buf);
-      b[e] = f16_narrow(__fmul_rn(f16_widen(b[e]), 0.0f));
-    }
-  }
+  if (buf) for_dtype(dt, [&](auto DT) { st1<DT>(buf, i - o0, __fmul_rn(ld1<DT>(buf, i - o0), 0.0f)); });
   if (memory) {
     const float v = values[j];
     memory[i] = v + (-v);
@@ -62,41 +48,25 @@ CHOCO_DEV void mask_slot(void* buf, int dt, int64_t o0, int64_t o1, const float*
 __global__ __launch_bounds__(kPbThreads) void param_mask_kernel(const MaskTable tb, const float* values,
                                                                 const int32_t* indices, float* memory,
                                                                 int64_t tile0) {
-  const int nt = tb.nt;
-  const int64_t tile = tile0 + blockIdx.x;
-  const int64_t tlo = i64max(tile * kMaskTile, tb.koff[0]);
-  const int64_t thi = i64min((tile + 1) * kMaskTile, tb.koff[nt]);
-  if (tlo >= thi) return;
-  // the first s in [1, nt] with koff[s] > tlo: tensor s - 1 holds slot tlo
-  int lo = 1, hi = nt;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (tb.koff[mid] > tlo) hi = mid; else lo = mid + 1;
-  }
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   int nshort = 0;
-  for (int s = lo - 1; s < nt; ++s) {
-    const int64_t k0 = tb.koff[s];
-    if (k0 >= thi) break;
-    const int64_t a = i64max(k0, tlo), b = i64min(tb.koff[s + 1], thi);
-    if (a >= b) continue;  // a tensor with no slot
+  // the shared walk over the slot offsets: [a, b) are tensor s's slots in this workgroup's tile
+  tile_walk(tb.koff, tb.nt, tile0 + blockIdx.x, [&](int s, int64_t a, int64_t b) {
     void* buf = tb.buf[s];
-    if (!buf && !memory) continue;
+    if (!buf && !memory) return;
     const int dt = tb.dt[s];
     const int64_t o0 = tb.off[s], o1 = tb.off[s + 1];
     if (b - a <= kMaskWaveMax) {
       const bool mine = (nshort & 3) == wave;
       ++nshort;
-      if (!mine) continue;
+      if (!mine) return;
       for (int64_t j = a + lane; j < b; j += 64) mask_slot(buf, dt, o0, o1, values, indices, memory, j);
     } else {
       for (int64_t j = a + tid; j < b; j += kPbThreads) mask_slot(buf, dt, o0, o1, values, indices, memory, j);
     }
-  }
+  }, kMaskTile);
 }
-
-static int mask_launches(int32_t nseg) { return nseg <= 0 ? 0 : (nseg + kMaskCap - 1) / kMaskCap; }
 
 struct MaskArgs {
   void* const* bufs;
@@ -114,29 +84,24 @@ struct MaskArgs {
 // Every argument is checked before the first launch, with no HIP call.
 static int mask_check(const MaskArgs& a) {
   CHOCO_REQUIRE(a.bufs && a.lens && a.dtypes && a.kseg, "null table argument");
-  CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
-  CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
-  CHOCO_REQUIRE(a.k >= 0 && a.k <= a.n, "k must be in [0, n], got %lld", (long long)a.k);
-  CHOCO_REQUIRE(a.k == 0 || (a.values && a.indices), "null values or indices with k > 0");
-  CHOCO_REQUIRE(aligned4(a.values) && aligned4(a.indices) && aligned4(a.memory),
-                "values, indices and memory must be 4-byte aligned");
-  int64_t sum = 0, ksum = 0;
+  int64_t ksum = 0;
   bool any = a.memory != nullptr;
-  for (int32_t s = 0; s < a.nseg; ++s) {
-    const int i = (int)s;
-    CHOCO_REQUIRE(a.lens[s] >= 0, "tensor %d: negative length", i);
-    CHOCO_REQUIRE(a.dtypes[s] >= CHOCO_DT_F32 && a.dtypes[s] <= CHOCO_DT_F16, "tensor %d: unknown dtype code %d", i,
-                  (int)a.dtypes[s]);
-    CHOCO_REQUIRE(a.lens[s] <= a.n - sum, "the lengths add up to more than n = %lld", (long long)a.n);
-    sum += a.lens[s];
-    CHOCO_REQUIRE(a.kseg[s] >= 0 && a.kseg[s] <= a.lens[s], "tensor %d: k_per_seg outside [0, length]", i);
-    ksum += a.kseg[s];
-    const uintptr_t esz = a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u;
-    CHOCO_REQUIRE((reinterpret_cast<uintptr_t>(a.bufs[s]) & (esz - 1)) == 0,
-                  "tensor %d: pointer not aligned to its element size", i);
-    any = any || a.bufs[s] != nullptr;
-  }
-  CHOCO_REQUIRE(sum == a.n, "the lengths add up to %lld, n is %lld", (long long)sum, (long long)a.n);
+  CHOCO_TRY(layout_check(
+      a.lens, a.dtypes, a.nseg, a.n,
+      [&]() -> int {
+        CHOCO_REQUIRE(a.k >= 0 && a.k <= a.n, "k must be in [0, n], got %lld", (long long)a.k);
+        CHOCO_REQUIRE(a.k == 0 || (a.values && a.indices), "null values or indices with k > 0");
+        CHOCO_REQUIRE(aligned4(a.values) && aligned4(a.indices) && aligned4(a.memory),
+                      "values, indices and memory must be 4-byte aligned");
+        return CHOCO_OK;
+      },
+      [&](int32_t s, uintptr_t esz) -> int {
+        CHOCO_REQUIRE(a.kseg[s] >= 0 && a.kseg[s] <= a.lens[s], "tensor %d: k_per_seg outside [0, length]", (int)s);
+        ksum += a.kseg[s];
+        CHOCO_REQUIRE(elem_aligned(a.bufs[s], esz), "tensor %d: pointer not aligned to its element size", (int)s);
+        any = any || a.bufs[s] != nullptr;
+        return CHOCO_OK;
+      }));
   CHOCO_REQUIRE(ksum == a.k, "k_per_seg adds up to %lld, k is %lld", (long long)ksum, (long long)a.k);
   CHOCO_REQUIRE(any, "nothing to write: memory is null and so is every buffer");
   return CHOCO_OK;
@@ -146,36 +111,26 @@ static int mask_run(const MaskArgs& a, hipStream_t st) {
   const int rc = mask_check(a);
   if (rc) return rc;
   MaskTable tb;
-  int64_t base = 0, kbase = 0;
-  for (int32_t s0 = 0; s0 < a.nseg; s0 += kMaskCap) {
-    const int nt = std::min<int32_t>(kMaskCap, a.nseg - s0);
-    tb.nt = nt;
-    tb.off[0] = base;
-    tb.koff[0] = kbase;
+  int64_t base = 0;
+  // the grid walks the slot offsets; a chunk without a slot still takes its launch
+  return for_chunks<kMaskCap>(a.kseg, a.nseg, tb.koff, [&](const Chunk& c) -> int {
+    tb.nt = c.nt;
+    base = chunk_offsets<kMaskCap>(a.lens, c.s0, c.nt, base, tb.off);
     for (int i = 0; i < kMaskCap; ++i) {
-      const bool in = i < nt;
-      const int32_t s = s0 + i;
-      tb.buf[i] = in ? a.bufs[s] : nullptr;
-      tb.dt[i] = in ? (uint8_t)a.dtypes[s] : (uint8_t)0;
-      base += in ? a.lens[s] : 0;
-      kbase += in ? a.kseg[s] : 0;
-      tb.off[i + 1] = base;
-      tb.koff[i + 1] = kbase;
+      const bool in = i < c.nt;
+      tb.buf[i] = in ? a.bufs[c.s0 + i] : nullptr;
+      tb.dt[i] = in ? (uint8_t)a.dtypes[c.s0 + i] : (uint8_t)0;
     }
-    // the slot tiles the chunk touches; a chunk without a slot still takes its launch
-    const int64_t tile0 = tb.koff[0] / kMaskTile;
-    const int64_t tiles = tb.koff[nt] > tb.koff[0] ? (tb.koff[nt] - 1) / kMaskTile - tile0 + 1 : 1;
-    CHOCO_TRY(CHOCO_LAUNCH("param_mask_kernel", "param_mask_kernel", param_mask_kernel, dim3((unsigned)tiles),
-                           dim3(kPbThreads), st, tb, a.values, a.indices, a.memory, tile0));
-  }
-  return CHOCO_OK;
+    return CHOCO_LAUNCH("param_mask_kernel", "param_mask_kernel", param_mask_kernel, dim3((unsigned)c.tiles),
+                        dim3(kPbThreads), st, tb, a.values, a.indices, a.memory, c.tile0);
+  }, kMaskTile);
 }
 
 }  // namespace choco
 
 using namespace choco;
 
-CHOCO_API int choco_params_mask_launches(int32_t nseg) { return mask_launches(nseg); }
+CHOCO_API int choco_params_mask_launches(int32_t nseg) { return chunk_launches(nseg, kMaskCap); }
 
 CHOCO_API int choco_params_mask(void* const* bufs, const int64_t* lens, const int32_t* dtypes, const int64_t* k_per_seg,
                                 int32_t nseg, const float* values, const int32_t* indices, int64_t k, float* memory,

@@ -97,81 +97,66 @@ CHOCO_DEV void mix_tail(const MixTensor& t, float& m, float g, float x, float& o
   out = t.extrap ? __fadd_rn(__fmul_rn(t.a, x), __fmul_rn(t.b, m)) : m;
 }
 
-// flat index i, element j of the tensor
+// One element at flat index i and one whole group at flat index e of a tensor of dtype DT at
+// flat offset o0 (span_walk's body); every load of a group is issued before its first store.
 template <int DT>
-CHOCO_DEV void mix_elem(const MixSrcs& sr, const MixTensor& t, int64_t i, int64_t j) {
-  float v[kMixSrc];
-#pragma unroll
-  for (int r = 0; r < kMixSrc; ++r) v[r] = r < sr.nsrc ? sr.src[r][i] : 0.0f;
-  const float run = sr.chained ? t.flat_out[i] : 0.0f;
-  const float g = (t.sub || t.fma) ? ld1<DT>(t.g, j) : 0.0f;
-  const float x = t.rd_p ? ld1<DT>(t.p, j) : 0.0f;
-  float m = mix_sum(sr, v, run), out;
-  mix_tail(t, m, g, x, out);
-  if (t.wr_p) st1<DT>(t.p, j, m);
-  if (t.flat_out) t.flat_out[i] = out;
-  if (t.x_out) t.x_out[i] = x;
-}
+struct MixBody {
+  const MixSrcs& sr;
+  const MixTensor& t;
+  int64_t o0;
 
-// Flat elements [a, b) of a tensor at flat offset o0, a < b inside this workgroup's tile.
-// vec: every side the launch touches is 16-byte aligned at every whole group's start.
-template <int DT>
-CHOCO_DEV void mix_span(const MixSrcs& sr, const MixTensor& t, int64_t o0, int64_t a, int64_t b, bool vec) {
-  const int tid = threadIdx.x;
-  if (!vec) {
-    for (int64_t i = a + tid; i < b; i += kPbThreads) mix_elem<DT>(sr, t, i, i - o0);
-    return;
+  CHOCO_DEV void elem(int64_t i) const {
+    const int64_t j = i - o0;
+    float v[kMixSrc];
+#pragma unroll
+    for (int r = 0; r < kMixSrc; ++r) v[r] = r < sr.nsrc ? sr.src[r][i] : 0.0f;
+    const float run = sr.chained ? t.flat_out[i] : 0.0f;
+    const float g = (t.sub || t.fma) ? ld1<DT>(t.g, j) : 0.0f;
+    const float x = t.rd_p ? ld1<DT>(t.p, j) : 0.0f;
+    float m = mix_sum(sr, v, run), out;
+    mix_tail(t, m, g, x, out);
+    if (t.wr_p) st1<DT>(t.p, j, m);
+    if (t.flat_out) t.flat_out[i] = out;
+    if (t.x_out) t.x_out[i] = x;
   }
-  const bool rd_g = t.sub || t.fma;
-  const int64_t g0 = a >> 3, g1 = (b - 1) >> 3;  // groups at absolute flat offsets, inclusive
-  for (int64_t gb = g0; gb <= g1; gb += kPbThreads) {
-    const int64_t e = (gb + tid) * kPbGroup;
-    if (e >= a && e + kPbGroup <= b) {
-      // every load of the group is issued before the first store
-      Raw8 rs[kMixSrc], rr, rg, rp;
+
+  CHOCO_DEV void group(int64_t e) const {
+    const bool rd_g = t.sub || t.fma;
+    Raw8 rs[kMixSrc], rr, rg, rp;
 #pragma unroll
-      for (int r = 0; r < kMixSrc; ++r)
-        if (r < sr.nsrc) ld8<CHOCO_DT_F32>(rs[r], sr.src[r], e);
-      if (sr.chained) ld8<CHOCO_DT_F32>(rr, t.flat_out, e);
-      if (rd_g) ld8<DT>(rg, t.g, e - o0);
-      if (t.rd_p) ld8<DT>(rp, t.p, e - o0);
-      float m[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[8] = {0, 0, 0, 0, 0, 0, 0, 0}, x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      float out[8], w8[8];
-      if (sr.chained) widen8<CHOCO_DT_F32>(rr, m);
+    for (int r = 0; r < kMixSrc; ++r)
+      if (r < sr.nsrc) ld8<CHOCO_DT_F32>(rs[r], sr.src[r], e);
+    if (sr.chained) ld8<CHOCO_DT_F32>(rr, t.flat_out, e);
+    if (rd_g) ld8<DT>(rg, t.g, e - o0);
+    if (t.rd_p) ld8<DT>(rp, t.p, e - o0);
+    float m[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[8] = {0, 0, 0, 0, 0, 0, 0, 0}, x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float out[8], w8[8];
+    if (sr.chained) widen8<CHOCO_DT_F32>(rr, m);
 #pragma unroll
-      for (int r = 0; r < kMixSrc; ++r) {
-        if (r < sr.nsrc) {
-          widen8<CHOCO_DT_F32>(rs[r], w8);
+    for (int r = 0; r < kMixSrc; ++r) {
+      if (r < sr.nsrc) {
+        widen8<CHOCO_DT_F32>(rs[r], w8);
 #pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const float tt = __fmul_rn(w8[k], sr.w[r]);
-            m[k] = (r == 0 && !sr.chained) ? __fadd_rn(0.0f, tt) : __fadd_rn(m[k], tt);
-          }
+        for (int k = 0; k < 8; ++k) {
+          const float tt = __fmul_rn(w8[k], sr.w[r]);
+          m[k] = (r == 0 && !sr.chained) ? __fadd_rn(0.0f, tt) : __fadd_rn(m[k], tt);
         }
       }
-      if (rd_g) widen8<DT>(rg, g);
-      if (t.rd_p) widen8<DT>(rp, x);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) mix_tail(t, m[k], g[k], x[k], out[k]);
-      if (t.wr_p) st8<DT>(t.p, e - o0, m);
-      if (t.flat_out) st8<CHOCO_DT_F32>(t.flat_out, e, out);
-      if (t.x_out) st8<CHOCO_DT_F32>(t.x_out, e, x);
-    } else {
-      // a group cut by the tensor's start or end (or past the span): its own elements only
-      const int64_t ea = e > a ? e : a, eb = e + kPbGroup < b ? e + kPbGroup : b;
-      for (int64_t i = ea; i < eb; ++i) mix_elem<DT>(sr, t, i, i - o0);
     }
+    if (rd_g) widen8<DT>(rg, g);
+    if (t.rd_p) widen8<DT>(rp, x);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) mix_tail(t, m[k], g[k], x[k], out[k]);
+    if (t.wr_p) st8<DT>(t.p, e - o0, m);
+    if (t.flat_out) st8<CHOCO_DT_F32>(t.flat_out, e, out);
+    if (t.x_out) st8<CHOCO_DT_F32>(t.x_out, e, x);
   }
-}
+};
 
 // all16: every source, flat_out and x_out (those not NULL) are 16-byte aligned
 __global__ __launch_bounds__(kPbThreads) void param_mix_kernel(const MixTable tb, const MixSrcs sr, float* flat_out,
                                                                float* x_out, int64_t tile0, float lr, float nlr,
                                                                float ext_a, float ext_b, int32_t mode, int32_t all16) {
-  const int nt = tb.nt;
-  int64_t tlo, thi;
-  const int s0 = tile_first_tensor(tb.off, nt, tile0 + blockIdx.x, tlo, thi);
-  if (s0 < 0) return;
   MixTensor t;
   t.flat_out = flat_out; t.x_out = x_out;
   t.lr = lr; t.nlr = nlr; t.a = ext_a; t.b = ext_b;
@@ -180,29 +165,22 @@ __global__ __launch_bounds__(kPbThreads) void param_mix_kernel(const MixTable tb
   t.wr_p = (mode & CHOCO_MIX_WRITE_PARAMS) != 0;
   t.extrap = (mode & CHOCO_MIX_EXTRAPOLATE) != 0;
   t.rd_p = t.extrap || x_out != nullptr;
-  for (int s = s0; s < nt; ++s) {
-    const int64_t o0 = tb.off[s];
-    if (o0 >= thi) break;
-    const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);
-    if (a >= b) continue;  // zero-length tensor
+  tile_walk(tb.off, tb.nt, tile0 + blockIdx.x, [&](int s, int64_t a, int64_t b) {
     const int dt = tb.dt[s];
+    const int64_t o0 = tb.off[s];
     t.p = tb.p[s]; t.g = tb.g[s];
-    // a tensor's side q + esz (e - o0) is 16-byte aligned at every group start e (a multiple
-    // of 8) when q - esz o0 is, esz e being a multiple of 16
-    const uintptr_t esz = dt == CHOCO_DT_F32 ? 4u : 2u, back = esz * (uintptr_t)o0;
+    const uintptr_t esz = dtype_size(dt);
     uintptr_t mis = 0;
-    if (t.rd_p || t.wr_p) mis |= reinterpret_cast<uintptr_t>(t.p) - back;
-    if (t.sub || t.fma) mis |= reinterpret_cast<uintptr_t>(t.g) - back;
-    const bool vec = all16 && (mis & 15u) == 0;
-    if (dt == CHOCO_DT_F32) mix_span<CHOCO_DT_F32>(sr, t, o0, a, b, vec);
-    else if (dt == CHOCO_DT_BF16) mix_span<CHOCO_DT_BF16>(sr, t, o0, a, b, vec);
-    else mix_span<CHOCO_DT_F16>(sr, t, o0, a, b, vec);
-  }
+    if (t.rd_p || t.wr_p) mis |= mis16(t.p, esz, o0);
+    if (t.sub || t.fma) mis |= mis16(t.g, esz, o0);
+    const bool vec = all16 && on_grid16(mis);
+    for_dtype(dt, [&](auto DT) { span_walk(MixBody<DT>{sr, t, o0}, a, b, vec); });
+  });
 }
 
 static int mix_launches(int32_t nseg, int32_t nsrc) {
   if (nseg <= 0 || nsrc < 1 || nsrc > kMixMaxSrc) return 0;
-  return (nsrc - 1) / kMixSrc + (nseg + kMixCap - 1) / kMixCap;
+  return (nsrc - 1) / kMixSrc + chunk_launches(nseg, kMixCap);
 }
 
 struct MixArgs {
@@ -221,49 +199,43 @@ struct MixArgs {
   int64_t n;
 };
 
-static bool mix_elem_aligned(const void* p, uintptr_t esz) { return (reinterpret_cast<uintptr_t>(p) & (esz - 1)) == 0; }
-
 // Every argument is checked before the first launch, with no HIP call.
 static int mix_check(const MixArgs& a) {
   CHOCO_REQUIRE(a.srcs && a.weights && a.lens && a.dtypes, "null table argument");
   CHOCO_REQUIRE(a.nsrc >= 1 && a.nsrc <= kMixMaxSrc, "nsrc must be in [1, %d], got %d", kMixMaxSrc, (int)a.nsrc);
-  CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
-  CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
   constexpr int32_t kGrad = CHOCO_MIX_GRAD_SUB | CHOCO_MIX_GRAD_FMA;
-  constexpr int32_t kModes = kGrad | CHOCO_MIX_WRITE_PARAMS | CHOCO_MIX_EXTRAPOLATE;
-  CHOCO_REQUIRE((a.mode & ~kModes) == 0, "unknown mode bits 0x%x", (unsigned)a.mode);
-  CHOCO_REQUIRE((a.mode & kGrad) != kGrad, "GRAD_SUB and GRAD_FMA are two gradient terms: one of them at most");
   const bool grad = (a.mode & kGrad) != 0;
   const bool use_p = (a.mode & (CHOCO_MIX_WRITE_PARAMS | CHOCO_MIX_EXTRAPOLATE)) != 0 || a.x_out != nullptr;
-  CHOCO_REQUIRE(!grad || a.grads, "a GRAD mode needs the grads table");
-  CHOCO_REQUIRE(!use_p || a.params, "WRITE_PARAMS, EXTRAPOLATE and x_out need the params table");
-  CHOCO_REQUIRE(a.flat_out || a.x_out || (a.mode & CHOCO_MIX_WRITE_PARAMS),
-                "nothing to write: flat_out and x_out are null and the mode does not write the params");
-  CHOCO_REQUIRE(a.flat_out || !(a.mode & CHOCO_MIX_EXTRAPOLATE), "EXTRAPOLATE writes flat_out, which is null");
-  CHOCO_REQUIRE(a.nsrc <= kMixSrc || a.flat_out, "more than %d sources need flat_out for the running sum", kMixSrc);
-  CHOCO_REQUIRE(aligned4(a.flat_out) && aligned4(a.x_out), "flat_out and x_out must be 4-byte aligned");
-  CHOCO_REQUIRE(!grad || std::isfinite(a.lr), "lr must be finite, got %g", a.lr);
-  for (int32_t r = 0; r < a.nsrc; ++r) {
-    CHOCO_REQUIRE(a.srcs[r] || a.n == 0, "source %d: null pointer", (int)r);
-    CHOCO_REQUIRE(aligned4(a.srcs[r]), "source %d: pointer must be 4-byte aligned", (int)r);
-  }
-  int64_t sum = 0;
-  for (int32_t s = 0; s < a.nseg; ++s) {
-    const int i = (int)s;
-    CHOCO_REQUIRE(a.lens[s] >= 0, "tensor %d: negative length", i);
-    CHOCO_REQUIRE(a.dtypes[s] >= CHOCO_DT_F32 && a.dtypes[s] <= CHOCO_DT_F16, "tensor %d: unknown dtype code %d", i,
-                  (int)a.dtypes[s]);
-    CHOCO_REQUIRE(a.lens[s] <= a.n - sum, "the lengths add up to more than n = %lld", (long long)a.n);
-    sum += a.lens[s];
-    const uintptr_t esz = a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u;
-    CHOCO_REQUIRE((!use_p || mix_elem_aligned(a.params[s], esz)) && (!grad || mix_elem_aligned(a.grads[s], esz)),
-                  "tensor %d: pointer not aligned to its element size", i);
-    if (a.lens[s] == 0) continue;
-    CHOCO_REQUIRE(!use_p || a.params[s], "tensor %d: null param pointer", i);
-    CHOCO_REQUIRE(!grad || a.grads[s], "tensor %d: null grad pointer in a GRAD mode", i);
-  }
-  CHOCO_REQUIRE(sum == a.n, "the lengths add up to %lld, n is %lld", (long long)sum, (long long)a.n);
-  return CHOCO_OK;
+  return layout_check(
+      a.lens, a.dtypes, a.nseg, a.n,
+      [&]() -> int {
+        constexpr int32_t kModes = kGrad | CHOCO_MIX_WRITE_PARAMS | CHOCO_MIX_EXTRAPOLATE;
+        CHOCO_REQUIRE((a.mode & ~kModes) == 0, "unknown mode bits 0x%x", (unsigned)a.mode);
+        CHOCO_REQUIRE((a.mode & kGrad) != kGrad, "GRAD_SUB and GRAD_FMA are two gradient terms: one of them at most");
+        CHOCO_REQUIRE(!grad || a.grads, "a GRAD mode needs the grads table");
+        CHOCO_REQUIRE(!use_p || a.params, "WRITE_PARAMS, EXTRAPOLATE and x_out need the params table");
+        CHOCO_REQUIRE(a.flat_out || a.x_out || (a.mode & CHOCO_MIX_WRITE_PARAMS),
+                      "nothing to write: flat_out and x_out are null and the mode does not write the params");
+        CHOCO_REQUIRE(a.flat_out || !(a.mode & CHOCO_MIX_EXTRAPOLATE), "EXTRAPOLATE writes flat_out, which is null");
+        CHOCO_REQUIRE(a.nsrc <= kMixSrc || a.flat_out, "more than %d sources need flat_out for the running sum",
+                      kMixSrc);
+        CHOCO_REQUIRE(aligned4(a.flat_out) && aligned4(a.x_out), "flat_out and x_out must be 4-byte aligned");
+        CHOCO_REQUIRE(!grad || std::isfinite(a.lr), "lr must be finite, got %g", a.lr);
+        for (int32_t r = 0; r < a.nsrc; ++r) {
+          CHOCO_REQUIRE(a.srcs[r] || a.n == 0, "source %d: null pointer", (int)r);
+          CHOCO_REQUIRE(aligned4(a.srcs[r]), "source %d: pointer must be 4-byte aligned", (int)r);
+        }
+        return CHOCO_OK;
+      },
+      [&](int32_t s, uintptr_t esz) -> int {
+        const int i = (int)s;
+        CHOCO_REQUIRE((!use_p || elem_aligned(a.params[s], esz)) && (!grad || elem_aligned(a.grads[s], esz)),
+                      "tensor %d: pointer not aligned to its element size", i);
+        if (a.lens[s] == 0) return CHOCO_OK;
+        CHOCO_REQUIRE(!use_p || a.params[s], "tensor %d: null param pointer", i);
+        CHOCO_REQUIRE(!grad || a.grads[s], "tensor %d: null grad pointer in a GRAD mode", i);
+        return CHOCO_OK;
+      });
 }
 
 static int mix_run(const MixArgs& a, hipStream_t st) {
@@ -298,27 +270,18 @@ static int mix_run(const MixArgs& a, hipStream_t st) {
                              0.0f, (int32_t)0, (int32_t)(all16 ? 1 : 0)));
       continue;
     }
-    int64_t base = 0;
-    for (int32_t s0 = 0; s0 < a.nseg; s0 += kMixCap) {
-      const int nt = std::min<int32_t>(kMixCap, a.nseg - s0);
-      tb.nt = nt;
-      tb.off[0] = base;
+    CHOCO_TRY(for_chunks<kMixCap>(a.lens, a.nseg, tb.off, [&](const Chunk& c) -> int {
+      tb.nt = c.nt;
       for (int i = 0; i < kMixCap; ++i) {
-        const bool in = i < nt;
-        const int32_t s = s0 + i;
-        tb.p[i] = in && use_p ? a.params[s] : nullptr;
-        tb.g[i] = in && grad ? a.grads[s] : nullptr;
-        tb.dt[i] = in ? (uint8_t)a.dtypes[s] : (uint8_t)0;
-        base += in ? a.lens[s] : 0;
-        tb.off[i + 1] = base;
+        const bool in = i < c.nt;
+        tb.p[i] = in && use_p ? a.params[c.s0 + i] : nullptr;
+        tb.g[i] = in && grad ? a.grads[c.s0 + i] : nullptr;
+        tb.dt[i] = in ? (uint8_t)a.dtypes[c.s0 + i] : (uint8_t)0;
       }
-      // the tiles the chunk [off[0], off[nt]) touches; an empty chunk still takes its launch
-      const int64_t tile0 = tb.off[0] / kPbTile;
-      const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
-      CHOCO_TRY(CHOCO_LAUNCH("param_mix_kernel", "param_mix_kernel", param_mix_kernel, dim3((unsigned)tiles),
-                             dim3(kPbThreads), st, tb, sr, a.flat_out, a.x_out, tile0, lr, nlr, ea, eb, a.mode,
-                             (int32_t)(all16 ? 1 : 0)));
-    }
+      return CHOCO_LAUNCH("param_mix_kernel", "param_mix_kernel", param_mix_kernel, dim3((unsigned)c.tiles),
+                          dim3(kPbThreads), st, tb, sr, a.flat_out, a.x_out, c.tile0, lr, nlr, ea, eb, a.mode,
+                          (int32_t)(all16 ? 1 : 0));
+    }));
   }
   return CHOCO_OK;
 }

@@ -20,15 +20,15 @@
 //   the launch  the parameter bridge's shape (params.hip): workgroups own 8192-element tiles at
 //               absolute flat offsets, the table of a chunk of tensors travels in the kernel
 //               arguments (scalar loads), the first tensor of a tile is found by the same uniform
-//               upper-bound search, zero-length tensors are skipped (sgd_tile_walk); row s of the
+//               upper-bound search, zero-length tensors are skipped (tile_walk, param_common.h); row s of the
 //               table becomes an SgdTensor (sgd_decode), and a kernel sets only what is its own.
 //   the test    a tensor takes the 16-byte path when the kernel's flat buffers are 16-byte aligned
 //               and every side the update touches is congruent with the group grid at that
-//               side's own element size (sgd_congruent); the dtype switch (sgd_for_dtype).
+//               side's own element size (sgd_congruent, on param_common.h's rule); the dtype switch (for_dtype).
 //   the lines   sgd_math, and the host side: one check, one table build, one launch switch.
 // Whole groups then move as 16-byte vectors, non-temporal, every load of a group issued before
 // its first store; cut groups and every other tensor move element by element, coalesced.  The
-// master and the flat-gradient kernels do that through one span walk (sgd_walk) and one element /
+// master and the flat-gradient kernels do that through the shared span walk (span_walk) and one element /
 // group body (SgdBody), compiled for the tensor's dtype, the parameter side and the gradient
 // source:
 //     parameter side  the tensor itself: bf16 / fp16 lines are computed in fp32 from the widened
@@ -50,10 +50,9 @@
 // bytes of its own elements.  g and buf of one tensor may be the same memory (the update is
 // elementwise; where both are written, d is stored last); distinct tensors must not overlap,
 // which is not checked.  The gradient norms these updates clip by: gradnorm.hip.
-#include "dispatch.h"
 #include "param_common.h"
 
-#include <algorithm>
+#include <cmath>
 
 namespace choco {
 
@@ -116,42 +115,17 @@ CHOCO_DEV SgdTensor sgd_decode(const SgdTable& tb, int s) {
   return t;
 }
 
-// f(s, a, b) for every tensor s of the table that has flat elements [a, b), a < b, in workgroup
-// `tile`'s share of the chunk
-template <typename F>
-CHOCO_DEV void sgd_tile_walk(const SgdTable& tb, int64_t tile, F&& f) {
-  const int nt = tb.nt;
-  int64_t tlo, thi;
-  const int s0 = tile_first_tensor(tb.off, nt, tile, tlo, thi);
-  if (s0 < 0) return;
-  for (int s = s0; s < nt; ++s) {
-    const int64_t o0 = tb.off[s];
-    if (o0 >= thi) break;
-    const int64_t a = i64max(o0, tlo), b = i64min(tb.off[s + 1], thi);
-    if (a < b) f(s, a, b);  // a zero-length tensor is passed over
-  }
-}
-
-// Is every whole group's start 16-byte aligned on every side the tensor touches?  A flat side,
-// base + 4 e, is at every group start e (a multiple of 8) when the base is: the caller's test.  A
-// tensor's side q + esz (e - o0) is when q - esz o0 is, esz e being a multiple of 16 -- esz the
-// tensor's own, but 4 for a master update's momentum buffer.
+// Is every whole group's start 16-byte aligned on every side the tensor touches (param_common.h's
+// rule; the flat sides are the caller's test)?  The element size is the tensor's own, but 4 for a
+// master update's momentum buffer.
 template <bool MASTER>
 CHOCO_DEV bool sgd_congruent(const SgdTensor& t) {
-  const uintptr_t esz = t.dt == CHOCO_DT_F32 ? 4u : 2u, o = (uintptr_t)t.o0;
+  const uintptr_t esz = dtype_size(t.dt);
   uintptr_t mis = 0;
-  if (MASTER ? t.wr_p : t.rd_p || t.wr_p) mis |= reinterpret_cast<uintptr_t>(t.p) - esz * o;
-  if (t.rd_g || t.wr_g) mis |= reinterpret_cast<uintptr_t>(t.g) - esz * o;
-  if (t.rd_b || t.wr_b) mis |= reinterpret_cast<uintptr_t>(t.buf) - (MASTER ? 4u : esz) * o;
-  return (mis & 15u) == 0;
-}
-
-// f(int_c<DT>) for the dtype code dt
-template <typename F>
-CHOCO_DEV void sgd_for_dtype(int dt, F&& f) {
-  if (dt == CHOCO_DT_F32) f(int_c<CHOCO_DT_F32>{});
-  else if (dt == CHOCO_DT_BF16) f(int_c<CHOCO_DT_BF16>{});
-  else f(int_c<CHOCO_DT_F16>{});
+  if (MASTER ? t.wr_p : t.rd_p || t.wr_p) mis |= mis16(t.p, esz, t.o0);
+  if (t.rd_g || t.wr_g) mis |= mis16(t.g, esz, t.o0);
+  if (t.rd_b || t.wr_b) mis |= mis16(t.buf, MASTER ? 4u : esz, t.o0);
+  return on_grid16(mis);
 }
 
 // rnd<DT>(v), the value as the storage dtype holds it: param_common.h
@@ -180,36 +154,10 @@ CHOCO_DEV void sgd_math(const SgdTensor& t, float p, float g, float b, float& bu
   out = t.grad_mode ? d : rnd<DT>(fmaf(t.nlr, d, p));
 }
 
-// Flat elements [a, b) of a tensor, a < b inside this workgroup's tile.  vec: every side the
-// update touches is 16-byte aligned at every whole group's start.  One 8-element group in flight
-// per thread; the body supplies elem(i), one element at flat index i, and group(e), one whole
-// group at flat index e, every load issued before the first store.  A group's loads and its
-// update stand under ONE test, so that the group path and the element path exclude each other:
-// with the loads in a phase of their own, ahead of the element path, these kernels take 8 to 16
-// VGPRs more and lose a wave of occupancy.
-template <typename BODY>
-CHOCO_DEV void sgd_walk(const BODY& body, int64_t a, int64_t b, bool vec) {
-  const int tid = threadIdx.x;
-  if (!vec) {
-    for (int64_t i = a + tid; i < b; i += kPbThreads) body.elem(i);
-    return;
-  }
-  const int64_t g0 = a >> 3, g1 = (b - 1) >> 3;  // groups at absolute flat offsets, inclusive
-  for (int64_t gb = g0; gb <= g1; gb += kPbThreads) {
-    const int64_t e = (gb + tid) * kPbGroup;
-    if (e >= a && e + kPbGroup <= b) {
-      body.group(e);
-    } else {
-      // a group cut by the tensor's start or end (or past the span): its own elements only
-      const int64_t ea = e > a ? e : a, eb = e + kPbGroup < b ? e + kPbGroup : b;
-      for (int64_t i = ea; i < eb; ++i) body.elem(i);
-    }
-  }
-}
-
 enum SgdGrad { kGradOwn, kGradCoef, kGradFlat };  // the gradient source
 
-// The update of one element and of one group, for the master and the flat-gradient kernels.
+// The update of one element and of one group, for the master and the flat-gradient kernels
+// (span_walk's body, param_common.h).
 template <int DT, bool MASTER, int GS>
 struct SgdBody {
   static constexpr int MDT = MASTER ? CHOCO_DT_F32 : DT;  // the arithmetic's and the momentum buffer's dtype
@@ -270,7 +218,7 @@ struct SgdBody {
 template <bool MASTER, int GS>
 CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t a, int64_t b, bool flat16) {
   const bool vec = flat16 && sgd_congruent<MASTER>(t);
-  sgd_for_dtype(t.dt, [&](auto DT) { sgd_walk(SgdBody<DT, MASTER, GS>{t}, a, b, vec); });
+  for_dtype(t.dt, [&](auto DT) { span_walk(SgdBody<DT, MASTER, GS>{t}, a, b, vec); });
 }
 
 // ------------------------------------------------------------------ the update fused with the pack
@@ -294,7 +242,7 @@ CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t a, int64_t b, bool flat16) {
 // its sides are optional (a pack-only tensor reads p alone, grad mode may not read p at all), it
 // has the flat output with ADD_FLAT and the per-tensor clip, and its walk issues the loads of a
 // thread's kSgdU groups in a phase of their own, ahead of a cut group's element path.  With
-// plain_elem / plain_span written as a body for sgd_walk (the same lines behind load / update,
+// plain_elem / plain_span written as a body for span_walk (the same lines behind load / update,
 // loads ahead) the bf16 ResNet-50 update took 124.2 to 125.3 us against the 111.9 to 112.8 of
 // the code before, the gclip instantiation 120.1 to 121.8 against 104.2 to 104.7, the clip one
 // 133.4 to 133.5 against 118.7 to 119.8, in one visit; as below it took 108.0 to 111.8, 104.4 to
@@ -387,7 +335,7 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
   const float gc = GC ? norms[SC ? 1 : 0] : 1.0f;  // a uniform load
   const bool found = SC && norms[2] != 0.0f;       // ... and another
   if (SC && found && flat == nullptr) return;
-  sgd_tile_walk(tb, tile0 + blockIdx.x, [&](int s, int64_t a, int64_t b) {
+  tile_walk(tb.off, tb.nt, tile0 + blockIdx.x, [&](int s, int64_t a, int64_t b) {
     SgdTensor t = sgd_decode(tb, s);
     t.flat = flat;
     t.pack_only = t.nograd || (SC && found);
@@ -409,7 +357,7 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
     t.wr_c = GC && !t.pack_only && (mode & CHOCO_SGD_MODE_WRITE_CLIPPED) != 0;  // apply mode (the host's check)
     t.gc = gc;
     const bool vec = (flat == nullptr || flat16) && sgd_congruent<false>(t);
-    sgd_for_dtype(t.dt, [&](auto DT) { plain_span<DT, GC>(t, t.o0, a, b, vec); });
+    for_dtype(t.dt, [&](auto DT) { plain_span<DT, GC>(t, t.o0, a, b, vec); });
   });
 }
 
@@ -438,7 +386,7 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_master_kernel(const SgdT
   float gc = 1.0f;
   ((gc = coef_of(coef)), ...);  // a uniform load
   if ((found_of(coef) || ...)) return;  // ... and, in the scaled instantiation alone, another
-  sgd_tile_walk(tb, tile0 + blockIdx.x, [&](int s, int64_t a, int64_t b) {
+  tile_walk(tb.off, tb.nt, tile0 + blockIdx.x, [&](int s, int64_t a, int64_t b) {
     SgdTensor t = sgd_decode(tb, s);
     if (t.nograd) return;  // no gradient: passed over
     t.master = master;
@@ -476,7 +424,7 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_flatgrad_kernel(const Sg
                                                                         float* master, int64_t tile0, float div,
                                                                         int32_t al16, int32_t mode, SLOT... slot) {
   if ((found_of(slot) || ...)) return;  // in the scaled instantiations alone
-  sgd_tile_walk(tb, tile0 + blockIdx.x, [&](int s, int64_t a, int64_t b) {
+  tile_walk(tb.off, tb.nt, tile0 + blockIdx.x, [&](int s, int64_t a, int64_t b) {
     SgdTensor t = sgd_decode(tb, s);
     t.gsum = gsum;
     t.master = master;
@@ -489,7 +437,7 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_flatgrad_kernel(const Sg
 }
 
 // ------------------------------------------------------------------ the host side
-static int sgd_launches(int32_t nseg) { return nseg <= 0 ? 0 : (nseg + kSgdCap - 1) / kSgdCap; }
+static int sgd_launches(int32_t nseg) { return chunk_launches(nseg, kSgdCap); }
 
 // The gradient side of an entry point; with `master`, the parameter side, that names the kernel.
 enum class SgdKind {
@@ -602,43 +550,35 @@ static int sgd_check(const SgdArgs& a) {
   CHOCO_REQUIRE(a.params && (a.grads || fg) && a.bufs && a.lens && a.dtypes && a.lr && a.wd && a.mom && a.damp &&
                     a.flags,
                 "null table argument");
-  CHOCO_REQUIRE(a.nseg > 0, "nseg must be positive, got %d", (int)a.nseg);
-  CHOCO_REQUIRE(a.n >= 0 && a.n <= (int64_t)INT32_MAX, "n must be in [0, 2^31), got %lld", (long long)a.n);
-  CHOCO_TRY(fg ? flatgrad_mode_check(a) : own_grad_mode_check(a));
   const bool grad_mode = (a.mode & CHOCO_SGD_MODE_GRAD) != 0;
-  int64_t sum = 0;
-  for (int32_t s = 0; s < a.nseg; ++s) {
-    const int i = (int)s;
-    CHOCO_REQUIRE(a.lens[s] >= 0, "tensor %d: negative length", i);
-    CHOCO_REQUIRE(a.dtypes[s] >= CHOCO_DT_F32 && a.dtypes[s] <= CHOCO_DT_F16, "tensor %d: unknown dtype code %d", i,
-                  (int)a.dtypes[s]);
-    CHOCO_REQUIRE(a.lens[s] <= a.n - sum, "the lengths add up to more than n = %lld", (long long)a.n);
-    sum += a.lens[s];
-    constexpr int32_t kFlags = CHOCO_SGD_F_NESTEROV | CHOCO_SGD_F_FIRST | CHOCO_SGD_F_NOGRAD;
-    CHOCO_REQUIRE((a.flags[s] & ~kFlags) == 0, "tensor %d: unknown flag bits 0x%x", i, (unsigned)a.flags[s]);
-    const bool nograd = (a.flags[s] & CHOCO_SGD_F_NOGRAD) != 0;
-    if (fg) CHOCO_REQUIRE(!nograd, "tensor %d: a no-grad tensor has no slot to skip in the flat gradient", i);
-    CHOCO_REQUIRE(!(nograd && grad_mode), "tensor %d: a no-grad tensor in grad mode", i);
-    const uintptr_t esz = a.dtypes[s] == CHOCO_DT_F32 ? 4u : 2u;
-    CHOCO_REQUIRE(elem_aligned(a.params[s], esz) && (!a.grads || elem_aligned(a.grads[s], esz)) &&
-                      elem_aligned(a.bufs[s], a.master ? 4u : esz),  // a master update's buffers are fp32
-                  "tensor %d: pointer not aligned to its element size", i);
-    if (!nograd) {
-      // the reference's constructors refuse these (torch.optim.SGD's rule)
-      CHOCO_REQUIRE(!((a.flags[s] & CHOCO_SGD_F_NESTEROV) && (!(a.mom[s] > 0.0) || a.damp[s] != 0.0)),
-                    "tensor %d: nesterov needs momentum > 0 and dampening == 0", i);
-    }
-    if (a.lens[s] == 0) continue;
-    CHOCO_REQUIRE(a.params[s], "tensor %d: null param pointer", i);
-    if (nograd) continue;
-    if (fg)
-      CHOCO_REQUIRE(!(a.mode & CHOCO_SGD_MODE_WRITE_GRADS) || a.grads[s],
-                    "tensor %d: null grad pointer with WRITE_GRADS", i);
-    else
-      CHOCO_REQUIRE(a.grads[s], "tensor %d: null grad pointer without the no-grad flag", i);
-    CHOCO_REQUIRE(a.bufs[s] || a.mom[s] == 0.0, "tensor %d: null momentum buffer with momentum != 0", i);
-  }
-  CHOCO_REQUIRE(sum == a.n, "the lengths add up to %lld, n is %lld", (long long)sum, (long long)a.n);
+  CHOCO_TRY(layout_check(
+      a.lens, a.dtypes, a.nseg, a.n, [&]() -> int { return fg ? flatgrad_mode_check(a) : own_grad_mode_check(a); },
+      [&](int32_t s, uintptr_t esz) -> int {
+        const int i = (int)s;
+        constexpr int32_t kFlags = CHOCO_SGD_F_NESTEROV | CHOCO_SGD_F_FIRST | CHOCO_SGD_F_NOGRAD;
+        CHOCO_REQUIRE((a.flags[s] & ~kFlags) == 0, "tensor %d: unknown flag bits 0x%x", i, (unsigned)a.flags[s]);
+        const bool nograd = (a.flags[s] & CHOCO_SGD_F_NOGRAD) != 0;
+        if (fg) CHOCO_REQUIRE(!nograd, "tensor %d: a no-grad tensor has no slot to skip in the flat gradient", i);
+        CHOCO_REQUIRE(!(nograd && grad_mode), "tensor %d: a no-grad tensor in grad mode", i);
+        CHOCO_REQUIRE(elem_aligned(a.params[s], esz) && (!a.grads || elem_aligned(a.grads[s], esz)) &&
+                          elem_aligned(a.bufs[s], a.master ? 4u : esz),  // a master update's buffers are fp32
+                      "tensor %d: pointer not aligned to its element size", i);
+        if (!nograd) {
+          // the reference's constructors refuse these (torch.optim.SGD's rule)
+          CHOCO_REQUIRE(!((a.flags[s] & CHOCO_SGD_F_NESTEROV) && (!(a.mom[s] > 0.0) || a.damp[s] != 0.0)),
+                        "tensor %d: nesterov needs momentum > 0 and dampening == 0", i);
+        }
+        if (a.lens[s] == 0) return CHOCO_OK;
+        CHOCO_REQUIRE(a.params[s], "tensor %d: null param pointer", i);
+        if (nograd) return CHOCO_OK;
+        if (fg)
+          CHOCO_REQUIRE(!(a.mode & CHOCO_SGD_MODE_WRITE_GRADS) || a.grads[s],
+                        "tensor %d: null grad pointer with WRITE_GRADS", i);
+        else
+          CHOCO_REQUIRE(a.grads[s], "tensor %d: null grad pointer without the no-grad flag", i);
+        CHOCO_REQUIRE(a.bufs[s] || a.mom[s] == 0.0, "tensor %d: null momentum buffer with momentum != 0", i);
+        return CHOCO_OK;
+      }));
   if (fg) CHOCO_REQUIRE((a.n == 0 && a.kind != SgdKind::FlatgradScaled) || a.gsum, "gsum is null");
   return CHOCO_OK;
 }
@@ -656,13 +596,12 @@ static int sgd_run(const SgdArgs& a, hipStream_t st) {
   const float div = (float)a.divisor;
   const float* const none = nullptr;
   SgdTable tb;
-  int64_t base = 0;
-  for (int32_t s0 = 0; s0 < a.nseg; s0 += kSgdCap) {
-    const int nt = std::min<int32_t>(kSgdCap, a.nseg - s0);
-    tb.nt = nt;
-    tb.off[0] = base;
+  return for_chunks<kSgdCap>(a.lens, a.nseg, tb.off, [&](const Chunk& c) -> int {
+    const int32_t s0 = c.s0;
+    const int64_t tile0 = c.tile0, tiles = c.tiles;
+    tb.nt = c.nt;
     for (int i = 0; i < kSgdCap; ++i) {
-      const bool in = i < nt;
+      const bool in = i < c.nt;
       const int32_t s = s0 + i;
       const bool upd = in && !(a.flags[s] & CHOCO_SGD_F_NOGRAD);
       tb.p[i] = in ? a.params[s] : nullptr;
@@ -678,12 +617,7 @@ static int sgd_run(const SgdArgs& a, hipStream_t st) {
       if (upd && a.wd[s] != 0.0) fl |= kSgdHasWd;
       if (upd && a.mom[s] != 0.0) fl |= kSgdHasMom;
       tb.fl[i] = (uint8_t)fl;
-      base += in ? a.lens[s] : 0;
-      tb.off[i + 1] = base;
     }
-    // the tiles the chunk [off[0], off[nt]) touches; an empty chunk still takes its launch
-    const int64_t tile0 = tb.off[0] / kPbTile;
-    const int64_t tiles = tb.off[nt] > tb.off[0] ? (tb.off[nt] - 1) / kPbTile - tile0 + 1 : 1;
     // the kernel of (kind, master) under its profile name, with its own argument list; a.flat is
     // the master copy where there is one, and null in a flat-gradient update without
     int rc = CHOCO_OK;
@@ -726,9 +660,8 @@ static int sgd_run(const SgdArgs& a, hipStream_t st) {
                             FoundSlot{a.gsum + a.n});
         break;
     }
-    CHOCO_TRY(rc);
-  }
-  return CHOCO_OK;
+    return rc;
+  });
 }
 
 }  // namespace choco
