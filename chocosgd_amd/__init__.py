@@ -3,6 +3,7 @@
 Drop-in modules (same class/function names as the reference's dl_code/pcode):
   chocosgd_amd.sparsification   <- pcode/utils/sparsification.py
   chocosgd_amd.parallel_choco   <- pcode/optim/parallel_choco_v.py (CHOCOCompressor & co.)
+  chocosgd_amd.wire             (what the compressor drop-ins share; the wire format is codec.py's)
   chocosgd_amd.tensor_buffer    <- pcode/utils/tensor_buffer.py
   chocosgd_amd.communication    <- pcode/utils/communication.py (decentralized exchange)
   chocosgd_amd.utils            <- pcode/optim/utils.py (recover_params, update_params_from_neighbor)

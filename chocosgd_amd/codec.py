@@ -572,6 +572,26 @@ def sign_wire(n, nseg, dev):
     return msg, (msg[hw:], msg[:hw].view(torch.float32)[:nseg])
 
 
+def sign_split(message, nseg):
+    """A received sign wire message taken apart: (int32 words, fp32 norms[nseg]), views of it."""
+    hw = wire_header_words(nseg)
+    return message[hw:], message[:hw].view(torch.float32)[:nseg].contiguous()
+
+
+def sparse_wire(k, dev):
+    """One sparse wire message [fp32 values[k] | int32 global indices[k]] and the (values,
+    indices) views topk_segmented / randk_segmented(out=...) fill in place."""
+    msg = torch.empty(2 * k, dtype=torch.int32, device=dev)
+    return msg, sparse_split(msg)
+
+
+def sparse_split(message, size=None):
+    """A sparse wire message taken apart: (fp32 values, int32 indices), views of it.  `size`:
+    the length every message of the exchange has (the sender's own), default this one's."""
+    k = (message.numel() if size is None else int(size)) // 2
+    return message[:k].view(torch.float32), message[k:]
+
+
 def sign_compress(x, xhat=None, seg_off=None, nseg=1, want_norms=True, gossip=None, out=None):
     """Pack sign bits in the (32, N') layout; optionally per-segment L1 norms (fp64-accumulated).
     `gossip=(memory, gamma)` fuses the consensus step; `out=(packed int32[N'], norms f32[nseg])`
@@ -809,6 +829,13 @@ def qsgd_wire(n, q, nseg, dev):
     msg = torch.empty(hb + qsgd_packed_bytes(n, q), dtype=torch.uint8, device=dev)
     msg[:hb].zero_()
     return msg, (msg[hb:], msg[:hb].view(torch.float32)[:nseg])
+
+
+def qsgd_split(message, nseg):
+    """A received QSGD wire message taken apart: (uint8 planes, fp32 norms[nseg]), views of it.
+    The header of a chunked message (qsgd_chunked_wire), sent alone, gives its norms."""
+    hb = 4 * wire_header_words(nseg)
+    return message[hb:], message[:hb].view(torch.float32)[:nseg].contiguous()
 
 
 def qsgd_compress(x, q, is_biased=False, xhat=None, seg_off=None, nseg=1, norm_in=None, u_in=None,

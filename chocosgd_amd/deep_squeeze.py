@@ -26,30 +26,8 @@ step as one torch op per line (CPU tensors).
 import torch
 
 from . import codec, utils
-from .communication import recover_device
-from .dcd import _ConsumerBase
 from .tensor_buffer import TensorBuffer
-
-
-class DeepSqueezeCompressor(object):
-    def __init__(self, **kargs):
-        if "top_k" in kargs["comm_op"] or "random_k" in kargs["comm_op"]:
-            self.compressor_fn = DeepSqueezeSparsificationCompressor(**kargs)
-        elif "quantize" in kargs["comm_op"]:
-            self.compressor_fn = DeepSqueezeQuantizationCompressor(**kargs)
-        elif "sign" in kargs["comm_op"]:
-            self.compressor_fn = DeepSqueezeSignCompressor(**kargs)
-        else:
-            raise NotImplementedError
-
-    def compress(self, *args, **kargs):
-        return self.compressor_fn.compress(*args, **kargs)
-
-    def sync(self, *args, **kargs):
-        return self.compressor_fn.sync(*args, **kargs)
-
-    def uncompress(self, *args, **kargs):
-        return self.compressor_fn.uncompress(*args, **kargs)
+from .wire import _Consumer, _Facade, _QsgdConsumer, _SignConsumer, _SparseConsumer
 
 
 def step_loop(compressor, param_groups, param_names, state, shapes, memory, neighbors_info):
@@ -94,7 +72,11 @@ def fused_step(compressor, param_groups, param_names, state, shapes, memory, nei
     return sync_buffer["n_bits"]
 
 
-class _DeepSqueezeBase(_ConsumerBase):
+
+
+class _DeepSqueezeBase(_Consumer):
+    norms_key, synced_norms_key = "param_norms_tb", "synced_param_norms"
+
     def __init__(self, aggregator, rank, comm_op, comm_device, compress_ratio, quantize_level, is_biased, backend,
                  use_ipc, consensus_stepsize, **kargs):
         super().__init__(aggregator, comm_op, comm_device, compress_ratio, quantize_level, is_biased, backend,
@@ -103,12 +85,19 @@ class _DeepSqueezeBase(_ConsumerBase):
         self.consensus_stepsize = consensus_stepsize
 
     def _inputs(self, sync_buffer):
+        """The error-compensated memory, compressed as is (no x_hat)."""
         tb = sync_buffer["params_tb"]
         x = tb.buffer
         lay = self._layout(sync_buffer, x.device)
         if lay.n != x.numel():
             raise RuntimeError("original_shapes do not match params_tb")
         return tb, x, lay
+
+    def _aggregate(self, sync_buffer, neighbors_info, received):
+        """params_tb, zeros like it, and the codec's receive iteration over the neighbours into them."""
+        tb = sync_buffer["params_tb"]
+        agg = torch.zeros_like(tb.buffer)
+        return tb, agg, received(sync_buffer, ((rank, agg) for rank in neighbors_info.keys()))
 
     def _weight(self, neighbors_info, rank):
         # deep_squeeze.py:275-277 -- a Python double, rounded to fp32 where torch multiplies
@@ -119,18 +108,8 @@ class _DeepSqueezeBase(_ConsumerBase):
         return TensorBuffer.from_flat(buffer, tb._tensors_sizes)
 
 
-class DeepSqueezeSparsificationCompressor(_DeepSqueezeBase):
+class DeepSqueezeSparsificationCompressor(_DeepSqueezeBase, _SparseConsumer):
     """top-k / random-k  (deep_squeeze.py:158-279)."""
-
-    def __init__(self, *args, **kargs):
-        super().__init__(*args, **kargs)
-        self._guards = {}
-
-    def _guard(self, dev):
-        g = self._guards.get(dev)
-        if g is None:
-            g = self._guards[dev] = codec.IndexGuard(dev)
-        return g
 
     def compress(self, sync_buffer, residual=False):
         """residual: params_tb.buffer -= local copy in place, at the selected positions only
@@ -144,27 +123,17 @@ class DeepSqueezeSparsificationCompressor(_DeepSqueezeBase):
         codec.sparse_accumulate(values, indices, local, 1.0)  # local[idx] = v  (deep_squeeze.py:206-208)
         return self._like(tb, local)
 
-    def sync(self, sync_buffer):
-        message = sync_buffer["wire_message"]
-        sync_buffer["synced_message"] = self._send(message)
-        sync_buffer["sycned_message_size"] = len(message)
-
     def uncompress(self, sync_buffer, neighbors_info):
-        tb = sync_buffer["params_tb"]
-        dev = tb.buffer.device
-        agg = torch.zeros_like(tb.buffer)
-        K = int(sync_buffer["sycned_message_size"] / 2)
-        guard = self._guard(dev)
-        for rank in neighbors_info.keys():
-            msg = recover_device(sync_buffer["synced_message"][rank], device=dev)
+        tb, agg, received = self._aggregate(sync_buffer, neighbors_info, self._sparse_received)
+        for rank, _, (values, indices) in received:
             # agg[idx] += c * v  (two roundings, deep_squeeze.py:274-278)
-            codec.sparse_accumulate(msg[:K].view(torch.float32), msg[K:], agg, self._weight(neighbors_info, rank),
-                                    guard=guard)
-        guard.check_then_arm()  # bad indices of an earlier step, after this step's work
+            codec.sparse_accumulate(values, indices, agg, self._weight(neighbors_info, rank),
+                                    guard=self._guards[agg.device])
+        self._guards.sweep()
         return self._like(tb, agg)
 
 
-class DeepSqueezeQuantizationCompressor(_DeepSqueezeBase):
+class DeepSqueezeQuantizationCompressor(_DeepSqueezeBase, _QsgdConsumer):
     """QSGD  (deep_squeeze.py:282-376)."""
 
     def compress(self, sync_buffer, residual=False):
@@ -179,37 +148,29 @@ class DeepSqueezeQuantizationCompressor(_DeepSqueezeBase):
             return None
         return self._like(tb, dense.clone() if int(self.quantize_level) == 32 else dense)
 
-    def sync(self, sync_buffer):
-        sync_buffer["synced_message"] = self._send(sync_buffer["flatten_updates"].buffer)
-
     def uncompress(self, sync_buffer, neighbors_info):
-        tb = sync_buffer["params_tb"]
-        dev = tb.buffer.device
-        lay = self._layout(sync_buffer, dev)
-        agg = torch.zeros_like(tb.buffer)
+        tb, agg, received = self._aggregate(sync_buffer, neighbors_info, self._qsgd_received)
+        lay = self._layout(sync_buffer, agg.device)
         q = int(self.quantize_level)
-        for rank in neighbors_info.keys():
-            msg = recover_device(sync_buffer["synced_message"][rank], device=dev)
+        for rank, _, msg in received:
             c = self._weight(neighbors_info, rank)
             if q == 32:
-                agg.add_(c * msg.view(torch.float32))
+                agg.add_(c * msg)
                 continue
             # agg += c * decode(msg)  (two roundings, deep_squeeze.py:371-375)
-            codec.qsgd_accumulate([self._qsgd_part(msg, lay)], [c], -1, lay.n, q, agg, is_biased=self.is_biased,
-                                  seg_off=lay.seg_off, nseg=lay.nseg)
+            codec.qsgd_accumulate([msg], [c], -1, lay.n, q, agg, is_biased=self.is_biased, seg_off=lay.seg_off,
+                                  nseg=lay.nseg)
         return self._like(tb, agg)
 
 
-class DeepSqueezeSignCompressor(_DeepSqueezeBase):
-    """sign + per-tensor L1 norm  (deep_squeeze.py:379-489); norms and signs travel in ONE
-    message, `synced_param_norms` / `synced_signs` are views of it."""
+class DeepSqueezeSignCompressor(_DeepSqueezeBase, _SignConsumer):
+    """sign + per-tensor L1 norm  (deep_squeeze.py:379-489)."""
 
     def compress(self, sync_buffer, residual=False):
         """residual: params_tb.buffer -= local copy in place, in the pass that decodes it
         (codec.sign_local_residual); returns None."""
         tb, x, lay = self._inputs(sync_buffer)
-        signs, norms = self._sign_message(sync_buffer, x, None, lay)
-        sync_buffer["param_norms_tb"] = TensorBuffer.from_flat(norms, [() for _ in range(lay.nseg)])
+        _, norms = self._sign_message(sync_buffer, x, None, lay)
         if residual:
             codec.sign_local_residual(x, norms, seg_off=lay.seg_off, nseg=lay.nseg, resid_out=x)
             return None
@@ -217,21 +178,16 @@ class DeepSqueezeSignCompressor(_DeepSqueezeBase):
         local = codec.sign_local_decode(x, norms, seg_off=lay.seg_off, nseg=lay.nseg)
         return self._like(tb, local)
 
-    def sync(self, sync_buffer):
-        norms = sync_buffer["param_norms_tb"].buffer
-        synced = self._send(self._sign_wire(sync_buffer))
-        sync_buffer["synced_message"] = synced
-        sync_buffer["synced_param_norms"], sync_buffer["synced_signs"] = self._sign_parts(synced, norms.numel())
-
     def uncompress(self, sync_buffer, neighbors_info):
-        tb = sync_buffer["params_tb"]
-        dev = tb.buffer.device
-        lay = self._layout(sync_buffer, dev)
-        agg = torch.zeros_like(tb.buffer)
-        for rank in neighbors_info.keys():
-            nm = recover_device(sync_buffer["synced_param_norms"][rank], device=dev).contiguous()
-            sg = recover_device(sync_buffer["synced_signs"][rank], device=dev)
+        tb, agg, received = self._aggregate(sync_buffer, neighbors_info, self._sign_received)
+        lay = self._layout(sync_buffer, agg.device)
+        for rank, _, msg in received:
             # agg_s.add_(c * (norm_s / numel_s * sign_s))  (two roundings, deep_squeeze.py:481-488)
-            codec.sign_axpy([(sg, nm)], [self._weight(neighbors_info, rank)], lay.n, agg, seg_off=lay.seg_off,
+            codec.sign_axpy([msg], [self._weight(neighbors_info, rank)], lay.n, agg, seg_off=lay.seg_off,
                             nseg=lay.nseg, two_roundings=True)
         return self._like(tb, agg)
+
+
+class DeepSqueezeCompressor(_Facade):
+    sparsification, quantization, sign = (DeepSqueezeSparsificationCompressor, DeepSqueezeQuantizationCompressor,
+                                          DeepSqueezeSignCompressor)

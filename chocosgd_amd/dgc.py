@@ -40,9 +40,9 @@ import torch
 
 from . import codec, utils
 from .communication import recover_device
-from .parallel_choco import _Layout
 from .sparsification import _draw_seed, get_n_bits
 from .tensor_buffer import flatten
+from .wire import _Layout, _received, _staged
 
 
 _warned = []
@@ -135,25 +135,22 @@ class DGCCodec(object):
 
     def sync(self, selected_values, selected_indices):
         if self.is_compress_op:
-            message = torch.cat([selected_values.view(torch.int32), selected_indices])
-            if self.comm_device == "cpu":
-                message = message.cpu().pin_memory()
+            # the sparse wire [values | indices] (codec.sparse_wire), joined here: this method takes
+            # the two tensors compress returned, and they need not share one buffer
+            message = _staged(torch.cat([selected_values.view(torch.int32), selected_indices]), self.comm_device)
             synced = self.world_aggregator._agg(message, communication_scheme="all_gather")
         else:
-            message = selected_values
-            if self.comm_device == "cpu":
-                message = message.cpu().pin_memory()
+            message = _staged(selected_values, self.comm_device)
             synced = self.world_aggregator._agg(message, op="sum", communication_scheme="all_reduce")
         return synced, len(message)
 
     def recover_info(self, flatten_params, synced_message, message_size, lr):
         if self.is_compress_op:
-            K = int(message_size / 2)
             grads = torch.zeros_like(flatten_params)
-            for message in synced_message:
-                m = recover_device(message, device=flatten_params.device)
+            ranks = ((rank, grads) for rank in range(len(synced_message)))
+            for _, _, (values, indices) in _received(synced_message, ranks, codec.sparse_split, message_size):
                 # empty_grads[q_indices] += q_values  (dgc.py:234-242), messages in rank order
-                codec.sparse_accumulate(m[:K].view(torch.float32), m[K:], grads, 1.0)
+                codec.sparse_accumulate(values, indices, grads, 1.0)
             update = grads
         else:
             update = recover_device(synced_message, device=flatten_params.device)

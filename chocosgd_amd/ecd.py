@@ -18,30 +18,8 @@ extrapolated model (codec.params_mix), then compress / sync / uncompress;
 import torch
 
 from . import codec, utils
-from .communication import recover_device
-from .dcd import _ConsumerBase
 from .tensor_buffer import TensorBuffer
-
-
-class ECDCompressor(object):
-    def __init__(self, **kargs):
-        if "top_k" in kargs["comm_op"] or "random_k" in kargs["comm_op"]:
-            self.compressor_fn = ECDSparsificationCompressor(**kargs)
-        elif "quantize" in kargs["comm_op"]:
-            self.compressor_fn = ECDQuantizationCompressor(**kargs)
-        elif "sign" in kargs["comm_op"]:
-            self.compressor_fn = ECDSignCompressor(**kargs)
-        else:
-            raise NotImplementedError
-
-    def compress(self, *args, **kargs):
-        return self.compressor_fn.compress(*args, **kargs)
-
-    def sync(self, *args, **kargs):
-        return self.compressor_fn.sync(*args, **kargs)
-
-    def uncompress(self, *args, **kargs):
-        return self.compressor_fn.uncompress(*args, **kargs)
+from .wire import _Facade, _QsgdConsumer, _SignConsumer, _SparseConsumer
 
 
 def _finish(compressor, sync_buffer, neighbor_hat_params, local_index):
@@ -96,88 +74,60 @@ def _coeffs(local_index):
     return 1 - 2 / local_index, 2 / local_index
 
 
-class _ECDBase(_ConsumerBase):
-    def _x(self, sync_buffer):
+class _ECDInputs(object):
+    """The extrapolated model, compressed as is (no x_hat)."""
+
+    def _inputs(self, sync_buffer):
         x = sync_buffer["flatten_updated_params"].buffer
-        return x, self._layout(sync_buffer, x.device)
+        return x, None, self._layout(sync_buffer, x.device)
 
 
-class ECDSparsificationCompressor(_ECDBase):
+class ECDSparsificationCompressor(_ECDInputs, _SparseConsumer):
     """top-k / random-k  (ecd_psgd.py:211-303)."""
 
-    def __init__(self, *args, **kargs):
-        super().__init__(*args, **kargs)
-        self._guards = {}
-
     def compress(self, sync_buffer):
-        x, lay = self._x(sync_buffer)
-        self._sparse_message(sync_buffer, x, None, lay)
-
-    def sync(self, sync_buffer):
-        message = sync_buffer["wire_message"]
-        sync_buffer["synced_message"] = self._send(message)
-        sync_buffer["sycned_message_size"] = len(message)
+        self._sparse_message(sync_buffer, *self._inputs(sync_buffer))
 
     def uncompress(self, sync_buffer, neighbor_hat_params, local_index):
-        K = int(sync_buffer["sycned_message_size"] / 2)
         a, b = _coeffs(local_index)
-        for rank, hat_params in neighbor_hat_params.items():
-            dev = hat_params.buffer.device
-            guard = self._guards.get(dev)
-            if guard is None:
-                guard = self._guards[dev] = codec.IndexGuard(dev)
-            msg = recover_device(sync_buffer["synced_message"][rank], device=dev)
-            codec.sparse_extrapolate(msg[:K].view(torch.float32), msg[K:], hat_params.buffer, a, b, guard=guard)
-        for guard in self._guards.values():  # bad indices of an earlier step, after this step's work
-            guard.check_then_arm()
+        for _, hat, (values, indices) in self._sparse_received(sync_buffer, self._replicas(neighbor_hat_params)):
+            codec.sparse_extrapolate(values, indices, hat, a, b, guard=self._guards[hat.device])
+        self._guards.sweep()
 
 
-class ECDQuantizationCompressor(_ECDBase):
+class ECDQuantizationCompressor(_ECDInputs, _QsgdConsumer):
     """QSGD  (ecd_psgd.py:306-423)."""
 
     def compress(self, sync_buffer):
-        x, lay = self._x(sync_buffer)
-        self._qsgd_message(sync_buffer, x, None, lay)
-
-    def sync(self, sync_buffer):
-        sync_buffer["synced_message"] = self._send(sync_buffer["flatten_updates"].buffer)
+        self._qsgd_message(sync_buffer, *self._inputs(sync_buffer))
 
     def uncompress(self, sync_buffer, neighbor_hat_params, local_index):
         q = int(self.quantize_level)
         a, b = _coeffs(local_index)
-        for rank, hat_params in neighbor_hat_params.items():
-            dev = hat_params.buffer.device
-            lay = self._layout(sync_buffer, dev)
-            msg = recover_device(sync_buffer["synced_message"][rank], device=dev)
+        for _, hat, msg in self._qsgd_received(sync_buffer, self._replicas(neighbor_hat_params)):
             if q == 32:
-                hat_params.buffer.mul_(a).add_(msg.view(torch.float32), alpha=b)
+                hat.mul_(a).add_(msg, alpha=b)
                 continue
-            packed, norms = self._qsgd_part(msg, lay)
-            codec.qsgd_extrapolate(packed, norms, lay.n, q, hat_params.buffer, a, b, is_biased=self.is_biased,
+            lay = self._layout(sync_buffer, hat.device)
+            codec.qsgd_extrapolate(msg[0], msg[1], lay.n, q, hat, a, b, is_biased=self.is_biased,
                                    seg_off=lay.seg_off, nseg=lay.nseg)
 
 
-class ECDSignCompressor(_ECDBase):
-    """sign + per-tensor L1 norm  (ecd_psgd.py:426-455); one [norms | words] message,
-    `synced_flatten_norms` / `synced_signs` are views of it."""
+class ECDSignCompressor(_ECDInputs, _SignConsumer):
+    """sign + per-tensor L1 norm  (ecd_psgd.py:426-455)."""
+
+    placeholder_key = "flatten_updates"
 
     def compress(self, sync_buffer):
-        x, lay = self._x(sync_buffer)
-        signs, norms = self._sign_message(sync_buffer, x, None, lay)
-        sync_buffer["flatten_norms"] = TensorBuffer.from_flat(norms, [() for _ in range(lay.nseg)])
-        sync_buffer["flatten_updates"] = None
-
-    def sync(self, sync_buffer):
-        norms = sync_buffer["flatten_norms"].buffer
-        synced = self._send(self._sign_wire(sync_buffer))
-        sync_buffer["synced_message"] = synced
-        sync_buffer["synced_flatten_norms"], sync_buffer["synced_signs"] = self._sign_parts(synced, norms.numel())
+        self._sign_message(sync_buffer, *self._inputs(sync_buffer))
 
     def uncompress(self, sync_buffer, neighbor_hat_params, local_index):
         a, b = _coeffs(local_index)
-        for rank, hat_params in neighbor_hat_params.items():
-            dev = hat_params.buffer.device
-            lay = self._layout(sync_buffer, dev)
-            nm = recover_device(sync_buffer["synced_flatten_norms"][rank], device=dev).contiguous()
-            sg = recover_device(sync_buffer["synced_signs"][rank], device=dev)
-            codec.sign_extrapolate(sg, nm, lay.n, hat_params.buffer, a, b, seg_off=lay.seg_off, nseg=lay.nseg)
+        for _, hat, (words, norms) in self._sign_received(sync_buffer, self._replicas(neighbor_hat_params)):
+            lay = self._layout(sync_buffer, hat.device)
+            codec.sign_extrapolate(words, norms, lay.n, hat, a, b, seg_off=lay.seg_off, nseg=lay.nseg)
+
+
+class ECDCompressor(_Facade):
+    sparsification, quantization, sign = ECDSparsificationCompressor, ECDQuantizationCompressor, ECDSignCompressor
+

@@ -20,10 +20,8 @@ tensors.  `step_loop(...)` is the same step as one torch op per line (CPU tensor
 import torch
 
 from . import codec, utils
-from .communication import recover_device
-from .parallel_choco import _Layout, _hdr_words
-from .sparsification import get_n_bits
 from .tensor_buffer import TensorBuffer
+from .wire import _Layout, _SignSender, _received, _staged
 
 
 def step_loop(compressor, param_groups, param_names, state, memory_tb):
@@ -70,7 +68,9 @@ def fused_step(compressor, param_groups, param_names, state, memory_tb):
     return sync_buffer["n_bits"]
 
 
-class EFSignCompressor(object):
+class EFSignCompressor(_SignSender):
+    norms_key = "grad_norms_tb"
+
     def __init__(self, rank, world_size, aggregator, comm_op, comm_device, use_ipc, **kargs):
         self.rank = rank
         self.world_size = world_size
@@ -90,43 +90,33 @@ class EFSignCompressor(object):
         ef_sign_sgd.py:104-106), written in the pass that decodes the copy."""
         g = grads_tb.buffer
         lay = self._layout(grads_tb)
-        message, (signs, norms) = codec.sign_wire(lay.n, lay.nseg, g.device)  # written in place by the kernels
-        codec.sign_compress(g, seg_off=lay.seg_off, nseg=lay.nseg, want_norms=True, out=(signs, norms))
+        sync_buffer = {"grads_tb": grads_tb}
+        _, norms = self._sign_message(sync_buffer, g, None, lay)
         if residual:
             local = torch.empty_like(g)
             codec.sign_local_residual(g, norms, seg_off=lay.seg_off, nseg=lay.nseg, local_out=local, resid_out=g)
         else:
             local = codec.sign_local_decode(g, norms, seg_off=lay.seg_off, nseg=lay.nseg)
-        return {"grad_norms_tb": TensorBuffer.from_flat(norms, [() for _ in range(lay.nseg)]),
-                "grads_tb": grads_tb,
-                "synced_grads_tb": TensorBuffer.from_flat(local, grads_tb._tensors_sizes),
-                "signs": signs, "sign_message": message, "sign_size": torch.Size([lay.n]),
-                "n_bits": get_n_bits(norms) + get_n_bits(signs)}
+        sync_buffer["synced_grads_tb"] = TensorBuffer.from_flat(local, grads_tb._tensors_sizes)
+        return sync_buffer
 
     def sync(self, sync_buffer):
-        norms = sync_buffer["grad_norms_tb"].buffer
-        hw = _hdr_words(norms.numel())
-        message = sync_buffer["sign_message"]  # [norms | signs]: written in place by compress
-        if self.comm_device == "cpu":
-            message = message.cpu().pin_memory()
-        synced = self.aggregator_fn._agg(message, communication_scheme="all_gather", async_op=False)
-        nseg = norms.numel()
+        # [norms | signs]: written in place by compress
+        synced = self.aggregator_fn._agg(_staged(sync_buffer["sign_message"], self.comm_device),
+                                         communication_scheme="all_gather", async_op=False)
+        # the all-gather's list in rank order, where the neighbour exchanges give a dict
+        parts = [codec.sign_split(m, len(sync_buffer["grad_norms_tb"])) for m in synced]
         sync_buffer["synced_message"] = synced
-        sync_buffer["synced_grad_norms"] = [m[:hw].view(torch.float32)[:nseg] for m in synced]
-        sync_buffer["synced_signs"] = [m[hw:] for m in synced]
+        sync_buffer["synced_grad_norms"] = [norms for _, norms in parts]
+        sync_buffer["synced_signs"] = [words for words, _ in parts]
 
     def decompress(self, sync_buffer, divide=True):
         """divide=False: the sum is left undivided (the caller's params_ef(EF_DIV) divides it)."""
         tb = sync_buffer["synced_grads_tb"]
         dev = tb.buffer.device
         lay = self._layout(tb)
-        parts = []
-        for rank in range(self.world_size):
-            if rank == self.rank:
-                continue
-            nm = recover_device(sync_buffer["synced_grad_norms"][rank], device=dev).contiguous()
-            sg = recover_device(sync_buffer["synced_signs"][rank], device=dev)
-            parts.append((sg, nm))
+        others = ((rank, tb.buffer) for rank in range(self.world_size) if rank != self.rank)
+        parts = [msg for _, _, msg in _received(sync_buffer["synced_message"], others, codec.sign_split, lay.nseg)]
         if parts:
             # synced_grad_s.add_(norm_s * sign_s / numel_s)  (ef_sign_sgd.py:212-215), ranks in order
             codec.sign_axpy(parts, [1.0] * len(parts), lay.n, tb.buffer, seg_off=lay.seg_off, nseg=lay.nseg)

@@ -33,95 +33,21 @@ import torch
 
 from . import codec
 from .communication import recover_device
-from .sparsification import get_n_bits, _draw_seed
-from .tensor_buffer import TensorBuffer
+from .sparsification import _draw_seed
+from .wire import _Compressor, _Facade, _Guards, _LazyDict, _hdr_words, _received, _staged
 
 
-def _seg_lens(original_shapes):
-    return tuple(int(s[1]) for s in original_shapes)
-
-
-class _Layout:
-    """Device-side segment table + top-k plans for one parameter layout."""
-
-    _cache = {}
-
-    def __init__(self, lens, device):
-        self.lens = lens
-        self.nseg = len(lens)
-        offs = [0]
-        for s in lens:
-            offs.append(offs[-1] + s)
-        self.n = offs[-1]
-        self.seg_off_list = offs
-        self.seg_off = torch.tensor(offs, dtype=torch.int64, device=device) if self.nseg > 1 else None
-        self.device = device
-        self._plans = {}
-
-    @classmethod
-    def get(cls, lens, device):
-        key = (lens, str(device))
-        lay = cls._cache.get(key)
-        if lay is None:
-            lay = cls(lens, device)
-            cls._cache[key] = lay
-        return lay
-
-    def topk_plan(self, ratio):
-        p = self._plans.get(ratio)
-        if p is None:
-            p = codec.SegmentPlan(self.lens, ratio, self.device)
-            self._plans[ratio] = p
-        return p
-
-
-_hdr_words = codec.wire_header_words  # int32 words of the fp32 norms header (16-byte aligned)
-
-
-class CHOCOCompressor(object):
-    def __init__(self, **kargs):
-        if "top_k" in kargs["comm_op"] or "random_k" in kargs["comm_op"]:
-            self.compressor_fn = CHOCOSparsificationCompressor(**kargs)
-        elif "quantize" in kargs["comm_op"]:
-            self.compressor_fn = CHOCOQuantizationCompressor(**kargs)
-        elif "sign" in kargs["comm_op"]:
-            self.compressor_fn = CHOCOSignCompressor(**kargs)
-        else:
-            raise NotImplementedError
-
-    def pipeline(self, *args, **kargs):
-        return self.compressor_fn.pipeline(*args, **kargs)
-
-    def compress(self, *args, **kargs):
-        return self.compressor_fn.compress(*args, **kargs)
-
-    def sync(self, *args, **kargs):
-        return self.compressor_fn.sync(*args, **kargs)
-
-    def uncompress(self, *args, **kargs):
-        return self.compressor_fn.uncompress(*args, **kargs)
-
-    def flush_receive(self):
-        return self.compressor_fn.flush_receive()
-
-
-class _CHOCOBase(object):
-    def __init__(self, aggregator, comm_op, comm_device, compress_ratio, quantize_level, is_biased, backend,
-                 use_ipc, **kargs):
-        self.aggregator_fn = aggregator
-        self.comm_op = comm_op
-        self.comm_device = comm_device
-        self.compress_ratio = compress_ratio
-        self.quantize_level = quantize_level
-        self.is_biased = is_biased
-        self.backend = backend
-        self.use_ipc = use_ipc
-        self.kargs = kargs
+class _CHOCOBase(_Compressor):
+    def __init__(self, *args, **kargs):
+        super().__init__(*args, **kargs)
         # the reference binds the current stream here (parallel_choco_v.py:214-218)
         self.gossip_stream = torch.cuda.current_stream()
         # deferred receive: (messages, weights, self slot, memory, x_hat_i, layout) that the
         # next compress applies in its first pass (or flush_receive() applies alone)
         self._pending = None
+
+    def _draw_seed(self):
+        return _draw_seed()  # this module's name, looked up per call: callers pin per-worker seeds through it
 
     def pipeline(self, sync_buffer, neighbor_hat_params, neighbors_info):
         with torch.cuda.stream(self.gossip_stream):
@@ -136,7 +62,7 @@ class _CHOCOBase(object):
     def _flat_inputs(self, sync_buffer):
         x = sync_buffer["flatten_params"].buffer
         xh = sync_buffer["flatten_hat_params"].buffer
-        lay = _Layout.get(_seg_lens(sync_buffer["original_shapes"]), x.device)
+        lay = self._layout(sync_buffer, x.device)
         if lay.n != x.numel():
             raise RuntimeError("original_shapes do not match flatten_params")
         return x, xh, lay
@@ -147,11 +73,22 @@ class _CHOCOBase(object):
         return None if g is None else (g[0], float(g[1]))
 
     def _send(self, sync_buffer, message, out=None):
-        if self.comm_device == "cpu":
-            message = message.cpu().pin_memory()
+        message = _staged(message, self.comm_device)
         if out is None:
             return self.aggregator_fn._agg(message, op="get_raw_sync_data", force_wait=False)
         return self.aggregator_fn._agg(message, op="get_raw_sync_data", force_wait=False, out=out)
+
+    def _receive_plan(self, sync_buffer, neighbor_hat_params, neighbors_info):
+        """The neighbour ranks in `neighbors_info` order and, as _apply / _defer take them after
+        the messages: their weights, the slot of this rank's own message (-1: none), memory,
+        x_hat_i and the layout."""
+        memory = neighbor_hat_params["memory"].buffer
+        lay = self._layout(sync_buffer, memory.device)
+        ranks = list(neighbors_info.keys())
+        weights = [neighbors_info[r] for r in ranks]
+        self_slot = self._self_slot(ranks, neighbor_hat_params)
+        xhat_self = neighbor_hat_params[ranks[self_slot]].buffer if self_slot >= 0 else None
+        return ranks, (weights, self_slot, memory, xhat_self, lay)
 
     # deferred receive ---------------------------------------------------------
     def _defer(self, parts, weights, self_slot, memory, xhat_self, lay):
@@ -176,11 +113,11 @@ class _CHOCOBase(object):
         self.flush_receive()
 
     def _take_pending(self, x, xh, g, lay):
-        """The pending receive if this compress can apply it in its first pass (the
-        consensus step fused, x_hat_i itself -- not a copy -- as flatten_hat_params);
-        otherwise it is applied on its own first (flush_receive; the fused consensus step
-        then reads the updated x_hat / memory), and None.  Raises when the consensus step
-        is not fused into this compress (_require_fused_consensus)."""
+        """The message builders' `pending` hook: the pending receive if this compress can apply
+        it in its first pass (the consensus step fused, x_hat_i itself -- not a copy -- as
+        flatten_hat_params); otherwise it is applied on its own first (flush_receive; the fused
+        consensus step then reads the updated x_hat / memory), and None.  Raises when the
+        consensus step is not fused into this compress (_require_fused_consensus)."""
         pend = self._pending
         if pend is None:
             return None
@@ -212,39 +149,16 @@ class _CHOCOBase(object):
 
 
 class CHOCOSparsificationCompressor(_CHOCOBase):
-    """top-k / random-k  (parallel_choco_v.py:189-332).
-
-    compress writes values and GLOBAL int32 indices straight into the wire
-    message [fp32 values | int32 indices]; `flatten_selected_indices` holds the
-    reference's LOCAL per-tensor indices (parallel_choco_v.py:248-249), derived
-    from the wire with the plan's cached segment starts."""
+    """top-k / random-k  (parallel_choco_v.py:189-332); the message and its keys are
+    wire._sparse_message's."""
 
     def __init__(self, *args, **kargs):
         super().__init__(*args, **kargs)
-        self._guards = {}
+        self._guards = _Guards()
 
     def compress(self, sync_buffer):
         x, xh, lay = self._flat_inputs(sync_buffer)
-        plan = lay.topk_plan(float(self.compress_ratio))
-        K = plan.k_total
-        message = torch.empty(2 * K, dtype=torch.int32, device=x.device)
-        values, indices = message[:K].view(torch.float32), message[K:]
-        g = self._gossip(sync_buffer)
-        if "top_k" in self.comm_op:
-            codec.topk_segmented(x, plan, xhat=xh, out=(values, indices), gossip=g)
-        elif "random_k" in self.comm_op:
-            # the reference never forwards is_biased to get_random_k (sparsification.py:60)
-            codec.randk_segmented(x, plan, _draw_seed(), is_biased=True, xhat=xh, out=(values, indices), gossip=g)
-        else:
-            raise NotImplementedError
-        selected_shapes = list(plan.k_per_seg)
-        local = torch.sub(indices, plan.selected_base())
-        sync_buffer["selected_shapes"] = selected_shapes
-        sync_buffer["flatten_selected_values"] = TensorBuffer.from_flat(values, [(k,) for k in selected_shapes])
-        sync_buffer["flatten_selected_indices"] = TensorBuffer.from_flat(local, [(k,) for k in selected_shapes])
-        sync_buffer["wire_message"] = message
-        # nominal bits as in parallel_choco_v.py:252-254 (32-bit values + 32-bit indices)
-        sync_buffer["n_bits"] = get_n_bits(values) + get_n_bits(local)
+        self._sparse_message(sync_buffer, x, xh, lay, gossip=self._gossip(sync_buffer))
 
     def sync(self, sync_buffer):
         message = sync_buffer["wire_message"]
@@ -253,16 +167,12 @@ class CHOCOSparsificationCompressor(_CHOCOBase):
         sync_buffer["synced_message"] = synced
         sync_buffer["sycned_message_size"] = len(message)
 
-    def _guard(self, device):
-        g = self._guards.get(device)
-        if g is None:
-            g = self._guards[device] = codec.IndexGuard(device)
-        return g
-
     def uncompress(self, sync_buffer, neighbor_hat_params, neighbors_info):
-        K = int(sync_buffer["sycned_message_size"] / 2)
-        memory = neighbor_hat_params["memory"]
-        guard = self._guard(memory.buffer.device)
+        # Not the consumers' receive loop: x_hat's scatter is queued before the wait in the
+        # middle, and one call then takes every message (no _receive_plan either: x_hat's slot
+        # depends on that early scatter).
+        memory = neighbor_hat_params["memory"].buffer
+        guard = self._guards[memory.device]
         # x_hat takes only the local message (hat_params.buffer += q_values,
         # parallel_choco_v.py:307-308): with remote messages pending, its scatter is
         # queued BEFORE waiting for them, so it runs while the exchange is in flight.
@@ -270,25 +180,22 @@ class CHOCOSparsificationCompressor(_CHOCOBase):
         local = [r for r in neighbors_info if r in neighbor_hat_params]
         hat_early = len(local) == 1 and len(neighbors_info) > 1
         if hat_early:
-            hat = neighbor_hat_params[local[0]].buffer
-            msg = sync_buffer["wire_message"]
-            codec.sparse_accumulate(msg[:K].view(torch.float32), msg[K:], hat, 1.0, guard=guard)
+            values, indices = codec.sparse_split(sync_buffer["wire_message"], sync_buffer["sycned_message_size"])
+            codec.sparse_accumulate(values, indices, neighbor_hat_params[local[0]].buffer, 1.0, guard=guard)
         self.aggregator_fn.complete_wait(sync_buffer["sync_reqs"])
         # every message applied by ONE call that runs the per-message kernels in neighbors_info
         # order (bit-identical to the reference's per-neighbour loop); a merged one-sweep form
         # was measured slower and removed ("Sparse accumulate")
-        msgs, weights, slot, hat = [], [], -1, None
-        for rank, weight in neighbors_info.items():
-            hat_params = neighbor_hat_params[rank if rank in neighbor_hat_params else "memory"]
-            msg = recover_device(sync_buffer["synced_message"][rank], device=hat_params.buffer.device)
+        targets = ((r, neighbor_hat_params[r if r in neighbor_hat_params else "memory"].buffer) for r in neighbors_info)
+        msgs, slot, hat = [], -1, None
+        for rank, target, msg in self._sparse_received(sync_buffer, targets):
             if rank in neighbor_hat_params and not hat_early:
-                slot, hat = len(msgs), hat_params.buffer
-            msgs.append((msg[:K].view(torch.float32), msg[K:]))
-            weights.append(weight)
-        codec.sparse_accumulate_multi(msgs, weights, memory.buffer, self_slot=slot, xhat_self=hat, guard=guard)
-        # out-of-range indices of an EARLIER step (lazy, no sync), reported once this step's
-        # messages are applied; pipeline() prints it as the reference prints its RuntimeErrors
-        guard.check_then_arm()
+                slot, hat = len(msgs), target
+            msgs.append(msg)
+        codec.sparse_accumulate_multi(msgs, list(neighbors_info.values()), memory, self_slot=slot, xhat_self=hat,
+                                      guard=guard)
+        # pipeline() prints what the sweep reports as the reference prints its RuntimeErrors
+        self._guards.sweep()
 
     def check(self, wait=True):
         """Report bad received indices now (teardown / checkpoint): raises RuntimeError."""
@@ -321,46 +228,22 @@ class CHOCOQuantizationCompressor(_CHOCOBase):
         if q != 32 and self.exchange_chunks > 1:
             return self._compress_chunked(sync_buffer, x, xh, lay, q, g)
         sync_buffer.pop("chunked", None)
-        if q == 32:  # the reference sends the raw delta (sparsification.py:118-119)
-            if g is not None:
-                codec.gossip_step(x, g[0], xh, g[1])
-            message = torch.sub(x, xh).view(torch.uint8)
-        else:
-            message, out = codec.qsgd_wire(lay.n, q, lay.nseg, x.device)  # written in place by the kernels
-            pend = self._take_pending(x, xh, g, lay)
-            if pend is not None:
-                # the previous step's receive + the consensus step + the norm pass, one kernel;
-                # then the quantize pass with those norms
-                codec.qsgd_recv_gossip_norms(pend[0], pend[1], pend[2], x, g[0], xh, g[1], q,
-                                             is_biased=self.is_biased, seg_off=lay.seg_off, nseg=lay.nseg,
-                                             out=out[1])
-                codec.qsgd_compress(x, q, is_biased=self.is_biased, xhat=xh, seg_off=lay.seg_off, nseg=lay.nseg,
-                                    norm_in=out[1], seed=_draw_seed(), out=out)
-            else:
-                codec.qsgd_compress(x, q, is_biased=self.is_biased, xhat=xh, seg_off=lay.seg_off, nseg=lay.nseg,
-                                    seed=_draw_seed(), gossip=g, out=out)
-        sync_buffer["flatten_updates"] = TensorBuffer.from_flat(message, [(message.numel(),)])
-        # nominal bits as in parallel_choco_v.py:393
-        sync_buffer["n_bits"] = get_n_bits(x) * self.quantize_level / 32
-        sync_buffer["n_bits_wire"] = 8 * message.numel()
+        self._qsgd_message(sync_buffer, x, xh, lay, gossip=g, pending=self._take_pending)
 
     def _compress_chunked(self, sync_buffer, x, xh, lay, q, g):
         message, norms, parts = codec.qsgd_chunked_wire(lay.n, q, lay.nseg, self.exchange_chunks, x.device)
         codec.qsgd_norms(x, xhat=xh, seg_off=lay.seg_off, nseg=lay.nseg, gossip=g, out=norms)
-        hb = 4 * _hdr_words(lay.nseg)
         # the norms header leaves first; every range is posted right after its quantize launch,
         # so its transfer (ordered after it on the stream) overlaps the next range's quantize
-        head = self._send(sync_buffer, message[:hb])
-        seed = _draw_seed()
+        head = self._send(sync_buffer, message[:4 * _hdr_words(lay.nseg)])
+        seed = self._draw_seed()
         posted = []
         for e0, e1, part in parts:
             codec.qsgd_quantize_range(x, q, norms, e0, e1, part, is_biased=self.is_biased, xhat=xh,
                                       seg_off=lay.seg_off, nseg=lay.nseg, seed=seed)
             posted.append(self._send(sync_buffer, part))
         sync_buffer["chunked"] = (head, [(e0, e1) for e0, e1, _ in parts], posted)
-        sync_buffer["flatten_updates"] = TensorBuffer.from_flat(message, [(message.numel(),)])
-        sync_buffer["n_bits"] = get_n_bits(x) * self.quantize_level / 32  # nominal (parallel_choco_v.py:393)
-        sync_buffer["n_bits_wire"] = 8 * message.numel()
+        self._qsgd_keys(sync_buffer, x, message)
 
     def sync(self, sync_buffer):
         if "chunked" in sync_buffer:  # posted by compress, range by range
@@ -374,19 +257,15 @@ class CHOCOQuantizationCompressor(_CHOCOBase):
 
     def _uncompress_chunked(self, sync_buffer, neighbor_hat_params, neighbors_info):
         (h_reqs, h_synced), ranges, posted = sync_buffer["chunked"]
-        memory = neighbor_hat_params["memory"]
-        dev = memory.buffer.device
-        lay = _Layout.get(_seg_lens(sync_buffer["original_shapes"]), dev)
-        ranks = list(neighbors_info.keys())
-        weights = [neighbors_info[r] for r in ranks]
-        self_slot = self._self_slot(ranks, neighbor_hat_params)
-        xhat_self = neighbor_hat_params[ranks[self_slot]].buffer if self_slot >= 0 else None
+        ranks, (weights, self_slot, memory, xhat_self, lay) = self._receive_plan(sync_buffer, neighbor_hat_params,
+                                                                                 neighbors_info)
         self.aggregator_fn.complete_wait(h_reqs)
-        norms = [recover_device(h_synced[r], device=dev).view(torch.float32)[:lay.nseg].contiguous() for r in ranks]
+        heads = _received(h_synced, ((r, memory) for r in ranks), codec.qsgd_split, lay.nseg)
+        norms = [nm for _, _, (_, nm) in heads]  # the header travels alone: no planes behind it
         for (e0, e1), (reqs, synced) in zip(ranges, posted):
             self.aggregator_fn.complete_wait(reqs)  # this range only: later ones are still in flight
-            msgs = [(recover_device(synced[r], device=dev), nm) for r, nm in zip(ranks, norms)]
-            codec.qsgd_accumulate_range(msgs, weights, self_slot, lay.n, int(self.quantize_level), memory.buffer,
+            msgs = [(recover_device(synced[r], device=memory.device), nm) for r, nm in zip(ranks, norms)]
+            codec.qsgd_accumulate_range(msgs, weights, self_slot, lay.n, int(self.quantize_level), memory,
                                         e0, e1, xhat_self=xhat_self, is_biased=self.is_biased,
                                         seg_off=lay.seg_off, nseg=lay.nseg)
 
@@ -394,34 +273,25 @@ class CHOCOQuantizationCompressor(_CHOCOBase):
         if "chunked" in sync_buffer:
             return self._uncompress_chunked(sync_buffer, neighbor_hat_params, neighbors_info)
         self.aggregator_fn.complete_wait(sync_buffer["sync_reqs"])
-        memory = neighbor_hat_params["memory"]
-        dev = memory.buffer.device
-        lay = _Layout.get(_seg_lens(sync_buffer["original_shapes"]), dev)
-        ranks = list(neighbors_info.keys())
-        weights = [neighbors_info[r] for r in ranks]
-        self_slot = self._self_slot(ranks, neighbor_hat_params)
-        xhat_self = neighbor_hat_params[ranks[self_slot]].buffer if self_slot >= 0 else None
-        q = int(self.quantize_level)
-        msgs = [recover_device(sync_buffer["synced_message"][r], device=dev) for r in ranks]
-        if q == 32:
-            for i, (m, w) in enumerate(zip(msgs, weights)):
-                v = m.view(torch.float32)
+        ranks, plan = self._receive_plan(sync_buffer, neighbor_hat_params, neighbors_info)
+        weights, self_slot, memory, xhat_self, _ = plan
+        msgs = [m for _, _, m in self._qsgd_received(sync_buffer, ((r, memory) for r in ranks))]
+        if int(self.quantize_level) == 32:
+            for i, (v, w) in enumerate(zip(msgs, weights)):
                 if i == self_slot:
                     xhat_self += v
-                memory.buffer += w * v
+                memory += w * v
             return
-        hb = 4 * _hdr_words(lay.nseg)
-        parts = [(m[hb:], m[:hb].view(torch.float32)[:lay.nseg].contiguous()) for m in msgs]
         if sync_buffer.get("defer_receive"):  # applied by the next compress's first pass
-            return self._defer(parts, weights, self_slot, memory.buffer, xhat_self, lay)
-        self._apply(parts, weights, self_slot, memory.buffer, xhat_self, lay)
+            return self._defer(msgs, *plan)
+        self._apply(msgs, *plan)
 
     def _apply(self, parts, weights, self_slot, memory, xhat_self, lay):
         codec.qsgd_accumulate(parts, weights, self_slot, lay.n, int(self.quantize_level), memory,
                               xhat_self=xhat_self, is_biased=self.is_biased, seg_off=lay.seg_off, nseg=lay.nseg)
 
 
-class _Reassembled(dict):
+class _Reassembled(_LazyDict):
     """{rank: [norms | words] message} of a chunked sign exchange over an aggregator without
     `out=`: each neighbour's message is concatenated from its received ranges on first
     access, i.e. after uncompress has waited for every request."""
@@ -441,14 +311,8 @@ class _Reassembled(dict):
             dict.__setitem__(self, r, v)
         return v
 
-    def items(self):
-        return [(r, self[r]) for r in self.keys()]
 
-    def values(self):
-        return [self[r] for r in self.keys()]
-
-
-class _LazyMap(dict):
+class _LazyMap(_LazyDict):
     """{rank: fn(src[rank])}, evaluated on access."""
 
     def __init__(self, src, fn):
@@ -457,12 +321,6 @@ class _LazyMap(dict):
 
     def __getitem__(self, r):
         return self._fn(self._src[r])
-
-    def items(self):
-        return [(r, self[r]) for r in self.keys()]
-
-    def values(self):
-        return [self[r] for r in self.keys()]
 
 
 class CHOCOSignCompressor(_CHOCOBase):
@@ -476,33 +334,23 @@ class CHOCOSignCompressor(_CHOCOBase):
     (include/choco_codec.h "Chunked sign pack").  Neighbours receive straight into one
     message per rank, so the wire, `synced_message` and the decode are those of C = 1."""
 
+    placeholder_key = "flatten_directions"
+
     def __init__(self, *args, **kargs):
         super().__init__(*args, **kargs)
         self.exchange_chunks = int(self.kargs.get("exchange_chunks", 1))
 
     def compress(self, sync_buffer):
         x, xh, lay = self._flat_inputs(sync_buffer)
-        message, (signs, norms) = codec.sign_wire(lay.n, lay.nseg, x.device)  # written in place by the kernels
         g = self._gossip(sync_buffer)
         sync_buffer.pop("chunked", None)
-        if self.exchange_chunks > 1:
-            self._flush_before_pass(g)  # (never deferred on this path)
-            sync_buffer["chunked"] = self._pack_and_post(sync_buffer, x, xh, lay, g, message, signs, norms)
-        else:
-            pend = self._take_pending(x, xh, g, lay)
-            if pend is not None:  # the previous step's receive + the consensus step + the pack, one pass
-                codec.sign_recv_gossip_compress(pend[0], pend[1], pend[2], x, g[0], xh, g[1], seg_off=lay.seg_off,
-                                                nseg=lay.nseg, out=(signs, norms))
-            else:
-                codec.sign_compress(x, xhat=xh, seg_off=lay.seg_off, nseg=lay.nseg, want_norms=True, gossip=g,
-                                    out=(signs, norms))
-        sync_buffer["sign_message"] = message
-        sync_buffer["flatten_norms"] = TensorBuffer.from_flat(norms, [() for _ in range(lay.nseg)])
-        sync_buffer["flatten_directions"] = None  # the delta is never materialised (fused)
-        sync_buffer["signs"] = signs
-        sync_buffer["sign_size"] = torch.Size([lay.n])
-        # nominal bits as in parallel_choco_v.py:492
-        sync_buffer["n_bits"] = get_n_bits(norms) + get_n_bits(signs)
+        if self.exchange_chunks == 1:
+            self._sign_message(sync_buffer, x, xh, lay, gossip=g, pending=self._take_pending)
+            return
+        message, (signs, norms) = codec.sign_wire(lay.n, lay.nseg, x.device)  # written in place by the kernels
+        self._flush_before_pass(g)  # (never deferred on this path)
+        sync_buffer["chunked"] = self._pack_and_post(sync_buffer, x, xh, lay, g, message, signs, norms)
+        self._sign_keys(sync_buffer, message, signs, norms, lay)
 
     def _agg_takes_out(self):
         """Whether the aggregator's _agg accepts `out=` (this package's DecentralizedAggregation
@@ -524,6 +372,8 @@ class CHOCOSignCompressor(_CHOCOBase):
             raise
 
     def _pack_and_post_ranges(self, sync_buffer, x, xh, lay, g, message, signs, norms):
+        # the ranges are the unit that travels here: a range of the message's words
+        # (codec.sign_chunks counts from the end of the header), and the header, sent last
         hw = _hdr_words(lay.nseg)
         ranges = codec.sign_chunks(lay.n, self.exchange_chunks)
         if not self._agg_takes_out():
@@ -554,44 +404,40 @@ class CHOCOSignCompressor(_CHOCOBase):
         return reqs + r, recv
 
     def sync(self, sync_buffer):
-        norms = sync_buffer["flatten_norms"].buffer
-        hw = _hdr_words(norms.numel())
         if "chunked" in sync_buffer:  # posted by compress, range by range
             reqs, synced = sync_buffer["chunked"]
         else:
             reqs, synced = self._send(sync_buffer, sync_buffer["sign_message"])  # [norms | signs]
         sync_buffer["sync_reqs_1"] = reqs
         sync_buffer["sync_reqs_2"] = []
-        sync_buffer["synced_message"] = synced
-        # the reference's two received dicts (parallel_choco_v.py:521-522), as views of
-        # the one message per rank: [fp32 norms (16-B padded) | int32 words]
-        nseg = norms.numel()
         if isinstance(synced, _Reassembled):  # assembled after uncompress's wait, not now
-            sync_buffer["synced_flatten_norms"] = _LazyMap(synced, lambda m: m[:hw].view(torch.float32)[:nseg])
-            sync_buffer["synced_signs"] = _LazyMap(synced, lambda m: m[hw:])
+            nseg = sync_buffer["flatten_norms"].buffer.numel()
+            sync_buffer["synced_message"] = synced
+            sync_buffer["synced_flatten_norms"] = _LazyMap(synced, lambda m: codec.sign_split(m, nseg)[1])
+            sync_buffer["synced_signs"] = _LazyMap(synced, lambda m: codec.sign_split(m, nseg)[0])
         else:
-            sync_buffer["synced_flatten_norms"] = {r: m[:hw].view(torch.float32)[:nseg] for r, m in synced.items()}
-            sync_buffer["synced_signs"] = {r: m[hw:] for r, m in synced.items()}
+            self._sign_synced(sync_buffer, synced)
 
     def uncompress(self, sync_buffer, neighbor_hat_params, neighbors_info):
         self.aggregator_fn.complete_wait(sync_buffer["sync_reqs_1"])
         self.aggregator_fn.complete_wait(sync_buffer["sync_reqs_2"])
-        memory = neighbor_hat_params["memory"]
-        dev = memory.buffer.device
-        lay = _Layout.get(_seg_lens(sync_buffer["original_shapes"]), dev)
-        ranks = list(neighbors_info.keys())
-        weights = [neighbors_info[r] for r in ranks]
-        self_slot = self._self_slot(ranks, neighbor_hat_params)
-        xhat_self = neighbor_hat_params[ranks[self_slot]].buffer if self_slot >= 0 else None
-        parts = []
-        for r in ranks:
-            nm = recover_device(sync_buffer["synced_flatten_norms"][r], device=dev).contiguous()
-            sg = recover_device(sync_buffer["synced_signs"][r], device=dev)
-            parts.append((sg, nm))
+        ranks, plan = self._receive_plan(sync_buffer, neighbor_hat_params, neighbors_info)
+        memory = plan[2]
+        parts = [m for _, _, m in self._sign_received(sync_buffer, ((r, memory) for r in ranks))]
         if sync_buffer.get("defer_receive") and "chunked" not in sync_buffer:  # the next compress applies them
-            return self._defer(parts, weights, self_slot, memory.buffer, xhat_self, lay)
-        self._apply(parts, weights, self_slot, memory.buffer, xhat_self, lay)
+            return self._defer(parts, *plan)
+        self._apply(parts, *plan)
 
     def _apply(self, parts, weights, self_slot, memory, xhat_self, lay):
         codec.sign_accumulate(parts, weights, self_slot, lay.n, memory, xhat_self=xhat_self, seg_off=lay.seg_off,
                               nseg=lay.nseg)
+
+
+class CHOCOCompressor(_Facade):
+    sparsification, quantization, sign = CHOCOSparsificationCompressor, CHOCOQuantizationCompressor, CHOCOSignCompressor
+
+    def pipeline(self, *args, **kargs):
+        return self.compressor_fn.pipeline(*args, **kargs)
+
+    def flush_receive(self):
+        return self.compressor_fn.flush_receive()

@@ -34,7 +34,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import param_sgd_probe as P  # noqa: E402
 from chocosgd_amd import codec, deep_squeeze, ef_sign  # noqa: E402
-from chocosgd_amd.parallel_choco import _Layout  # noqa: E402
+from chocosgd_amd.wire import _Layout  # noqa: E402
 from chocosgd_amd.tensor_buffer import TensorBuffer  # noqa: E402
 
 DEV = P.DEV
