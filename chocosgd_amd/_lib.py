@@ -150,6 +150,9 @@ SIGNATURES = {
                                         _vp, _c_i64, _c_i32, _vp, _vp]),
     "choco_params_sgd_master_gclip": (_c_i32, [_pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64, _p_i32,
                                                _c_i32, _vp, _c_i64, _c_i32, _vp, _vp]),
+    "choco_params_unpack_sr": (_c_i32, [_pp, _p_i64, _p_i32, _c_i32, _vp, _c_i64, _c_u64, _c_u64, _vp]),
+    "choco_params_sgd_sr": (_c_i32, [_pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64, _p_i32, _c_i32,
+                                     _vp, _c_i64, _c_i32, _vp, _c_u64, _c_u64, _vp]),
     "choco_params_gradnorm_scaled": (_c_i32, [_pp, _p_i64, _p_i32, _p_i32, _c_i32, _c_i64, _c_f64, _c_i32, _vp, _vp,
                                               _c_f64, _c_f64, _c_i32, _c_i32, _vp, _vp, _vp, _c_sz, _vp]),
     "choco_params_sgd_scaled": (_c_i32, [_pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64, _p_i32, _c_i32,

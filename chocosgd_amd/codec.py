@@ -1066,11 +1066,25 @@ def params_pack(tensors, flat):
                "choco_params_pack")
 
 
-def params_unpack(flat, tensors):
+def _sr_words(sr):
+    """sr = (seed, step) as the two uint64 arguments."""
+    seed, step = sr
+    return int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF
+
+
+def params_unpack(flat, tensors, sr=None):
     """tensors[s][...] = flat[off_s : off_s + len_s] narrowed to the tensor's dtype (round to
     nearest even, as torch's converting copy), one batched launch per chunk
-    (TensorBuffer.unpack, tensor_buffer.py:38-40)."""
+    (TensorBuffer.unpack, tensor_buffer.py:38-40).
+
+    sr = (seed, step): choco_params_unpack_sr -- a bf16 tensor receives the stochastic rounding
+    of its flat values with the bits of (seed, step, flat index) (rounding.sr_bits /
+    sr_narrow_bf16 restate it), an fp32 tensor the copy; an fp16 tensor raises."""
     ptrs, lens, dts, nseg = _param_tables(tensors, flat)
+    if sr is not None:
+        _lib.check(lib().choco_params_unpack_sr(ptrs, lens, dts, nseg, _ptr(flat), flat.numel(), *_sr_words(sr),
+                                                _stream(flat.device)), "choco_params_unpack_sr")
+        return
     _lib.check(lib().choco_params_unpack(ptrs, lens, dts, nseg, _ptr(flat), flat.numel(), _stream(flat.device)),
                "choco_params_unpack")
 
@@ -1291,7 +1305,7 @@ class ParamSgdPlan:
                                         *tail, _stream(self.device)), name)
 
     def run(self, flat=None, grad_mode=False, write=True, norms=None, clip_threshold=None, add_flat=False,
-            gclip=None, write_clipped=False, scaled=None):
+            gclip=None, write_clipped=False, scaled=None, sr=None):
         """One choco_params_sgd over the tables as they stand.  apply mode (grad_mode False):
         write -> the params are updated; grad mode: write -> d_p goes into the grads' storage.
         flat (fp32, n elements, or None) receives the new params / d_p in the same pass.
@@ -1310,7 +1324,13 @@ class ParamSgdPlan:
         choco_params_sgd_scaled -- every gradient is multiplied by its second element (the clip
         coefficient over the loss scale), and where its third says the gradients held an inf or
         a NaN the step is skipped on the device: flat receives the unchanged params and nothing
-        else is written.  write_clipped stores the unscaled, clipped gradient."""
+        else is written.  write_clipped stores the unscaled, clipped gradient.
+
+        sr = (seed, step) (apply mode; bf16 and fp32 tensors; with or without gclip /
+        write_clipped): choco_params_sgd_sr -- the parameter line stays fp32, flat receives
+        p_new unrounded and a bf16 parameter, where written, its stochastic rounding with the
+        bits of (seed, step, flat index).  Not with grad_mode, norms / clip_threshold /
+        add_flat or scaled."""
         if flat is not None:
             _require(flat, torch.float32, "flat")
             if flat.device != self.device or flat.numel() != self.n:
@@ -1318,6 +1338,19 @@ class ParamSgdPlan:
         mode = (SGD_MODE_GRAD | (SGD_MODE_WRITE_GRADS if write else 0)) if grad_mode else \
             (SGD_MODE_WRITE_PARAMS if write else 0)
         clipped = SGD_MODE_WRITE_CLIPPED if write_clipped else 0
+        if sr is not None:
+            if scaled is not None:
+                raise RuntimeError("sr (stochastic rounding) has no loss-scaled form: bf16 needs no loss scale, "
+                                   "and fp16 models use LossScaler with MasterWeights")
+            if norms is not None or clip_threshold is not None:
+                raise RuntimeError("sr (stochastic rounding) does not combine with norms / clip_threshold (DGC's "
+                                   "per-tensor clipping)")
+            if gclip is None and write_clipped:
+                raise RuntimeError("write_clipped needs gclip (gradnorm()'s tensor)")
+            # grad mode and add_flat are refused by the entry point, with its own messages
+            mode |= SGD_MODE_ADD_FLAT if add_flat else 0
+            return self._sgd("_sr", _ptr(flat), self.n, mode | clipped,
+                             None if gclip is None else self._coef_ptr(gclip), *_sr_words(sr))
         if scaled is not None:
             out = self._scaled_ptr(scaled, gclip is not None or norms is not None or clip_threshold is not None
                                    or add_flat or grad_mode)

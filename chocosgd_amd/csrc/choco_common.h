@@ -381,6 +381,18 @@ CHOCO_DEV __host__ uint64_t qrng_key(uint64_t seed, uint64_t offset) {
 }
 CHOCO_DEV float u24(uint32_t b24) { return (float)b24 * 5.9604644775390625e-08f; }
 
+// The stochastic-rounding bit stream of (seed, step) (include/choco_codec.h; param_common.h
+// bf16_narrow_sr takes the bits): key = qrng_key(seed, step); the four flat elements
+// 4 q .. 4 q + 3 share the word mix(key + (q + 1) * gamma), element i taking its bits
+// [16 (i & 3), 16 (i & 3) + 16).  A pure function of (seed, step, i): whichever path stores
+// element i draws the same bits.
+CHOCO_DEV __host__ uint64_t sr_word(uint64_t key, int64_t i) {
+  return splitmix64_mix(key + (((uint64_t)i >> 2) + 1) * kGoldenGamma);
+}
+CHOCO_DEV __host__ uint32_t sr_bits16(uint64_t w, int64_t i) {
+  return (uint32_t)(w >> (16 * ((int)i & 3))) & 0xffffu;
+}
+
 // The uniforms themselves come from xoroshiro128+ (Blackman & Vigna 2018, the
 // a=24 b=16 c=37 parameters) run for 8 steps per 16-element STREAM, its state
 // seeded by SplitMix64 as its authors prescribe: stream `sid` starts at

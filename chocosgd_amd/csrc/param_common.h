@@ -3,8 +3,9 @@
 // gradient norms beside them; ef.hip: the error-feedback lines; mix.hip: the neighbour-weighted
 // model mix; consensus.hip: the averaged model and the distance to it; mask.hip: DGC's masking,
 // which walks the slot space the same way).
-//   device  the tile geometry, the SGD table's flag bits, the 16-bit conversions, the 16-byte
-//           non-temporal store, the element / group moves; the tile walk and its search
+//   device  the tile geometry, the SGD table's flag bits, the 16-bit conversions (the stochastic
+//           bf16 rounding among them), the 16-byte non-temporal store, the element / group moves
+//           and their stochastically rounded stores; the tile walk and its search
 //           (tile_walk), the dtype switch (for_dtype), the 16-byte congruence rule (mis16,
 //           on_grid16) and the one-group-in-flight span walk (span_walk)
 //   host    the layout's argument check (layout_check), the chunk loop with the table's offsets
@@ -40,6 +41,21 @@ CHOCO_DEV unsigned short bf16_narrow(float f) {
   const uint32_t u = __float_as_uint(f);
   if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)0x7fc0u;
   return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+// Stochastic rounding of v to bf16 with the 16 random bits r16 (< 65536): the add carries into
+// the kept half with probability low16 / 65536.
+//   * a value already representable in bf16 (low16 == 0) is unchanged for every r16
+//   * the result is always the truncation or its successor in magnitude (the sign bit is not
+//     touched: bf16 is sign-magnitude)
+//   * P(successor) = low16 / 65536, also across a binade boundary, where the carry runs from
+//     the mantissa into the exponent and lands on the next binade's first value
+//   * +-0 and subnormals need no special case: the bit pattern is monotone in the magnitude
+//   * a finite value above the largest finite bf16 may round to inf, as rounding up past it does
+// inf and NaN go through bf16_narrow (inf kept, quiet NaN): the add would walk off them.
+CHOCO_DEV unsigned short bf16_narrow_sr(float v, uint32_t r16) {
+  const uint32_t u = __float_as_uint(v);
+  if ((u & 0x7fffffffu) >= 0x7f800000u) return bf16_narrow(v);
+  return (unsigned short)((u + r16) >> 16);
 }
 CHOCO_DEV float f16_widen(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
 // v_cvt_f16_f32: round-to-nearest-even, overflow -> inf, subnormal results kept
@@ -124,6 +140,20 @@ CHOCO_DEV void st8(void* base, int64_t j, const float (&v)[8]) {
     for (int k = 0; k < 8; ++k) o[k] = narrow16<DT>(v[k]);
     __builtin_nontemporal_store(o, reinterpret_cast<choco_u16x8*>(reinterpret_cast<unsigned short*>(base) + j));
   }
+}
+
+// The stochastically rounded stores of a bf16 tensor (choco_common.h sr_word): element j of the
+// tensor is flat element i; a whole group starts at a flat index e that is a multiple of 8 and
+// costs two mixes, a single element one.
+CHOCO_DEV void st1_sr(void* base, int64_t j, float v, uint64_t key, int64_t i) {
+  reinterpret_cast<unsigned short*>(base)[j] = bf16_narrow_sr(v, sr_bits16(sr_word(key, i), i));
+}
+CHOCO_DEV void st8_sr(void* base, int64_t j, const float (&v)[8], uint64_t key, int64_t e) {
+  const uint64_t w0 = sr_word(key, e), w1 = sr_word(key, e + 4);
+  choco_u16x8 o;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) o[k] = bf16_narrow_sr(v[k], sr_bits16(k < 4 ? w0 : w1, k));
+  __builtin_nontemporal_store(o, reinterpret_cast<choco_u16x8*>(reinterpret_cast<unsigned short*>(base) + j));
 }
 
 // ---------------------------------------------------------------- the dtype switch

@@ -8,6 +8,8 @@
 //              (TensorBuffer.unpack, dl_code/pcode/utils/tensor_buffer.py:38-40: the
 //              converting copy narrows round-to-nearest-even; +-0, +-inf and NaN are
 //              kept, fp16 overflow gives inf, fp16 subnormals are produced)
+//   * unpack, stochastically rounded ("param_unpack_sr_kernel"): a bf16 tensor receives
+//              bf16_narrow_sr(flat[i], the 16 bits of flat element i), an fp32 tensor the copy
 // in the manner of torch's multi_tensor_apply: the table of a chunk of tensors (device
 // pointers, int64 flat offsets, one dtype code each) travels in the kernel arguments, so
 // there is no device-side table, no allocation and no synchronisation.
@@ -37,12 +39,21 @@ struct ParamTable {
   uint8_t dt[kParamCap];       // CHOCO_DT_*
   int32_t nt;
 };
-// the table, the flat pointer and two words: a launch carries at most 4 KB of arguments
-static_assert(sizeof(ParamTable) + 24 <= 4096, "ParamTable must fit in the kernel arguments");
+// the table, the flat pointer and three words: a launch carries at most 4 KB of arguments
+static_assert(sizeof(ParamTable) + 32 <= 4096, "ParamTable must fit in the kernel arguments");
 
 // What the copy does to one widened value of a tensor of dtype DT on its way across: nothing
 // (pack, unpack: widening and the store's round-to-nearest-even narrowing are the moves' own) ...
 struct CopyOp {
+  static constexpr bool kSr = false;
+  template <int DT>
+  CHOCO_DEV float apply(float v) const { return v; }
+};
+// ... nothing either, but the store into a bf16 tensor rounds stochastically with the bits of the
+// element's flat index (param_common.h st1_sr / st8_sr): compiled into param_unpack_sr_kernel alone
+struct SrOp {
+  static constexpr bool kSr = true;
+  uint64_t key;
   template <int DT>
   CHOCO_DEV float apply(float v) const { return v; }
 };
@@ -57,7 +68,11 @@ template <int SDT, int DDT, int DT, typename OP>
 CHOCO_DEV void param_span(const void* src, int64_t so, void* dst, int64_t d_o, const OP& op, int64_t a, int64_t b,
                           bool vec) {
   const int tid = threadIdx.x;
-  const auto elem = [&](int64_t i) { st1<DDT>(dst, i - d_o, op.template apply<DT>(ld1<SDT>(src, i - so))); };
+  constexpr bool kSr = OP::kSr && DDT == CHOCO_DT_BF16;
+  const auto elem = [&](int64_t i) {
+    if constexpr (kSr) st1_sr(dst, i - d_o, op.template apply<DT>(ld1<SDT>(src, i - so)), op.key, i);
+    else st1<DDT>(dst, i - d_o, op.template apply<DT>(ld1<SDT>(src, i - so)));
+  };
   if (!vec) {
     for (int64_t i = a + tid; i < b; i += kPbThreads) elem(i);
     return;
@@ -80,7 +95,8 @@ CHOCO_DEV void param_span(const void* src, int64_t so, void* dst, int64_t d_o, c
         widen8<SDT>(r[u], v);
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = op.template apply<DT>(v[k]);
-        st8<DDT>(dst, e - d_o, v);
+        if constexpr (kSr) st8_sr(dst, e - d_o, v, op.key, e);
+        else st8<DDT>(dst, e - d_o, v);
       } else {
         // a group cut by the tensor's start or end (or past the span): its own elements only
         const int64_t ea = e > a ? e : a, eb = e + kPbGroup < b ? e + kPbGroup : b;
@@ -115,6 +131,11 @@ __global__ __launch_bounds__(kPbThreads) void param_unpack_kernel(const ParamTab
   param_tile<false>(tb, flat, tile0, flat16, CopyOp{});
 }
 
+__global__ __launch_bounds__(kPbThreads) void param_unpack_sr_kernel(const ParamTable tb, float* flat, int64_t tile0,
+                                                                     int flat16, uint64_t key) {
+  param_tile<false>(tb, flat, tile0, flat16, SrOp{key});
+}
+
 // ------------------------------------------------------------------ the scaled pack
 // choco_params_pack_scaled ("param_pack_scaled_kernel"): the pack of the all-reduce SGD step with
 // the global-norm clip coefficient and 1 / loss scale on the load it does anyway,
@@ -133,6 +154,7 @@ CHOCO_DEV float pack_scaled1(float c, float g) {
 // ... or that product
 template <bool RND>
 struct ScaleOp {
+  static constexpr bool kSr = false;
   float c;
   template <int DT>
   CHOCO_DEV float apply(float v) const { return pack_scaled1<DT, RND>(c, v); }
@@ -148,8 +170,9 @@ __global__ __launch_bounds__(kPbThreads) void param_pack_scaled_kernel(const Par
 }
 
 // Every argument is checked before the first launch, with no HIP call.
+// sr: the stochastically rounded unpack, which has no fp16 form.
 static int params_check(const void* const* ptrs, const int64_t* lens, const int32_t* dtypes, int32_t nseg,
-                        const float* flat, int64_t n) {
+                        const float* flat, int64_t n, bool sr = false) {
   CHOCO_REQUIRE(ptrs && lens && dtypes, "null table argument");
   return layout_check(
       lens, dtypes, nseg, n,
@@ -159,6 +182,8 @@ static int params_check(const void* const* ptrs, const int64_t* lens, const int3
         return CHOCO_OK;
       },
       [&](int32_t s, uintptr_t esz) -> int {
+        CHOCO_REQUIRE(!(sr && dtypes[s] == CHOCO_DT_F16),
+                      "tensor %d: fp16 has no stochastic rounding (bf16 and fp32 tensors only)", (int)s);
         CHOCO_REQUIRE(ptrs[s] || lens[s] == 0, "tensor %d: null pointer", (int)s);
         CHOCO_REQUIRE(elem_aligned(ptrs[s], esz), "tensor %d: pointer not aligned to its element size", (int)s);
         return CHOCO_OK;
@@ -174,8 +199,9 @@ struct PackScale {
 
 template <bool PACK>
 static int params_run(const void* const* ptrs, const int64_t* lens, const int32_t* dtypes, int32_t nseg,
-                      float* flat, int64_t n, hipStream_t st, const PackScale* sc = nullptr) {
-  const int rc = params_check(ptrs, lens, dtypes, nseg, flat, n);
+                      float* flat, int64_t n, hipStream_t st, const PackScale* sc = nullptr,
+                      const uint64_t* sr_key = nullptr) {
+  const int rc = params_check(ptrs, lens, dtypes, nseg, flat, n, sr_key != nullptr);
   if (rc) return rc;
   if (sc) {
     CHOCO_REQUIRE(sc->coef && aligned4(sc->coef), "coef must be a 4-byte aligned device pointer");
@@ -200,6 +226,9 @@ static int params_run(const void* const* ptrs, const int64_t* lens, const int32_
                           sc->round ? param_pack_scaled_kernel<true> : param_pack_scaled_kernel<false>,
                           dim3((unsigned)c.tiles), dim3(kPbThreads), st, tb, flat, c.tile0, flat16, sc->coef, found, n);
     }
+    if (sr_key)
+      return CHOCO_LAUNCH("param_unpack_sr_kernel", "param_unpack_sr_kernel", param_unpack_sr_kernel,
+                          dim3((unsigned)c.tiles), dim3(kPbThreads), st, tb, flat, c.tile0, flat16, *sr_key);
     return CHOCO_LAUNCH(name, name, PACK ? param_pack_kernel : param_unpack_kernel, dim3((unsigned)c.tiles),
                         dim3(kPbThreads), st, tb, flat, c.tile0, flat16);
   });
@@ -227,4 +256,11 @@ CHOCO_API int choco_params_unpack(void* const* ptrs, const int64_t* lens, const 
                                   const float* flat, int64_t n, void* stream) {
   return params_run<false>(const_cast<const void* const*>(ptrs), lens, dtypes, nseg, const_cast<float*>(flat), n,
                            as_stream(stream));
+}
+
+CHOCO_API int choco_params_unpack_sr(void* const* ptrs, const int64_t* lens, const int32_t* dtypes, int32_t nseg,
+                                     const float* flat, int64_t n, uint64_t seed, uint64_t step, void* stream) {
+  const uint64_t key = qrng_key(seed, step);
+  return params_run<false>(const_cast<const void* const*>(ptrs), lens, dtypes, nseg, const_cast<float*>(flat), n,
+                           as_stream(stream), nullptr, &key);
 }

@@ -46,7 +46,10 @@
 //                     front of master arithmetic; WRITE_GRADS stores it, narrowed, into g).
 // param_sgd_kernel keeps a span walk and a body of its own (plain_span, plain_elem: optional
 // sides, the flat output, kSgdU groups in flight with their loads ahead of a cut group's element
-// path); on the shared walk it measured 11 to 14 % slower (see there).  A launch writes only the
+// path); on the shared walk it measured 11 to 14 % slower (see there).  Its stochastic-rounding
+// instantiations ("param_sgd_sr_kernel", choco_params_sgd_sr; apply mode, bf16 and fp32 tensors)
+// leave the parameter line in fp32 and round the one store that writes a bf16 parameter with 16
+// bits that are a function of (seed, step, flat index) alone.  A launch writes only the
 // bytes of its own elements.  g and buf of one tensor may be the same memory (the update is
 // elementwise; where both are written, d is stored last); distinct tensors must not overlap,
 // which is not checked.  The gradient norms these updates clip by: gradnorm.hip.
@@ -70,8 +73,9 @@ struct SgdTable {
   uint8_t fl[kSgdCap];       // CHOCO_SGD_F_* | kSgdHas* (param_common.h)
   int32_t nt;
 };
-// the table, the flat and norms pointers and four words: a launch carries at most 4 KB of arguments
-static_assert(sizeof(SgdTable) + 40 <= 4096 - 256, "SgdTable must fit in the kernel arguments");
+// the table, the flat and norms pointers, four words and the stochastic-rounding key: a launch
+// carries at most 4 KB of arguments
+static_assert(sizeof(SgdTable) + 48 <= 4096 - 256, "SgdTable must fit in the kernel arguments");
 
 // what one tensor's update needs (workgroup-uniform)
 struct SgdTensor {
@@ -96,6 +100,7 @@ struct SgdTensor {
   float c;                 // the tensor's clip coefficient
   bool wr_c;               // kGradCoef: the clipped gradient goes back into g (WRITE_CLIPPED)
   float gc;                // ... and the coefficient
+  uint64_t sr_key;         // param_sgd_sr_kernel: the key of the step's stochastic-rounding bits
 };
 
 CHOCO_DEV SgdTensor sgd_decode(const SgdTable& tb, int s) {
@@ -130,8 +135,10 @@ CHOCO_DEV bool sgd_congruent(const SgdTensor& t) {
 
 // rnd<DT>(v), the value as the storage dtype holds it: param_common.h
 
-// one element; out = what goes to params / grads and to flat
-template <int DT>
+// one element; out = what goes to params / grads and to flat.  SR (param_sgd_sr_kernel, apply
+// mode): the parameter line is left in fp32, p_new = fma(-lr, d, p) unrounded -- flat takes it as
+// it is and the parameter's store rounds it stochastically.
+template <int DT, bool SR = false>
 CHOCO_DEV void sgd_math(const SgdTensor& t, float p, float g, float b, float& buf_out, float& out) {
   if (t.pack_only) {
     out = p;
@@ -151,7 +158,8 @@ CHOCO_DEV void sgd_math(const SgdTensor& t, float p, float g, float b, float& bu
     buf_out = nb;
     d = t.nesterov ? rnd<DT>(fmaf(t.mom, nb, d)) : nb;
   }
-  out = t.grad_mode ? d : rnd<DT>(fmaf(t.nlr, d, p));
+  if (SR) out = fmaf(t.nlr, d, p);
+  else out = t.grad_mode ? d : rnd<DT>(fmaf(t.nlr, d, p));
 }
 
 enum SgdGrad { kGradOwn, kGradCoef, kGradFlat };  // the gradient source
@@ -250,7 +258,9 @@ CHOCO_DEV void sgd_span(const SgdTensor& t, int64_t a, int64_t b, bool flat16) {
 
 // flat index i, element j of the tensor.  GC (the gclip kernel's instantiations): the gradient
 // is clipped as it is loaded, g = rnd(gc * g), one fp32 multiply narrowed to the tensor's dtype.
-template <int DT, bool GC = false>
+// SR (the stochastic-rounding kernel's instantiations): sgd_math leaves p_new in fp32, and a
+// bf16 parameter's store rounds it with the bits of flat index i (param_common.h st1_sr / st8_sr).
+template <int DT, bool GC = false, bool SR = false>
 CHOCO_DEV void plain_elem(const SgdTensor& t, int64_t i, int64_t j) {
   const float p = t.rd_p ? ld1<DT>(t.p, j) : 0.0f;
   float g = t.rd_g ? ld1<DT>(t.g, j) : 0.0f;
@@ -260,20 +270,23 @@ CHOCO_DEV void plain_elem(const SgdTensor& t, int64_t i, int64_t j) {
     g = rnd<DT>(__fmul_rn(t.gc, g));
     if (t.wr_c) st1<DT>(t.g, j, g);
   }
-  sgd_math<DT>(t, p, g, b, nb, out);
+  sgd_math<DT, SR>(t, p, g, b, nb, out);
   if (t.wr_b) st1<DT>(t.buf, j, nb);
-  if (t.wr_p) st1<DT>(t.p, j, out);
+  if (t.wr_p) {
+    if constexpr (SR && DT == CHOCO_DT_BF16) st1_sr(t.p, j, out, t.sr_key, i);
+    else st1<DT>(t.p, j, out);
+  }
   if (t.wr_g) st1<DT>(t.g, j, out);
   if (t.flat) t.flat[i] = t.add_flat ? t.flat[i] + out : out;
 }
 
 // Flat elements [a, b) of a tensor at flat offset o0, a < b inside this workgroup's tile.
 // vec: every side the update touches is 16-byte aligned at every whole group's start.
-template <int DT, bool GC = false>
+template <int DT, bool GC = false, bool SR = false>
 CHOCO_DEV void plain_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, bool vec) {
   const int tid = threadIdx.x;
   if (!vec) {
-    for (int64_t i = a + tid; i < b; i += kPbThreads) plain_elem<DT, GC>(t, i, i - o0);
+    for (int64_t i = a + tid; i < b; i += kPbThreads) plain_elem<DT, GC, SR>(t, i, i - o0);
     return;
   }
   const int64_t g0 = a >> 3, g1 = (b - 1) >> 3;  // groups at absolute flat offsets, inclusive
@@ -307,9 +320,12 @@ CHOCO_DEV void plain_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, 
           if (t.wr_c) st8<DT>(t.g, e - o0, g);
         }
 #pragma unroll
-        for (int k = 0; k < 8; ++k) sgd_math<DT>(t, p[k], g[k], bi[k], nb[k], out[k]);
+        for (int k = 0; k < 8; ++k) sgd_math<DT, SR>(t, p[k], g[k], bi[k], nb[k], out[k]);
         if (t.wr_b) st8<DT>(t.buf, e - o0, nb);
-        if (t.wr_p) st8<DT>(t.p, e - o0, out);
+        if (t.wr_p) {
+          if constexpr (SR && DT == CHOCO_DT_BF16) st8_sr(t.p, e - o0, out, t.sr_key, e);
+          else st8<DT>(t.p, e - o0, out);
+        }
         if (t.wr_g) st8<DT>(t.g, e - o0, out);
         if (t.add_flat) {
           float f[8];
@@ -321,16 +337,26 @@ CHOCO_DEV void plain_span(const SgdTensor& t, int64_t o0, int64_t a, int64_t b, 
       } else {
         // a group cut by the tensor's start or end (or past the span): its own elements only
         const int64_t ea = e > a ? e : a, eb = e + kPbGroup < b ? e + kPbGroup : b;
-        for (int64_t i = ea; i < eb; ++i) plain_elem<DT, GC>(t, i, i - o0);
+        for (int64_t i = ea; i < eb; ++i) plain_elem<DT, GC, SR>(t, i, i - o0);
       }
     }
   }
 }
 
-template <bool EXT, bool GC = false, bool SC = false>
+// KEY: no argument at all (the argument lists above), or one SrKey ("param_sgd_sr_kernel",
+// choco_params_sgd_sr; with GC where it is given a clip coefficient): the key of the step's
+// stochastic-rounding bits.  The host has refused grad mode, ADD_FLAT and fp16 tensors.
+struct SrKey {
+  uint64_t key;
+};
+
+template <bool EXT, bool GC = false, bool SC = false, typename... KEY>
 __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb, float* flat, int64_t tile0,
                                                                int32_t flat16, int32_t mode, const float* norms,
-                                                               float thr) {
+                                                               float thr, KEY... sr) {
+  constexpr bool SR = sizeof...(KEY) != 0;
+  uint64_t sr_key = 0;
+  ((sr_key = sr.key), ...);
   const bool grad_mode = (mode & CHOCO_SGD_MODE_GRAD) != 0;
   const float gc = GC ? norms[SC ? 1 : 0] : 1.0f;  // a uniform load
   const bool found = SC && norms[2] != 0.0f;       // ... and another
@@ -356,8 +382,9 @@ __global__ __launch_bounds__(kPbThreads) void param_sgd_kernel(const SgdTable tb
     t.wr_g = !t.pack_only && grad_mode && (mode & CHOCO_SGD_MODE_WRITE_GRADS) != 0;
     t.wr_c = GC && !t.pack_only && (mode & CHOCO_SGD_MODE_WRITE_CLIPPED) != 0;  // apply mode (the host's check)
     t.gc = gc;
+    t.sr_key = sr_key;
     const bool vec = (flat == nullptr || flat16) && sgd_congruent<false>(t);
-    for_dtype(t.dt, [&](auto DT) { plain_span<DT, GC>(t, t.o0, a, b, vec); });
+    for_dtype(t.dt, [&](auto DT) { plain_span<DT, GC, SR>(t, t.o0, a, b, vec); });
   });
 }
 
@@ -448,6 +475,8 @@ enum class SgdKind {
                    // four floats; the step is skipped on the device where out[2] != 0
   Flatgrad,        // choco_params_sgd[_master]_flatgrad: gsum and divisor
   FlatgradScaled,  // choco_params_sgd[_master]_flatgrad_scaled: gsum holds n + 1 elements, the last the flag
+  Sr,              // choco_params_sgd_sr: apply mode, the parameter's store rounded stochastically; coef (or
+                   // null) as Gclip's
 };
 
 struct SgdArgs {
@@ -474,8 +503,9 @@ struct SgdArgs {
                                  // Scaled: choco_params_gradnorm_scaled's out
   const float* gsum = nullptr;   // Flatgrad*: the all-reduced sum, n fp32
   double divisor = 0.0;          // ... and what it is divided by
+  uint64_t sr_key = 0;           // Sr: qrng_key(seed, step)
 
-  bool gclip() const { return kind == SgdKind::Gclip || kind == SgdKind::Scaled; }
+  bool gclip() const { return kind == SgdKind::Gclip || kind == SgdKind::Scaled || (kind == SgdKind::Sr && coef); }
   bool flatgrad() const { return kind == SgdKind::Flatgrad || kind == SgdKind::FlatgradScaled; }
 };
 
@@ -507,6 +537,14 @@ static int flatgrad_mode_check(const SgdArgs& a) {
 static int own_grad_mode_check(const SgdArgs& a) {
   const int32_t clipped = a.gclip() ? CHOCO_SGD_MODE_WRITE_CLIPPED : 0;
   const bool scaled = a.kind == SgdKind::Scaled;
+  if (a.kind == SgdKind::Sr) {
+    CHOCO_REQUIRE(!(a.mode & CHOCO_SGD_MODE_GRAD),
+                  "the stochastic-rounding update runs in apply mode (grad mode stores no parameter): mode bits 0x%x",
+                  (unsigned)a.mode);
+    CHOCO_REQUIRE(!(a.mode & CHOCO_SGD_MODE_ADD_FLAT),
+                  "ADD_FLAT and the per-tensor clip have no stochastic-rounding variant: mode bits 0x%x",
+                  (unsigned)a.mode);
+  }
   if (a.master) {
     CHOCO_REQUIRE((a.mode & ~(CHOCO_SGD_MODE_WRITE_PARAMS | clipped)) == 0,
                   "the master update runs in apply mode, optionally | WRITE_PARAMS%s: mode bits 0x%x",
@@ -558,6 +596,9 @@ static int sgd_check(const SgdArgs& a) {
         constexpr int32_t kFlags = CHOCO_SGD_F_NESTEROV | CHOCO_SGD_F_FIRST | CHOCO_SGD_F_NOGRAD;
         CHOCO_REQUIRE((a.flags[s] & ~kFlags) == 0, "tensor %d: unknown flag bits 0x%x", i, (unsigned)a.flags[s]);
         const bool nograd = (a.flags[s] & CHOCO_SGD_F_NOGRAD) != 0;
+        if (a.kind == SgdKind::Sr)
+          CHOCO_REQUIRE(a.dtypes[s] != CHOCO_DT_F16,
+                        "tensor %d: fp16 has no stochastic rounding (bf16 and fp32 tensors only)", i);
         if (fg) CHOCO_REQUIRE(!nograd, "tensor %d: a no-grad tensor has no slot to skip in the flat gradient", i);
         CHOCO_REQUIRE(!(nograd && grad_mode), "tensor %d: a no-grad tensor in grad mode", i);
         CHOCO_REQUIRE(elem_aligned(a.params[s], esz) && (!a.grads || elem_aligned(a.grads[s], esz)) &&
@@ -659,6 +700,14 @@ static int sgd_run(const SgdArgs& a, hipStream_t st) {
                             "param_sgd_flatgrad_scaled_kernel", tiles, st, tb, a.gsum, a.flat, tile0, div, al16, a.mode,
                             FoundSlot{a.gsum + a.n});
         break;
+      case SgdKind::Sr:  // both under one name
+        rc = a.coef ? sgd_launch<param_sgd_kernel<false, true, false, SrKey>>("param_sgd_sr_kernel", tiles, st, tb,
+                                                                             a.flat, tile0, flat16, a.mode, a.coef,
+                                                                             0.0f, SrKey{a.sr_key})
+                    : sgd_launch<param_sgd_kernel<false, false, false, SrKey>>("param_sgd_sr_kernel", tiles, st, tb,
+                                                                              a.flat, tile0, flat16, a.mode, none,
+                                                                              0.0f, SrKey{a.sr_key});
+        break;
     }
     return rc;
   });
@@ -711,6 +760,18 @@ CHOCO_API int choco_params_sgd_gclip(void* const* params, const void* const* gra
   SgdArgs a = sgd_args(SgdKind::Gclip, false, params, grads, bufs, lens, dtypes, lr, weight_decay, momentum,
                        dampening, flags, nseg, flat, n, mode);
   a.coef = coef;
+  return sgd_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_sgd_sr(void* const* params, const void* const* grads, void* const* bufs,
+                                  const int64_t* lens, const int32_t* dtypes, const double* lr,
+                                  const double* weight_decay, const double* momentum, const double* dampening,
+                                  const int32_t* flags, int32_t nseg, float* flat, int64_t n, int32_t mode,
+                                  const float* coef_or_null, uint64_t seed, uint64_t step, void* stream) {
+  SgdArgs a = sgd_args(SgdKind::Sr, false, params, grads, bufs, lens, dtypes, lr, weight_decay, momentum, dampening,
+                       flags, nseg, flat, n, mode);
+  a.coef = coef_or_null;
+  a.sr_key = qrng_key(seed, step);
   return sgd_run(a, as_stream(stream));
 }
 

@@ -58,7 +58,8 @@ def step_loop(compressor, param_groups, param_names, state, shapes, neighbor_hat
     return sync_buffer["n_bits"]
 
 
-def fused_step(compressor, param_groups, param_names, state, shapes, neighbor_hat_params, neighbors_info):
+def fused_step(compressor, param_groups, param_names, state, shapes, neighbor_hat_params, neighbors_info,
+               rounding=None):
     """DCD_PSGD.step end to end (dcd_psgd.py:96-144): the batched
     apply_gradient(apply_grad_to_model=False); ONE mix launch for :104-125, which writes the
     half params sum(hat_r * w_r) - lr * d_p and packs the params beside them (the two inputs of
@@ -66,6 +67,7 @@ def fused_step(compressor, param_groups, param_names, state, shapes, neighbor_ha
     straight from this rank's own replica (the reference clones it first).  lr is
     param_groups[0]["lr"], as in the reference.  Returns n_bits.  Tensors the kernels do not
     take run step_loop."""
+    utils.no_rounding("dcd.fused_step", rounding)  # stochastic rounding: not part of this step (DESIGN.md section 8)
     entries = utils.step_entries(param_groups, param_names, "dcd.fused_step", need_grads=True)
     plan = utils.grad_step_plan(entries, state, neighbor_hat_params)
     if plan is None:

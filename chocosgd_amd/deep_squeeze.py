@@ -48,7 +48,7 @@ def step_loop(compressor, param_groups, param_names, state, shapes, memory, neig
     return sync_buffer["n_bits"]
 
 
-def fused_step(compressor, param_groups, param_names, state, shapes, memory, neighbors_info):
+def fused_step(compressor, param_groups, param_names, state, shapes, memory, neighbors_info, rounding=None):
     """DeepSqueeze.step end to end (deep_squeeze.py:94-127): the batched
     apply_gradient(apply_grad_to_model=True) writes the params; ONE params_ef launch (per chunk)
     adds them onto memory.buffer (:101-108, no flat copy of the params); the compressor builds
@@ -57,6 +57,7 @@ def fused_step(compressor, param_groups, param_names, state, shapes, memory, nei
     adds the aggregate onto the params (:125-126).  No pack, no unpack.  memory.buffer is
     updated in place, where the reference rebinds it.  Returns n_bits.  Tensors the kernels do
     not take run step_loop."""
+    utils.no_rounding("deep_squeeze.fused_step", rounding)  # stochastic rounding: not part of this step (DESIGN.md section 8)
     entries = utils.step_entries(param_groups, param_names, "deep_squeeze.fused_step")
     mem = memory.buffer
     plan = utils._sgd_fill(entries, state, True, mem) if mem.is_cuda else None

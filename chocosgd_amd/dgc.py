@@ -264,13 +264,14 @@ def apply_gradient(param_groups, state, clip_grad=False, clip_grad_val=None, n_n
 
 
 def fused_step(codec_, param_groups, param_names, state, memory_tb, compress_ratio, clip_grad=False,
-               clip_grad_val=None, mask_momentum=False):
+               clip_grad_val=None, mask_momentum=False, rounding=None):
     """DGC.step (dgc.py:118-151) end to end with a DGCCodec: the norms, the clipped update adding
     d_p into the error-feedback memory in the same pass, compress, the momentum-factor masking
     fused with the memory clear, sync, recover_info and the unpack into the model.  Returns
     n_bits.  Every group must hold one parameter, named in order in param_names, as the
     reference's groups do.  A quantize op keeps its memory (dgc.py:183-185) and takes the
     unfused compress."""
+    utils.no_rounding("dgc.fused_step", rounding)  # stochastic rounding: not part of this step (DESIGN.md section 8)
     if len(param_names) != len(param_groups) or any(len(g["params"]) != 1 for g in param_groups) \
             or [idx for idx, _ in param_names] != list(range(len(param_groups))):
         raise RuntimeError("dgc.fused_step needs one parameter per group, named in order in param_names")

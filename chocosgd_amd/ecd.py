@@ -47,7 +47,8 @@ def step_loop(compressor, param_groups, param_names, state, shapes, neighbor_hat
     return _finish(compressor, sync_buffer, neighbor_hat_params, local_index)
 
 
-def fused_step(compressor, param_groups, param_names, state, shapes, neighbor_hat_params, neighbors_info, local_index):
+def fused_step(compressor, param_groups, param_names, state, shapes, neighbor_hat_params, neighbors_info, local_index,
+               rounding=None):
     """ECD_PSGD.step end to end (ecd_psgd.py:99-157): the batched
     apply_gradient(apply_grad_to_model=False); ONE mix launch for :107-140, which writes the
     updated model sum(hat_r * w_r) + (-lr) * d_p (fused, as add_(alpha=)) into the params and
@@ -55,6 +56,7 @@ def fused_step(compressor, param_groups, param_names, state, shapes, neighbor_ha
     the buffer the compressor takes; this module's compress / sync / uncompress.  lr is
     param_groups[0]["lr"], as in the reference.  Returns n_bits.  Tensors the kernels do not
     take run step_loop."""
+    utils.no_rounding("ecd.fused_step", rounding)  # stochastic rounding: not part of this step (DESIGN.md section 8)
     entries = utils.step_entries(param_groups, param_names, "ecd.fused_step", need_grads=True)
     plan = utils.grad_step_plan(entries, state, neighbor_hat_params)
     if plan is None:

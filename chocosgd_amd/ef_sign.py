@@ -42,7 +42,7 @@ def step_loop(compressor, param_groups, param_names, state, memory_tb):
     return sync_buffer["n_bits"]
 
 
-def fused_step(compressor, param_groups, param_names, state, memory_tb):
+def fused_step(compressor, param_groups, param_names, state, memory_tb, rounding=None):
     """EF_SignSGD.step end to end (ef_sign_sgd.py:78-123): the batched
     apply_gradient(apply_grad_to_model=False) writes d_p into the grads and adds it onto
     memory_tb.buffer in the same pass (:79-93; the buffer now holds d_p + memory, no flat copy
@@ -54,6 +54,7 @@ def fused_step(compressor, param_groups, param_names, state, memory_tb):
     memory_tb.buffer is updated in place, where the reference rebinds it.  lr is
     param_groups[0]["lr"], as in the reference.  Returns n_bits.  Tensors the kernels do not take
     run step_loop."""
+    utils.no_rounding("ef_sign.fused_step", rounding)  # stochastic rounding: not part of this step (DESIGN.md section 8)
     entries = utils.step_entries(param_groups, param_names, "ef_sign.fused_step", need_grads=True)
     mem = memory_tb.buffer
     plan = utils._sgd_fill(entries, state, False, mem) if mem.is_cuda else None

@@ -13,6 +13,7 @@ params_unpack) in place of one copy per tensor, with the same bits.
 import torch
 
 from . import codec
+from .rounding import sr_bits, sr_narrow_bf16, sr_pair
 
 
 def _batched(tensors, buffer):
@@ -81,12 +82,26 @@ class TensorBuffer:
     def nelement(self):
         return self.buffer.nelement()
 
-    def unpack(self, tensors):
+    def unpack(self, tensors, rounding=None):
+        """rounding (a rounding.StochasticRounding, which advances by one step, or a
+        (seed, step) pair): bf16 tensors receive the stochastic rounding of their fp32 slice
+        with the bits of (seed, step, flat index), fp32 tensors the copy; anything else raises.
+        None: round to nearest, as before."""
         tensors = list(tensors)
+        if rounding is not None:  # refused before the stream advances
+            if self.buffer.dtype != torch.float32:
+                raise RuntimeError("unpack(rounding=...) needs a float32 flat buffer")
+            for i, t in enumerate(tensors):
+                if t.dtype not in (torch.bfloat16, torch.float32):
+                    raise RuntimeError(f"unpack(rounding=...): tensor {i} is {t.dtype}; stochastic rounding takes "
+                                       "bfloat16 (and passes float32 through)")
+        sr = sr_pair(rounding)
         if (len(tensors) == self._tensors_len and self._end_idx[-1:] == [self.buffer.nelement()]
                 and _batched(tensors, self.buffer)
                 and all(t.size() == s for t, s in zip(tensors, self._tensors_sizes))):
-            codec.params_unpack(self.buffer, tensors)
+            codec.params_unpack(self.buffer, tensors, sr=sr)
             return
-        for tensor, entry in zip(tensors, self):
+        for i, (tensor, entry) in enumerate(zip(tensors, self)):
+            if sr is not None and tensor.dtype == torch.bfloat16:
+                entry = sr_narrow_bf16(entry, sr_bits(sr[0], sr[1], self._start_idx[i], entry.numel()))
             tensor.data[:] = entry

@@ -3,6 +3,7 @@ CHOCO half)."""
 import torch
 
 from . import codec
+from .rounding import StochasticRounding, sr_bits, sr_narrow_bf16, sr_pair  # noqa: F401  (re-exported)
 from .sparsification import get_n_bits
 from .tensor_buffer import TensorBuffer, flatten
 
@@ -309,22 +310,23 @@ def _sgd_master(param_groups, state, master, write, clip=None, ls=None):
     return plan
 
 
-def _sgd_batched(entries, state, apply_grad_to_model, flat, write, clip=None, ls=None):
+def _sgd_batched(entries, state, apply_grad_to_model, flat, write, clip=None, ls=None, sr=None):
     """One batched launch (per chunk) for `entries`, a list of (group, param) in flat order.
     Returns False, with nothing changed, where a tensor cannot take it.  clip, a (clip_norm,
     write_clipped, total_norm) tuple: the norm pass in front and the clipped update.  ls, a
     (scaler, clip_norm or None, write_clipped) tuple: the loss-scaled step; a first step that
-    overflowed launches the pack of the unchanged params alone."""
+    overflowed launches the pack of the unchanged params alone.  sr, a (seed, step) pair (apply
+    mode, not with ls): the stochastic-rounding kernel, which refuses fp16 tensors."""
     plan = _sgd_fill(entries, state, apply_grad_to_model, flat)
     if plan is None:
         return False
     if ls is not None:
         _run_scaled(plan, [p for _, p in entries], flat, write, ls)
     elif clip is None:
-        plan.run(flat, grad_mode=not apply_grad_to_model, write=write)
+        plan.run(flat, grad_mode=not apply_grad_to_model, write=write, sr=sr)
     else:
         plan.run(flat, grad_mode=not apply_grad_to_model, write=write,
-                 gclip=plan.gradnorm(clip[0], total_norm=clip[2]), write_clipped=clip[1])
+                 gclip=plan.gradnorm(clip[0], total_norm=clip[2]), write_clipped=clip[1], sr=sr)
     return True
 
 
@@ -559,8 +561,38 @@ def _clip_args(what, clip_norm, write_clipped=False, total_norm=None, apply_grad
     return float(clip_norm), bool(write_clipped), total_norm
 
 
+def _sr_args(what, rounding, param_groups, master=None, loss_scale=None, apply_grad_to_model=True):
+    """The (seed, step) pair of a step with rounding=..., or None without.  The combinations
+    stochastic rounding does not take raise before anything is changed or the stream advanced."""
+    if rounding is None:
+        return None
+    if master is not None:
+        raise RuntimeError(f"{what}: rounding= (stochastic rounding) with master= -- the master weights keep small "
+                           "updates already, and the parameters are their round-to-nearest narrowing")
+    if loss_scale is not None:
+        raise RuntimeError(f"{what}: rounding= (stochastic rounding) has no loss-scaled form: bf16 needs no loss "
+                           "scale, and fp16 models use LossScaler with MasterWeights")
+    if not apply_grad_to_model:
+        raise RuntimeError(f"{what}: rounding= (stochastic rounding) rounds the store of a parameter; "
+                           "apply_grad_to_model=False stores none")
+    for group in param_groups:
+        for p in group["params"]:
+            if p.dtype not in (torch.bfloat16, torch.float32):
+                raise RuntimeError(f"{what}: rounding= (stochastic rounding) takes bfloat16 parameters (and passes "
+                                   f"float32 ones through), found {p.dtype}")
+    return sr_pair(rounding)
+
+
+def no_rounding(what, rounding):
+    """The steps stochastic rounding does not cover raise when handed it."""
+    if rounding is not None:
+        raise RuntimeError(f"{what}: rounding= (stochastic rounding) is not supported here -- this step's parameter "
+                           "store is not the SGD update's or the unpack's; apply_gradient and the CHOCO fused_step "
+                           "take it")
+
+
 def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None, master=None, clip_norm=None,
-                   write_clipped=False, total_norm=None, loss_scale=None):
+                   write_clipped=False, total_norm=None, loss_scale=None, rounding=None):
     """optim/utils.py:13-47: weight decay, momentum with dampening, optional Nesterov, then
     p -= lr * d_p (apply_grad_to_model) or d_p left as the gradient.  Missing
     state[p]["momentum_buffer"] entries are created.  fp32 / bf16 / fp16 ROCm tensors take ONE
@@ -599,7 +631,19 @@ def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None,
     (with or without clip_norm) stores the unscaled, clipped gradient.  Nothing is read on the
     host, except while a step creates momentum buffers (the first taken step): `found` is then
     read, and an overflowed step leaves no buffer behind.  loss_scale=None is the code path
-    above, launch for launch."""
+    above, launch for launch.
+
+    rounding (a StochasticRounding, which advances by one step, or a (seed, step) pair;
+    apply_grad_to_model only, bf16 and fp32 parameters, with or without flat_out and clip_norm,
+    not with master or loss_scale): the third way to train a bf16 model.  Every line up to d_p
+    is as above; the parameter line stays fp32, flat_out receives it unrounded, and the ONE
+    store that writes a bf16 parameter rounds stochastically, with 16 bits that are a function
+    of (seed, step, flat index in group order) alone (include/choco_codec.h; sr_bits and
+    sr_narrow_bf16 restate it): an update below half a bf16 ulp survives in expectation, with
+    no extra memory and the plain update's traffic.  fp32 parameters get the same bits as
+    without.  One launch of codec ParamSgdPlan.run(sr=) per chunk; CPU tensors take
+    apply_gradient_sr_loop.  rounding=None is the code path above, launch for launch."""
+    sr = _sr_args("apply_gradient", rounding, param_groups, master, loss_scale, apply_grad_to_model)
     clip, ls = _scale_args("apply_gradient", loss_scale, clip_norm, write_clipped, total_norm, apply_grad_to_model)
     if master is not None:
         if not apply_grad_to_model:
@@ -611,8 +655,12 @@ def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None,
         return
     entries = [(group, p) for group in param_groups for p in group["params"]]
     flat = getattr(flat_out, "buffer", flat_out)
-    if _sgd_batched(entries, state, apply_grad_to_model, flat, write=True, clip=clip, ls=ls):
+    if _sgd_batched(entries, state, apply_grad_to_model, flat, write=True, clip=clip, ls=ls, sr=sr):
         return
+    if sr is not None:
+        if flat is not None and (flat.dtype != torch.float32 or flat.dim() != 1):
+            raise RuntimeError("apply_gradient(rounding=...): flat_out must be a flat float32 buffer")
+        return apply_gradient_sr_loop(param_groups, state, sr[0], sr[1], clip, flat)
     if ls is not None:
         apply_gradient_scaled_loop(param_groups, state, ls[0], None, ls[1], ls[2])
     elif clip is None:
@@ -645,7 +693,7 @@ def recover_params(param_groups, param_names, rank=None, neighbor_hat_params=Non
 
 def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_params, neighbors_info,
                consensus_stepsize, rank, defer_receive=False, state=None, master=None, clip_norm=None,
-               loss_scale=None):
+               loss_scale=None, rounding=None):
     """ParallelCHOCO_V.step after apply_gradient (parallel_choco_v.py:115-155), with the
     consensus step fused into the compressor's first pass: recover_params, then
     compress (x += gamma * (memory - x_hat_i) and d = x_new - x_hat_i in one pass), sync,
@@ -679,8 +727,19 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
 
     loss_scale (a LossScaler; needs state): apply_gradient(loss_scale=...)'s loss-scaled
     update.  A step whose gradients overflowed leaves x as it was and goes on: the consensus
-    step, the compressor and the exchange run on the unchanged x."""
+    step, the compressor and the exchange run on the unchanged x.
+
+    rounding (a StochasticRounding or a (seed, step) pair; needs state; bf16 and fp32
+    parameters; not with master or loss_scale): the step's first launch is the
+    stochastic-rounding update with the parameters not written -- the flat x receives the
+    unrounded fp32 p_new, so the consensus step and the compressor see no rounding at all --
+    and the unpack at the end is the stochastic one.  One (seed, step) serves both, and only
+    the unpack stores parameters: the whole step rounds each parameter once."""
     flatten_params = None
+    if rounding is not None and state is None:
+        raise RuntimeError("fused_step(rounding=...) rounds in the step's own apply_gradient and unpack: pass "
+                           "state=optimizer.state (without it the caller's apply_gradient has already rounded)")
+    sr = _sr_args("fused_step", rounding, param_groups, master, loss_scale)
     clip, ls = _scale_args("fused_step", loss_scale, clip_norm)
     if ls is not None and state is None:
         raise RuntimeError("fused_step(loss_scale=...) unscales in the step's own apply_gradient: pass "
@@ -696,7 +755,7 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
         _sgd_master(param_groups, state, master, write=False, clip=clip, ls=ls)
         flatten_params = master.flat
     elif state is not None:
-        flatten_params = _sgd_packed(param_groups, param_names, state, clip, ls)
+        flatten_params = _sgd_packed(param_groups, param_names, state, clip, ls, sr)
     if defer_receive:
         if flatten_params is None:
             params, flatten_params = recover_params(param_groups, param_names, get_hat_params=False)
@@ -720,18 +779,27 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
     if defer_receive:
         sync_buffer["defer_receive"] = True
     compressor.pipeline(sync_buffer, neighbor_hat_params, neighbors_info)
-    flatten_params.unpack(params)
+    if sr is None:
+        flatten_params.unpack(params)
+    else:
+        flatten_params.unpack(params, rounding=sr)
     return sync_buffer
 
 
-def _sgd_packed(param_groups, param_names, state, clip=None, ls=None):
+def _sgd_packed(param_groups, param_names, state, clip=None, ls=None, sr=None):
     """fused_step(state=...): apply_gradient and the pack of the new params in one launch.
     Returns the flat TensorBuffer, or None after the per-tensor loop has updated the params
-    (tensors the batched kernel does not take: recover_params packs them as before)."""
+    (tensors the batched kernel does not take: recover_params packs them as before).  sr, a
+    (seed, step) pair: the stochastic-rounding update; its loop too leaves the params unwritten
+    and returns the flat buffer of the unrounded p_new."""
     entries = step_entries(param_groups, param_names, "fused_step(state=...)")
     dev = entries[0][1].device
     flat = torch.empty(sum(p.numel() for _, p in entries), dtype=torch.float32, device=dev)
-    if dev.type == "cuda" and _sgd_batched(entries, state, True, flat, write=False, clip=clip, ls=ls):
+    if dev.type == "cuda" and _sgd_batched(entries, state, True, flat, write=False, clip=clip, ls=ls, sr=sr):
+        return TensorBuffer.from_flat(flat, [p.size() for _, p in entries])
+    if sr is not None:
+        groups = [group for group, _ in entries]  # flat order is param_names' order
+        apply_gradient_sr_loop(groups, state, sr[0], sr[1], clip, flat, write=False)
         return TensorBuffer.from_flat(flat, [p.size() for _, p in entries])
     if ls is not None:
         apply_gradient_scaled_loop(param_groups, state, ls[0], None, ls[1], ls[2])
@@ -802,7 +870,7 @@ def dpsgd_step_loop(param_groups, param_names, state, aggregator, clip=None, ls=
 
 
 def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, master=None, clip_norm=None,
-               loss_scale=None):
+               loss_scale=None, rounding=None):
     """The decentralized branch of SGD.step (sgd.py:94-121), plain D-PSGD: apply_gradient fused
     with the pack of the new params (one launch; the params themselves are not written yet),
     the exchange of the flat fp32 buffer (_agg(op="get_raw_sync_data")), and ONE mix launch
@@ -820,7 +888,10 @@ def dpsgd_step(param_groups, param_names, state, aggregator, neighbors_info, mas
 
     loss_scale (a LossScaler): apply_gradient(loss_scale=...)'s loss-scaled update.  A worker
     whose gradients overflowed keeps its x and still exchanges and mixes it: each worker skips
-    on its own."""
+    on its own.
+
+    rounding: not supported (the mix kernel stores the parameters); anything but None raises."""
+    no_rounding("dpsgd_step", rounding)
     clip, ls = _scale_args("dpsgd_step", loss_scale, clip_norm)
     entries = step_entries(param_groups, param_names, "dpsgd_step")
     params = [p for _, p in entries]
@@ -875,22 +946,76 @@ def _apply_averaged_loop(entries, state, grads):
     that model everywhere: an fp16 op on the device rounds the exact result once, a 16-bit op on
     the CPU rounds the product before the sum."""
     for (group, p), g in zip(entries, grads):
-        weight_decay, momentum = group["weight_decay"], group["momentum"]
-        dt = p.dtype
-        d_p = g.data
-        if weight_decay != 0:
-            d_p = d_p.float().add(p.data.float(), alpha=weight_decay).to(dt)
-        if momentum != 0:
-            param_state = state[p]
-            first = "momentum_buffer" not in param_state
-            if first:
-                param_state["momentum_buffer"] = torch.zeros_like(p.data)
-            buf = param_state["momentum_buffer"]
-            t = buf.float().mul(momentum).to(dt)                                   # buf.mul_(momentum)
-            t = t.float().add(d_p.float(), alpha=1 if first else 1 - group["dampening"]).to(dt)  # .add_(d_p, alpha=)
-            buf.copy_(t)
-            d_p = d_p.float().add(buf.float(), alpha=momentum).to(dt) if group["nesterov"] else buf
-        p.data.copy_(p.data.float().add(d_p.float(), alpha=-group["lr"]).to(dt))
+        p.data.copy_(_update_lines(group, p, g, state).to(p.dtype))
+
+
+def _update_lines(group, p, g, state):
+    """_apply_averaged_loop's lines for one tensor with gradient g, up to the parameter line,
+    which is returned in fp32, not yet narrowed: p_new = p + (-lr) * d_p.  The momentum buffer
+    is written (and created)."""
+    weight_decay, momentum = group["weight_decay"], group["momentum"]
+    dt = p.dtype
+    d_p = g.data
+    if weight_decay != 0:
+        d_p = d_p.float().add(p.data.float(), alpha=weight_decay).to(dt)
+    if momentum != 0:
+        param_state = state[p]
+        first = "momentum_buffer" not in param_state
+        if first:
+            param_state["momentum_buffer"] = torch.zeros_like(p.data)
+        buf = param_state["momentum_buffer"]
+        t = buf.float().mul(momentum).to(dt)                                   # buf.mul_(momentum)
+        t = t.float().add(d_p.float(), alpha=1 if first else 1 - group["dampening"]).to(dt)  # .add_(d_p, alpha=)
+        buf.copy_(t)
+        d_p = d_p.float().add(buf.float(), alpha=momentum).to(dt) if group["nesterov"] else buf
+    return p.data.float().add(d_p.float(), alpha=-group["lr"])
+
+
+def apply_gradient_sr_loop(param_groups, state, seed, step, clip=None, flat=None, write=True):
+    """apply_gradient(rounding=...) as one torch op per line and tensor: the path CPU tensors
+    keep, and what the kernel is compared against.  Every line up to d_p is _update_lines'
+    (fp32 on the widened operands, narrowed to the tensor's dtype after each line); the
+    parameter line stays fp32, `flat` (a flat fp32 tensor over every parameter in group order,
+    or None) receives it unrounded, and a bf16 parameter (write) is stored through
+    sr_narrow_bf16 with sr_bits(seed, step, its flat offset, its length) -- the flat index in
+    group order, as flat lays the parameters out.  An fp32 parameter receives p_new itself;
+    a parameter without a gradient puts its values into flat and is not written; any other
+    dtype raises.  clip, a (clip_norm, write_clipped, total_norm) tuple: global-norm clipping in
+    front, the kernel's lines -- the total (_total_norm) and the coefficient (_clip_coef32) in the
+    gradients' common dtype, then one fp32 product per element narrowed once to the gradient's
+    dtype; without write_clipped the gradients get their own values back."""
+    params = [p for group in param_groups for p in group["params"]]
+    for p in params:
+        if p.dtype not in (torch.bfloat16, torch.float32):
+            raise RuntimeError(f"stochastic rounding takes bfloat16 and float32 parameters, found {p.dtype}")
+    saved = None
+    with_grad = [p for p in params if p.grad is not None]
+    if clip is not None and with_grad:
+        clip_norm, write_clipped, total_norm = clip
+        saved = None if write_clipped else [(p, p.grad.data.clone()) for p in with_grad]
+        grads = [p.grad for p in with_grad]
+        cd = codec.common_grad_dtype(g.dtype for g in grads)
+        gc = _clip_coef32(_total_norm(grads, total_norm, cd), clip_norm).float()
+        for g in grads:
+            g.data.copy_(g.data.float() * gc.to(g.device))
+    off = 0
+    for group in param_groups:
+        for p in group["params"]:
+            n = p.numel()
+            if p.grad is None:
+                new = p.data.float()
+            else:
+                new = _update_lines(group, p, p.grad, state)
+                if write and p.dtype == torch.bfloat16:
+                    p.data.copy_(sr_narrow_bf16(new, sr_bits(seed, step, off, n)))
+                elif write:
+                    p.data.copy_(new)
+            if flat is not None:
+                flat[off:off + n] = new.reshape(-1)
+            off += n
+    if saved is not None:
+        for p, g in saved:
+            p.grad.data.copy_(g)
 
 
 def _allreduce_scaled_loop(entries, param_groups, state, aggregator, distributed, write_grads, master, clip, ls):
@@ -985,7 +1110,7 @@ def allreduce_sgd_step_loop(param_groups, param_names, state, aggregator, distri
 
 
 def allreduce_sgd_step(param_groups, param_names, state, aggregator, distributed=True, write_grads=True, master=None,
-                       clip_norm=None, total_norm=None, loss_scale=None):
+                       clip_norm=None, total_norm=None, loss_scale=None, rounding=None):
     """The centralized branch of SGD.step (sgd.py:68-92), plain all-reduce data-parallel SGD, end
     to end: ONE pack launch per chunk of the gradients into a flat fp32 buffer (16-bit
     gradients are widened, which is exact), aggregator._agg(flat, op="sum",
@@ -1028,7 +1153,11 @@ def allreduce_sgd_step(param_groups, param_names, state, aggregator, distributed
     buffers (the first taken step): the summed flag is then read after the all-reduce, and
     an overflowed step leaves no buffer behind and launches no update.
 
-    With all three None this is the code path above, launch for launch."""
+    With all three None this is the code path above, launch for launch.
+
+    rounding: not supported (the flat-gradient kernels store the parameters); anything but
+    None raises."""
+    no_rounding("allreduce_sgd_step", rounding)
     clip, ls = _scale_args("allreduce_sgd_step", loss_scale, clip_norm, False, total_norm)
     entries = _allreduce_entries(param_groups, param_names, master)
     plan = _sgd_fill(entries, state, True, None if master is None else master.buffer, master=master is not None)

@@ -860,6 +860,71 @@ int choco_params_sgd_master_gclip(void* const* params, const void* const* grads,
                                   float* master, int64_t n, int32_t mode, const float* coef,
                                   void* stream);
 
+/* ------------------------------------------- stochastic rounding for bf16 models
+ * The third way to train a bf16 model, beside the plain update (every line narrowed
+ * round-to-nearest-even: an update below half a bf16 ulp of the parameter is lost, at
+ * every step) and fp32 master weights (4 B per parameter more, twice the traffic): the ONE
+ * store that writes a bf16 parameter rounds stochastically.  The parameter takes one of its
+ * two bf16 neighbours with probabilities that make the expectation exact, so small updates
+ * survive in expectation; no extra memory, the plain update's traffic.  The reference has
+ * no counterpart.  bf16 only: an fp32 tensor of the same model passes through unchanged, an
+ * fp16 tensor is rejected (its subnormal and overflow ranges make the bit trick wrong;
+ * fp16 models use loss scaling with master weights).
+ *
+ * The rounding, with u = the bits of the fp32 value v and r16 in [0, 65536):
+ *     (u & 0x7fffffff) >= 0x7f800000 (inf, NaN):  the round-to-nearest narrowing (inf kept,
+ *                                                 quiet NaN 0x7fc0)
+ *     otherwise:                                  (u + r16) >> 16
+ *   A value already representable in bf16 is unchanged for every r16; the result is always
+ *   the truncation or its successor in magnitude; P(successor) = low16 / 65536, also across
+ *   a binade boundary; +-0 and subnormals need no special case; a finite value above the
+ *   largest finite bf16 may round to inf, as rounding up past it does.
+ *
+ * The bits.  The 16 bits of FLAT element i (its index in the layout, sum(lens[0..s)) + j)
+ * are a pure function of (seed, step, i) -- this definition is part of the ABI, and the
+ * vector path, the element path, the tile, the chunk of tensors and the tensors' alignment
+ * cannot change a result:
+ *     mix(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *              return z ^ (z >> 31)                                  (SplitMix64's output function)
+ *     key = mix(seed + (step + 1) * 0xD1B54A32D192ED03)              (the QSGD stream's key rule)
+ *     w   = mix(key + ((i >> 2) + 1) * 0x9E3779B97F4A7C15)
+ *     r16 = (w >> (16 * (i & 3))) & 0xffff
+ *   all in uint64 arithmetic modulo 2^64.  A group of 8 elements at a flat index that is a
+ *   multiple of 8 costs two mixes, a cut group's elements one each.  A caller advances
+ *   `step` once per optimizer step and keeps `seed`; the same (seed, step) must not round
+ *   the same parameter twice.  chocosgd_amd/rounding.py restates both in numpy.
+ *
+ * choco_params_unpack_sr: choco_params_unpack's tables, tiles, walk, 16-byte rule, checks
+ *   and launch count; a bf16 tensor receives the stochastic rounding of flat[i] with the
+ *   bits of i, an fp32 tensor the copy.  Rejects an fp16 tensor (the message names it) in
+ *   addition to choco_params_unpack's list.  Launches: choco_params_launches(nseg) of
+ *   "param_unpack_sr_kernel"; "param_pack_kernel" / "param_unpack_kernel" carry none of it.
+ *
+ * choco_params_sgd_sr: choco_params_sgd in apply mode.  Every line up to d is as there
+ *   (fp32 from the widened operands, narrowed round-to-nearest-even after each line), the
+ *   momentum buffer is written as there; the parameter line stays fp32,
+ *   p_new = fma(-lr, d, p), flat (if not NULL) receives p_new UNROUNDED, and the parameter
+ *   (WRITE_PARAMS) receives its stochastic rounding with the bits of its flat index (an
+ *   fp32 tensor p_new itself: the same bits as choco_params_sgd).  NOGRAD tensors put p
+ *   into flat and are not written.  coef_or_null != NULL is choco_params_sgd_gclip's form,
+ *   g = rnd_DT(*coef * g) on the load, with its WRITE_CLIPPED bit; coef is ONE float, so
+ *   there is no loss-scaled form.  With WRITE_PARAMS unset and flat given, a later
+ *   choco_params_unpack_sr of flat with the same (seed, step) stores what this call would
+ *   have: a step that ends in the unpack rounds each parameter once.
+ *   Rejects, each with its own message and in addition to choco_params_sgd's list: grad
+ *   mode; CHOCO_SGD_MODE_ADD_FLAT (the per-tensor clip's entry point has no such form);
+ *   fp16 tensors; a misaligned coef.  Launches: choco_params_sgd_launches(nseg) of
+ *   "param_sgd_sr_kernel", instantiations of their own: the kernels above carry neither the
+ *   key nor the mixes. */
+int choco_params_unpack_sr(void* const* ptrs, const int64_t* lens, const int32_t* dtypes,
+                           int32_t nseg, const float* flat, int64_t n, uint64_t seed, uint64_t step,
+                           void* stream);
+int choco_params_sgd_sr(void* const* params, const void* const* grads, void* const* bufs,
+                        const int64_t* lens, const int32_t* dtypes, const double* lr,
+                        const double* weight_decay, const double* momentum, const double* dampening,
+                        const int32_t* flags, int32_t nseg, float* flat, int64_t n, int32_t mode,
+                        const float* coef_or_null, uint64_t seed, uint64_t step, void* stream);
+
 /* ------------------------------------------- dynamic loss scaling
  * torch.amp.GradScaler's unscale_, inf/NaN check, skipped step and scale update for an fp16
  * (or bf16) model, fused into the norm pass and the update above: no pass that rewrites the

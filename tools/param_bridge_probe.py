@@ -16,6 +16,9 @@ tensors of 100 elements.  One JSON line per layout:
   kernel_us_*    dispatch-attached kernel times of the batched kernels, where the library
                  has them
 (medians over `reps` windows after a warm-up window).
+
+--sr [--runs 5], alone: the kernel time of the bf16 ResNet-50 unpack, round to nearest and
+stochastically rounded, `runs` interleaved measurements each and their range (measure_sr).
 """
 import argparse
 import json
@@ -140,15 +143,60 @@ def measure(name, lens, dtype, pairs, reps):
     return row
 
 
+def measure_sr(lens, runs, iters=20):
+    """--sr: TensorBuffer.unpack of a bf16 ResNet-50, dispatch-attached kernel time per call,
+    `runs` interleaved measurements of `iters` calls each and their range: round to nearest
+    (param_unpack_kernel) and, where the tree has it, stochastically rounded
+    (param_unpack_sr_kernel).  A tree without stochastic rounding reports the first: the parent's
+    column of an A/B visit."""
+    g = torch.Generator(device=DEV).manual_seed(0)
+    params = [torch.randn(m, generator=g, device=DEV).to(torch.bfloat16) for m in lens]
+    n = sum(lens)
+    tb = TensorBuffer.from_flat(torch.randn(n, generator=g, device=DEV), [(m,) for m in lens])
+    cases = [("plain", lambda: tb.unpack(params), "param_unpack_kernel")]
+    if hasattr(utils, "StochasticRounding"):
+        sr = utils.StochasticRounding(5)
+        cases.append(("sr", lambda: tb.unpack(params, rounding=sr), "param_unpack_sr_kernel"))
+    row = {"sr_unpack": "resnet50_bf16", "tensors": len(lens), "elements": n, "runs": runs, "iters": iters,
+           "unpack_bytes": n * 6}
+    times = {name: [] for name, _, _ in cases}
+    for _, fn, _ in cases:
+        fn()  # warm-up: code objects
+    for _ in range(runs):
+        for name, fn, kernel in cases:
+            codec.profile_reset()
+            codec.profile_filter([kernel])
+            codec.profile_enable(True)
+            for _ in range(iters):
+                fn()
+            torch.cuda.synchronize()
+            codec.profile_enable(False)
+            t, c = codec.profile_read(kernel)
+            times[name].append(round(t / iters * 1e3, 2))
+            row[f"kernel_launches_{name}"] = c // iters
+    codec.profile_filter(None)
+    codec.profile_reset()
+    for name, ts in times.items():
+        row[f"kernel_us_{name}"] = ts
+        row[f"kernel_us_{name}_range"] = [min(ts), max(ts)]
+        row[f"kernel_tbps_{name}"] = round(n * 6 / statistics.median(ts) / 1e6, 3)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--pairs", type=int, default=100)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sr", action="store_true", help="only the stochastic-rounding row (see measure_sr)")
+    ap.add_argument("--runs", type=int, default=5, help="--sr: measurements per column")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "the probe needs a ROCm device"
     rows = []
-    for name, lens, dtype in layouts():
+    if args.sr:
+        rows.append(measure_sr(layouts()[1][1], args.runs))
+        print(json.dumps(rows[-1]), flush=True)
+    for name, lens, dtype in ([] if args.sr else layouts()):
         rows.append(measure(name, lens, dtype, args.pairs, args.reps))
         print(json.dumps(rows[-1]), flush=True)
     if args.out:

@@ -47,6 +47,11 @@ loopback aggregator), both columns in the same process:
 The loss scale is 1.0 with growth switched off and the gradients are rewritten by every step
 (the averaged gradient), so the values settle; the time does not depend on them.
 
+Stochastic-rounding row (--sr [--runs 5], alone): ResNet-50 in bf16, the kernel time of the plain
+update, of the master update and of the stochastic-rounding update, `runs` measurements each and
+their range, every column on a model of its own, alone on the device (measure_sr); run from a tree without stochastic rounding it
+reports the first two, the other column of an A/B visit.
+
 Parity rows: elements of p, buf and flat on which three steps of the kernel differ from the
 same three steps of torch's own op sequence on the device, per dtype, on the fixture layout
 (tests/golden/sgd_inputs.npz) and on one tensor of 2^20 elements.
@@ -348,6 +353,55 @@ def allreduce_layouts():
             ("resnet50_bf16_master", r50, torch.bfloat16, True), ("t3000x100_fp32", [100] * 3000, torch.float32, False)]
 
 
+def measure_sr(lens, runs, iters=20):
+    """--sr: the three ways to update a bf16 ResNet-50, dispatch-attached kernel time per step,
+    `runs` measurements of `iters` steps each and their range: the plain update
+    (param_sgd_kernel, with the flat output), the master update (param_sgd_master_kernel) and,
+    where the library has it, the stochastic-rounding update (param_sgd_sr_kernel, with the flat
+    output: the plain update's traffic).  A tree without stochastic rounding reports the first
+    two: the parent's column of an A/B visit."""
+    n = sum(lens)
+    dtype = torch.bfloat16
+
+    def case(name):
+        """The step of one column and its kernel, on a model of its own."""
+        params, groups, names = model(lens, dtype)
+        state = collections.defaultdict(dict)
+        if name == "master":
+            mw = utils.MasterWeights(groups, names)
+            return (lambda: utils.apply_gradient(groups, state, master=mw)), "param_sgd_master_kernel"
+        flat = torch.empty(n, device=DEV)
+        if name == "plain":
+            return (lambda: utils.apply_gradient(groups, state, flat_out=flat)), "param_sgd_kernel"
+        sr = utils.StochasticRounding(5)
+        return (lambda: utils.apply_gradient(groups, state, flat_out=flat, rounding=sr)), "param_sgd_sr_kernel"
+
+    columns = ["plain", "master"] + (["sr"] if hasattr(utils, "StochasticRounding") else [])
+    row = {"sr_update": "resnet50_bf16", "tensors": len(lens), "elements": n, "runs": runs, "iters": iters,
+           "bytes_plain": n * 14, "bytes_master": n * 20, "bytes_sr": n * 14}
+    times = {}
+    # one column at a time, the only model on the device while it is measured: the allocator hands every
+    # tree, and every column, the same addresses (with a third model alive the master update of the same code
+    # measured 3.5 % slower)
+    for name in columns:
+        fn, kernel = case(name)
+        for _ in range(3):  # warm-up: code objects, first-step buffers
+            fn()
+        times[name] = []
+        for _ in range(runs):
+            t, launches = kernel_time(fn, kernel, iters)
+            times[name].append(round(t, 2))
+            row[f"kernel_launches_{name}"] = launches
+        del fn
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+    for name, ts in times.items():
+        row[f"kernel_us_{name}"] = ts
+        row[f"kernel_us_{name}_range"] = [min(ts), max(ts)]
+        row[f"kernel_tbps_{name}"] = round(row[f"bytes_{name}"] / statistics.median(ts) / 1e6, 3)
+    return row
+
+
 def _differ(a, b):
     a, b = a.float().reshape(-1), b.float().reshape(-1)
     same = (a.view(torch.int32) == b.view(torch.int32)) | (torch.isnan(a) & torch.isnan(b))
@@ -408,21 +462,27 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rows", choices=["all", "allreduce", "allreduce_scaled"], default="all")
+    ap.add_argument("--sr", action="store_true", help="only the stochastic-rounding row (see measure_sr)")
+    ap.add_argument("--runs", type=int, default=5, help="--sr: measurements per column")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "the probe needs a ROCm device"
     rows = []
-    for name, lens, dtype, master, scaled in (allreduce_scaled_layouts() if args.rows == "allreduce_scaled" else []):
+    kind = "sr" if args.sr else args.rows
+    if kind == "sr":
+        rows.append(measure_sr(layouts()[1][1], args.runs))
+        print(json.dumps(rows[-1]), flush=True)
+    for name, lens, dtype, master, scaled in (allreduce_scaled_layouts() if kind == "allreduce_scaled" else []):
         rows.append(measure_allreduce_scaled(name, lens, dtype, master, scaled, args.steps, args.reps))
         print(json.dumps(rows[-1]), flush=True)
-    for name, lens, dtype in (layouts() if args.rows != "allreduce_scaled" else []):
+    for name, lens, dtype in (layouts() if kind in ("all", "allreduce") else []):
         # the fp32 ResNet-50 row stays in an all-reduce run: its kernel_tbps_sgd is the yardstick
-        if args.rows == "all" or name == "resnet50_fp32":
+        if kind == "all" or name == "resnet50_fp32":
             rows.append(measure(name, lens, dtype, args.steps, args.reps))
             print(json.dumps(rows[-1]), flush=True)
-    for name, lens, dtype, master in (allreduce_layouts() if args.rows != "allreduce_scaled" else []):
+    for name, lens, dtype, master in (allreduce_layouts() if kind in ("all", "allreduce") else []):
         rows.append(measure_allreduce(name, lens, dtype, master, args.steps, args.reps))
         print(json.dumps(rows[-1]), flush=True)
-    for row in (parity_rows() if args.rows == "all" else []):
+    for row in (parity_rows() if kind == "all" else []):
         rows.append(row)
         print(json.dumps(row), flush=True)
     if args.out:
