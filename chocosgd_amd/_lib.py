@@ -179,6 +179,11 @@ SIGNATURES = {
     "choco_params_consensus_workspace_size": (_c_sz, [_c_i32, _c_i64]),
     "choco_params_consensus": (_c_i32, [_pp, _pp, _p_i64, _p_i32, _c_i32, _vp, _vp, _c_i64, _c_f64, _c_i32, _vp, _vp,
                                         _vp, _c_sz, _vp]),
+    "choco_params_adam_launches": (_c_i32, [_c_i32]),
+    "choco_params_adam": (_c_i32, [_pp, _pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64, _p_f64, _p_f64,
+                                   _p_i32, _c_i32, _vp, _c_i64, _c_i32, _vp, _vp]),
+    "choco_params_adam_master": (_c_i32, [_pp, _pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64, _p_f64,
+                                          _p_f64, _p_i32, _c_i32, _vp, _c_i64, _c_i32, _vp, _vp]),
     "choco_gossip_topk_compress": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
     "choco_gossip_topk_compress_accumulate": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i64, _vp, _vp, _c_i32,
                                                        _c_f32, _vp, _c_sz, _vp]),

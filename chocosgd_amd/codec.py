@@ -1758,6 +1758,138 @@ def _sgd_tables(params, grads, bufs, lr, weight_decay, momentum, dampening, nest
     return plan
 
 
+ADAM_F_DECOUPLED, ADAM_F_FIRST, ADAM_F_NOGRAD = 1, 2, 4                # CHOCO_ADAM_F_*
+
+
+def params_adam_launches(nseg):
+    """Launches one params_adam / params_adam_master of `nseg` tensors takes."""
+    return int(lib().choco_params_adam_launches(int(nseg)))
+
+
+class ParamAdamPlan:
+    """The host tables of choco_params_adam / choco_params_adam_master for one parameter list,
+    built once: a step rewrites only what changes -- the data pointers (`param_ptrs`,
+    `grad_ptrs`, `exp_avg_ptrs`, `exp_avg_sq_ptrs`), `flags` (ADAM_F_*), `step` (the count after
+    the increment) and the hyperparameters (`lr`, `beta1`, `beta2`, `eps`, `weight_decay`,
+    doubles; `seen[i]` is the tuple last written) -- by index, then calls run() / run_master().
+    Holds the ParamSgdPlan of the same list (`sgd`) and shares its layout, pointer and flag
+    tables: gradnorm() is that plan's, over the gradient pointers and flags as they stand (the
+    no-grad bit is the same one)."""
+
+    def __init__(self, params):
+        sgd = self.sgd = ParamSgdPlan(params)
+        nseg = self.nseg = sgd.nseg
+        self.device, self.n, self.dtypes, self.numels = sgd.device, sgd.n, sgd.dtypes, sgd.numels
+        self.param_ptrs, self.grad_ptrs, self.flags, self.lr, self.weight_decay = (
+            sgd.param_ptrs, sgd.grad_ptrs, sgd.flags, sgd.lr, sgd.weight_decay)
+        self.exp_avg_ptrs, self.exp_avg_sq_ptrs = ((ctypes.c_void_p * nseg)() for _ in range(2))
+        self.beta1, self.beta2, self.eps, self.step = ((ctypes.c_double * nseg)() for _ in range(4))
+        self.seen = [None] * nseg  # the hyperparameter tuple last written, per tensor
+        self.holds, self.fits, self.fits_master_buf, self.gradnorm = (sgd.holds, sgd.fits, sgd.fits_master_buf,
+                                                                      sgd.gradnorm)
+
+    def _adam(self, name, flat, mode, gclip, write_clipped):
+        if gclip is None and write_clipped:
+            raise RuntimeError("write_clipped needs gclip (gradnorm()'s tensor)")
+        sgd = self.sgd
+        mode |= SGD_MODE_WRITE_CLIPPED if write_clipped else 0
+        _lib.check(getattr(lib(), name)(self.param_ptrs, self.grad_ptrs, self.exp_avg_ptrs, self.exp_avg_sq_ptrs,
+                                        sgd.lens, sgd.dts, self.lr, self.beta1, self.beta2, self.eps,
+                                        self.weight_decay, self.step, self.flags, self.nseg, _ptr(flat), self.n, mode,
+                                        None if gclip is None else sgd._coef_ptr(gclip), _stream(self.device)), name)
+
+    def run(self, flat=None, write=True, gclip=None, write_clipped=False):
+        """One choco_params_adam over the tables as they stand: write -> the params are
+        updated; flat (fp32, n elements, or None) receives the new params in the same pass (a
+        tensor without a gradient is packed as it is).  gclip (gradnorm()'s tensor): every
+        gradient is scaled by the global-norm clip coefficient as it is loaded, the product
+        narrowed to the tensor's dtype; write_clipped: it is also stored into the grads'
+        storage."""
+        if flat is not None:
+            _require(flat, torch.float32, "flat")
+            if flat.device != self.device or flat.numel() != self.n:
+                raise RuntimeError(f"flat must hold {self.n} elements on {self.device}")
+        self._adam("choco_params_adam", flat, SGD_MODE_WRITE_PARAMS if write else 0, gclip, write_clipped)
+
+    def run_master(self, master, write=True, gclip=None, write_clipped=False):
+        """One choco_params_adam_master over the tables as they stand: the update runs on
+        `master` (the persistent flat fp32 copy of the parameters, n elements) in place, with
+        fp32 moments behind `exp_avg_ptrs` / `exp_avg_sq_ptrs` and the gradients in their
+        parameters' dtype; write -> the parameters receive the new master values narrowed to
+        their dtype.  gclip (gradnorm(coef_dtype=torch.float32)'s tensor): g = c * g in fp32,
+        not narrowed, in front of the update; write_clipped: that product, narrowed, is stored
+        into the grads' storage."""
+        _require(master, torch.float32, "master")
+        if master.device != self.device or master.numel() != self.n:
+            raise RuntimeError(f"master must hold {self.n} elements on {self.device}")
+        self._adam("choco_params_adam_master", master, SGD_MODE_WRITE_PARAMS if write else 0, gclip, write_clipped)
+
+
+def _adam_tables(params, grads, exp_avgs, exp_avg_sqs, lr, betas, eps, weight_decay, step, decoupled, first, plan,
+                 master):
+    """The plan of `params` with one call's pointers, flags and hyperparameters written."""
+    params = list(params)
+    nseg = len(params)
+    if plan is None:
+        plan = ParamAdamPlan(params)
+    elif not plan.holds(params):
+        raise RuntimeError("the plan was built for another parameter list")
+    if isinstance(betas, (tuple, list)) and len(betas) == 2 and not isinstance(betas[0], (list, tuple)):
+        betas = [betas] * nseg  # one (beta1, beta2) pair for every tensor
+    cols = [_per_tensor(v, nseg, nm) for v, nm in ((grads, "grads"), (exp_avgs, "exp_avgs"),
+                                                   (exp_avg_sqs, "exp_avg_sqs"), (lr, "lr"), (betas, "betas"),
+                                                   (eps, "eps"), (weight_decay, "weight_decay"), (step, "step"),
+                                                   (decoupled, "decoupled"), (first, "first"))]
+    for i, (p, g, m, v, a, (b1, b2), e, wd, k, dec, fst) in enumerate(zip(params, *cols)):
+        if g is not None and not plan.fits(i, g):
+            raise RuntimeError(f"grad {i} must match its parameter's dtype, device and size, and be contiguous")
+        for t, nm in ((m, "exp_avg"), (v, "exp_avg_sq")):
+            if t is not None and not (plan.fits_master_buf(i, t) if master else plan.fits(i, t)):
+                what = "be float32 and match its parameter's" if master else "match its parameter's dtype,"
+                raise RuntimeError(f"{nm} {i} must {what} device and size, and be contiguous")
+        plan.param_ptrs[i] = p.data_ptr()
+        plan.grad_ptrs[i] = g.data_ptr() if g is not None else None
+        plan.exp_avg_ptrs[i] = m.data_ptr() if m is not None else None
+        plan.exp_avg_sq_ptrs[i] = v.data_ptr() if v is not None else None
+        plan.flags[i] = ((ADAM_F_DECOUPLED if dec else 0) | (ADAM_F_FIRST if fst else 0)
+                         | (ADAM_F_NOGRAD if g is None else 0))
+        plan.lr[i], plan.beta1[i], plan.beta2[i], plan.eps[i], plan.weight_decay[i], plan.step[i] = a, b1, b2, e, wd, k
+        plan.seen[i] = None
+    return plan
+
+
+def params_adam(params, grads, exp_avgs, exp_avg_sqs, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1,
+                decoupled=False, first=False, flat=None, write=True, gclip=None, write_clipped=False, plan=None):
+    """torch.optim.Adam.step / AdamW.step (decoupled) over a list of tensors in one batched
+    launch per chunk (include/choco_codec.h, choco_params_adam).  grads[s] None: p.grad is None
+    (the tensor is only packed into `flat`).  exp_avgs[s] / exp_avg_sqs[s]: the moments in the
+    parameter's dtype, written, and read unless first[s].  step: the count after the increment.
+    The hyperparameters, `betas` (a (beta1, beta2) pair), `step`, `decoupled` and `first` are
+    scalars or per-tensor lists.  gclip / write_clipped: ParamAdamPlan.run's.  Returns the plan
+    (pass it back in to reuse its tables)."""
+    plan = _adam_tables(params, grads, exp_avgs, exp_avg_sqs, lr, betas, eps, weight_decay, step, decoupled, first,
+                        plan, False)
+    plan.run(flat, write, gclip, write_clipped)
+    return plan
+
+
+def params_adam_master(params, grads, exp_avgs, exp_avg_sqs, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                       step=1, decoupled=False, first=False, master=None, write=True, gclip=None, write_clipped=False,
+                       plan=None):
+    """The Adam / AdamW update on fp32 master weights (include/choco_codec.h,
+    choco_params_adam_master): params_adam's arguments, except that the update runs in place on
+    `master` -- the persistent flat fp32 copy of `params`, laid out back to back -- and the
+    moments are fp32 tensors whatever their parameter's dtype.  grads[s] None: the tensor is
+    passed over.  write: the parameters receive the new master values narrowed to their dtype.
+    Returns the plan (pass it back in to reuse its tables)."""
+    if master is None:
+        raise RuntimeError("params_adam_master needs the master buffer")
+    plan = _adam_tables(params, grads, exp_avgs, exp_avg_sqs, lr, betas, eps, weight_decay, step, decoupled, first,
+                        plan, True)
+    plan.run_master(master, write, gclip, write_clipped)
+    return plan
+
+
 def params_sqnorm_launches(nseg):
     """Launches one params_sqnorm of `nseg` tensors takes."""
     return int(lib().choco_params_sqnorm_launches(int(nseg)))

@@ -671,6 +671,276 @@ def apply_gradient(param_groups, state, apply_grad_to_model=True, flat_out=None,
         flat.copy_(flatten([p.data if apply_grad_to_model else p.grad.data for _, p in entries], dtype=flat.dtype))
 
 
+# ----------------------------------------------------------------------------- Adam / AdamW
+_ADAM_REFUSED = ("amsgrad", "maximize", "capturable", "differentiable")
+
+
+def _adam_hp(what, group):
+    """(lr, beta1, beta2, eps, weight_decay, decoupled) of a torch.optim.Adam / AdamW group;
+    raises for what the update does not take."""
+    for key in _ADAM_REFUSED:
+        if group.get(key, False):
+            raise RuntimeError(f"{what}: {key}=True is not supported (DESIGN.md section 8, the Adam update's scope)")
+    lr, (beta1, beta2) = group["lr"], group["betas"]
+    if any(torch.is_tensor(x) for x in (lr, beta1, beta2)):
+        raise RuntimeError(f"{what}: a tensor lr or beta is not supported -- the hyperparameters are host floats "
+                           "(DESIGN.md section 8, the Adam update's scope)")
+    return (float(lr), float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
+            bool(group.get("decoupled_weight_decay", False)))
+
+
+def _adam_state(what, entries, state, master):
+    """Per entry with a gradient (step tensor or None, exp_avg or None, exp_avg_sq or None) of
+    what the state holds, None for the others; raises, before anything is changed, for a state
+    the update does not take."""
+    out = []
+    for _, p in entries:
+        if p.grad is None:
+            out.append(None)
+            continue
+        st = state.get(p) or {}
+        step, m, v = st.get("step"), st.get("exp_avg"), st.get("exp_avg_sq")
+        if (m is None) != (v is None):
+            raise RuntimeError(f"{what}: a state with one of exp_avg / exp_avg_sq and not the other")
+        if step is not None and (not torch.is_tensor(step) or step.is_cuda):
+            raise RuntimeError(f"{what}: state['step'] must be a CPU tensor (torch's own, without capturable): the "
+                               "count is kept and incremented on the host")
+        if m is None and step is not None and float(step) != 0:
+            raise RuntimeError(f"{what}: a state with a step count of {float(step):g} and no moments")
+        want = torch.float32 if master is not None else p.dtype
+        for t in (m, v):
+            if t is None or t.dtype == want:
+                continue
+            if master is not None:
+                raise RuntimeError(f"{what}: a step with master weights needs float32 moments, found {t.dtype}: "
+                                   "convert optimizer.state's exp_avg / exp_avg_sq (.float()) when switching to "
+                                   "master weights")
+            raise RuntimeError(f"{what}: {t.dtype} moments beside a {p.dtype} parameter need a master copy "
+                               "(master=); without one the moments have the parameter's dtype (DESIGN.md section 8)")
+        out.append((step, m, v))
+    return out
+
+
+def _adam_begin(entries, state, held, master):
+    """The step's host side, once nothing can raise any more: missing step counts and moments
+    are created (torch.empty: the first update writes them and does not read them) and every
+    count is incremented, on the host.  Returns per entry (step after the increment, exp_avg,
+    exp_avg_sq, first) or None."""
+    out = []
+    for (_, p), h in zip(entries, held):
+        if h is None:
+            out.append(None)
+            continue
+        st = state[p]
+        step, m, v = h
+        if step is None:
+            step = st["step"] = torch.tensor(0.0, dtype=torch.float32)
+        first = m is None
+        if first:
+            dt = torch.float32 if master is not None else p.dtype
+            m = st["exp_avg"] = torch.empty_like(p.data, dtype=dt, memory_format=torch.preserve_format)
+            v = st["exp_avg_sq"] = torch.empty_like(p.data, dtype=dt, memory_format=torch.preserve_format)
+        step += 1
+        out.append((float(step), m, v, first))
+    return out
+
+
+def _adam_lines(hp, p, g, m, v, step, first):
+    """choco_params_adam's lines on one tensor, one torch op each: p (the parameter's data or
+    its master view) is updated in place, g is read, m and v are updated in place."""
+    lr, beta1, beta2, eps, wd, decoupled = hp
+    bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
+    if first:
+        m.zero_()
+        v.zero_()
+    if wd != 0:
+        if decoupled:
+            p.mul_(1 - lr * wd)
+        else:
+            g = g.add(p, alpha=wd)  # out of place: p.grad keeps its values
+    m.lerp_(g, 1 - beta1)
+    v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+    # the correctly rounded fp32 square root, narrowed to v's dtype: torch's CPU sqrt of a large fp32 tensor goes
+    # through a vector math library that is 1 ulp off on some inputs, the float64 one rounded to fp32 is not
+    den = v.double().sqrt_().float().to(v.dtype)
+    den = den.div_(bc2 ** 0.5)
+    den = den.add_(eps)
+    q = m.div(den)
+    p.add_(q, alpha=-(lr / bc1))  # q rounded, then one fused multiply-add: the kernel's line
+
+
+def apply_adam_loop(param_groups, state, master=None, clip_norm=None, write_clipped=False, total_norm=None,
+                    write=True):
+    """apply_adam as one torch op per line and tensor: the path CPU tensors, and anything the
+    batched kernel does not take, keep.  The same bits as the kernel on fp32 tensors; the
+    parameter line is q = m / den rounded and then one fused multiply-add, where torch's addcdiv_
+    rounds elsewhere, and the square root is taken in float64 and rounded to fp32 (the correctly
+    rounded one, which torch's CPU sqrt of a large fp32 tensor is not).  With master the lines run on fp32 views of the master with
+    p.grad.float(), then p.data.copy_(view) (write)."""
+    what = "apply_adam_loop"
+    if master is not None:
+        entries = master.entries(param_groups)
+    else:
+        entries = [(group, p) for group in param_groups for p in group["params"]]
+    hps = [_adam_hp(what, group) for group, _ in entries]
+    clip = _clip_args(what, clip_norm, write_clipped, total_norm)
+    held = _adam_state(what, entries, state, master)
+    rows = _adam_begin(entries, state, held, master)
+    with_grad = [p for _, p in entries if p.grad is not None]
+    grads = {}
+    if clip is not None and with_grad:
+        if master is not None:  # the coefficient in fp32, the product not narrowed
+            c = _clip_coef32(_total_norm([p.grad for p in with_grad], clip[2], torch.float32), clip[0])
+            grads = {p: p.grad.data.float() * c.to(p.grad.device) for p in with_grad}
+        else:
+            saved = None if clip[1] else [p.grad.data.clone() for p in with_grad]
+            clip_grad_norm_loop(with_grad, clip[0], clip[2])
+    for i, ((_, p), hp, row) in enumerate(zip(entries, hps, rows)):
+        if row is None:
+            continue
+        step, m, v, first = row
+        if master is None:
+            _adam_lines(hp, p.data, p.grad.data, m, v, step, first)
+            continue
+        view = master.flat[i]
+        _adam_lines(hp, view, grads[p] if p in grads else p.grad.data.float(), m, v, step, first)
+        if write:
+            p.data.copy_(view)
+    if clip is not None and with_grad:
+        if master is not None and clip[1]:
+            for p in with_grad:
+                p.grad.data.copy_(grads[p])
+        elif master is None and saved is not None:
+            for p, g in zip(with_grad, saved):
+                p.grad.data.copy_(g)
+
+
+_adam_plans = {}  # id of a list's first parameter -> its ParamAdamPlan (which holds weak references only)
+
+
+def _adam_plan(params):
+    """The cached Adam plan of this parameter list, or None where the batched kernel does not
+    take it (CPU tensors, other dtypes, non-contiguous or several devices)."""
+    plan = _adam_plans.get(id(params[0]))
+    if plan is not None and plan.holds(params):
+        return plan
+    dev = params[0].device
+    if not all(p.is_cuda and p.device == dev and p.dtype in codec.PARAM_DTYPES and p.is_contiguous()
+               for p in params):
+        return None
+    if len(_adam_plans) >= 64:  # plans of parameter lists long gone
+        _adam_plans.clear()
+    plan = _adam_plans[id(params[0])] = codec.ParamAdamPlan(params)
+    return plan
+
+
+def _adam_batched(what, entries, hps, state, flat, master, write, clip):
+    """One batched launch (per chunk) for `entries`, a list of (group, param) in flat order:
+    the plan's tables are written by index, missing state is created, the counts are
+    incremented and the kernel runs -- after the norm pass where clip, a (clip_norm,
+    write_clipped, total_norm) tuple, is given.  flat: the flat output or None; with master the
+    master's buffer.  Returns False, with nothing changed, where a tensor cannot take it."""
+    if not entries:
+        return False
+    held = _adam_state(what, entries, state, master)
+    plan = _adam_plan([p for _, p in entries])
+    if plan is None or (flat is not None and (flat.dtype != torch.float32 or flat.device != plan.device
+                                              or flat.numel() != plan.n or not flat.is_contiguous())):
+        return False
+    fits_moment = plan.fits_master_buf if master is not None else plan.fits
+    for i, ((_, p), h) in enumerate(zip(entries, held)):
+        if h is None:
+            continue
+        if not plan.fits(i, p.grad) or any(t is not None and not fits_moment(i, t) for t in h[1:]):
+            return False
+    rows = _adam_begin(entries, state, held, master)
+    pp, gp, mp, vp, flags, seen = (plan.param_ptrs, plan.grad_ptrs, plan.exp_avg_ptrs, plan.exp_avg_sq_ptrs,
+                                   plan.flags, plan.seen)
+    for i, ((_, p), hp, row) in enumerate(zip(entries, hps, rows)):
+        if row is None:
+            pp[i], gp[i], mp[i], vp[i], flags[i] = p.data_ptr(), None, None, None, codec.ADAM_F_NOGRAD
+            continue
+        step, m, v, first = row
+        pp[i], gp[i], mp[i], vp[i] = p.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr()
+        flags[i] = (codec.ADAM_F_DECOUPLED if hp[5] else 0) | (codec.ADAM_F_FIRST if first else 0)
+        plan.step[i] = step
+        if hp != seen[i]:  # an unchanged lr costs nothing
+            plan.lr[i], plan.beta1[i], plan.beta2[i], plan.eps[i], plan.weight_decay[i] = hp[:5]
+            seen[i] = hp
+    gclip = None
+    if clip is not None:
+        gclip = plan.gradnorm(clip[0], coef_dtype=torch.float32 if master is not None else None, total_norm=clip[2])
+    if master is not None:
+        plan.run_master(flat, write, gclip=gclip, write_clipped=clip is not None and clip[1])
+    else:
+        plan.run(flat, write, gclip=gclip, write_clipped=clip is not None and clip[1])
+    return True
+
+
+def apply_adam(param_groups, state, flat_out=None, master=None, clip_norm=None, write_clipped=False,
+               total_norm=None):
+    """Drop-in for torch.optim.Adam.step / AdamW.step on torch's own group keys (`lr`, `betas`,
+    `eps`, `weight_decay`, `decoupled_weight_decay`, default False) and state keys
+    (state[p]["step"], a CPU float32 0-dim tensor incremented on the host with no sync,
+    "exp_avg", "exp_avg_sq"): a torch.optim.AdamW state_dict loads into it and its state loads
+    into torch.optim.AdamW.  fp32 / bf16 / fp16 ROCm tensors take ONE batched HIP launch per
+    chunk of tensors (codec.params_adam: every operand read once); CPU tensors, and anything
+    else, apply_adam_loop.  The arithmetic is include/choco_codec.h's: torch's op sequence with
+    one rounding per line, the same bits on every path for fp32 tensors.
+
+    Missing moments are created with torch.empty, in the parameter's dtype or, with master, in
+    fp32; the first update writes them and never reads them.  `amsgrad`, `maximize`,
+    `capturable`, `differentiable`, a tensor lr or beta, and moments of another dtype than the
+    step's raise before anything is touched.
+
+    flat_out (a TensorBuffer or a flat fp32 tensor over every parameter, in group order)
+    receives the new parameters in the same pass.  master (a MasterWeights of this model; no
+    flat_out): the update runs in fp32 on the master copy, in place, with fp32 moments, and the
+    parameters receive its values narrowed to their dtype.  clip_norm / write_clipped /
+    total_norm: apply_gradient's global-norm clipping, fused into the update the same way."""
+    what = "apply_adam"
+    hps_of = {id(group): _adam_hp(what, group) for group in param_groups}
+    clip = _clip_args(what, clip_norm, write_clipped, total_norm)
+    if master is not None:
+        if flat_out is not None:
+            raise RuntimeError("apply_adam(master=...): the master buffer is the flat copy; flat_out has no use")
+        _adam_master(what, param_groups, state, master, True, clip)
+        return
+    entries = [(group, p) for group in param_groups for p in group["params"]]
+    flat = getattr(flat_out, "buffer", flat_out)
+    hps = [hps_of[id(group)] for group, _ in entries]
+    if _adam_batched(what, entries, hps, state, flat, None, True, clip):
+        return
+    apply_adam_loop(param_groups, state, None, clip_norm, write_clipped, total_norm)
+    if flat is not None:
+        flat.copy_(flatten([p.data for _, p in entries], dtype=flat.dtype))
+
+
+def _adam_master(what, param_groups, state, master, write, clip):
+    """apply_adam on the master weights: the batched launch, or the loop for tensors the kernel
+    does not take.  Raises, with nothing changed, where the master does not fit the model or a
+    moment is not fp32."""
+    entries = master.entries(param_groups)
+    hps = [_adam_hp(what, group) for group, _ in entries]
+    if not _adam_batched(what, entries, hps, state, master.buffer, master, write, clip):
+        apply_adam_loop(param_groups, state, master, *(clip or (None, False, None)), write=write)
+
+
+def _adam_packed(param_groups, param_names, state, clip):
+    """fused_step(state=..., update="adam"): apply_adam and the pack of the new params in one
+    launch.  Returns the flat TensorBuffer, or None after the per-tensor loop has updated the
+    params (tensors the batched kernel does not take: recover_params packs them as before)."""
+    what = 'fused_step(update="adam")'
+    entries = step_entries(param_groups, param_names, what)
+    hps = [_adam_hp(what, group) for group, _ in entries]
+    dev = entries[0][1].device
+    flat = torch.empty(sum(p.numel() for _, p in entries), dtype=torch.float32, device=dev)
+    if dev.type == "cuda" and _adam_batched(what, entries, hps, state, flat, None, False, clip):
+        return TensorBuffer.from_flat(flat, [p.size() for _, p in entries])
+    apply_adam_loop(param_groups, state, None, *(clip or (None, False, None)))
+    return None
+
+
 def recover_params(param_groups, param_names, rank=None, neighbor_hat_params=None, get_hat_params=True):
     """optim/utils.py:50-64: flat copies of the params (and of x_hat_i).
 
@@ -693,7 +963,7 @@ def recover_params(param_groups, param_names, rank=None, neighbor_hat_params=Non
 
 def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_params, neighbors_info,
                consensus_stepsize, rank, defer_receive=False, state=None, master=None, clip_norm=None,
-               loss_scale=None, rounding=None):
+               loss_scale=None, rounding=None, update="sgd"):
     """ParallelCHOCO_V.step after apply_gradient (parallel_choco_v.py:115-155), with the
     consensus step fused into the compressor's first pass: recover_params, then
     compress (x += gamma * (memory - x_hat_i) and d = x_new - x_hat_i in one pass), sync,
@@ -734,8 +1004,24 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
     stochastic-rounding update with the parameters not written -- the flat x receives the
     unrounded fp32 p_new, so the consensus step and the compressor see no rounding at all --
     and the unpack at the end is the stochastic one.  One (seed, step) serves both, and only
-    the unpack stores parameters: the whole step rounds each parameter once."""
+    the unpack stores parameters: the whole step rounds each parameter once.
+
+    update ("sgd", the default: everything above, launch for launch; or "adam"; needs state):
+    with "adam" the groups and state are torch.optim.Adam's / AdamW's (apply_adam) and the
+    step's first launch is the Adam update with the parameters not written and the flat x
+    receiving p_new; with master it is the master update, and the master's buffer is x.
+    clip_norm works as above.  loss_scale and rounding have no Adam form yet (DESIGN.md section
+    8, the Adam update's scope) and raise."""
     flatten_params = None
+    if update not in ("sgd", "adam"):
+        raise RuntimeError(f"fused_step: update must be 'sgd' or 'adam', got {update!r}")
+    if update == "adam":
+        if loss_scale is not None or rounding is not None:
+            raise RuntimeError("fused_step(update='adam'): loss_scale= and rounding= have no Adam form -- a skipped "
+                               "step must not advance the step count, which is kept on the host (DESIGN.md section "
+                               "8, the Adam update's scope)")
+        if state is None:
+            raise RuntimeError("fused_step(update='adam') runs apply_adam itself: pass state=optimizer.state")
     if rounding is not None and state is None:
         raise RuntimeError("fused_step(rounding=...) rounds in the step's own apply_gradient and unpack: pass "
                            "state=optimizer.state (without it the caller's apply_gradient has already rounded)")
@@ -752,8 +1038,13 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
             raise RuntimeError("fused_step(master=...) runs apply_gradient itself: pass state=optimizer.state")
         if master.param_names != list(param_names):
             raise RuntimeError("fused_step(master=...): the master weights were built for other param_names")
-        _sgd_master(param_groups, state, master, write=False, clip=clip, ls=ls)
+        if update == "adam":
+            _adam_master("fused_step(update='adam')", param_groups, state, master, False, clip)
+        else:
+            _sgd_master(param_groups, state, master, write=False, clip=clip, ls=ls)
         flatten_params = master.flat
+    elif update == "adam":
+        flatten_params = _adam_packed(param_groups, param_names, state, clip)
     elif state is not None:
         flatten_params = _sgd_packed(param_groups, param_names, state, clip, ls, sr)
     if defer_receive:

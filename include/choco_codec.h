@@ -1248,6 +1248,75 @@ int choco_params_consensus(const void* const* params, void* const* avg_out,
                            float* out /* 2 floats */, float* dists /* nseg or NULL */,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------- Adam / AdamW update fused with the pack
+ * torch.optim.Adam.step / AdamW.step (torch.optim.adam._single_tensor_adam; the reference's
+ * command line carries --adam_beta_1, --adam_beta_2 and --adam_eps) for nseg parameter
+ * tensors as ONE launch per chunk of tensors, with the pack into the flat fp32 buffer, the
+ * global-norm clip coefficient and the fp32 master copy in the same pass.  The tables are laid
+ * out as those of choco_params_sgd: tensor s holds lens[s] contiguous elements of dtype
+ * dtypes[s] in params[s] and grads[s] and owns flat elements [sum(lens[0..s)), + lens[s]);
+ * exp_avg[s] and exp_avg_sq[s] are its moments.  step[s] is the tensor's step count AFTER the
+ * increment (>= 1).  The hyperparameters are computed in doubles as torch computes them from
+ * Python floats, and each is narrowed once to fp32:
+ *     bc1 = 1 - beta1**step;  bc2 = 1 - beta2**step
+ *     nss = f32(-(lr / bc1));  bs = f32(bc2 ** 0.5);  dec = f32(1 - lr * wd)
+ *     w = f32(1 - beta1);  b2 = f32(beta2);  omb2 = f32(1 - beta2);  e = f32(eps)
+ * Per element, each line one rounding; rnd is the identity for an fp32 tensor and the
+ * round-to-nearest-even narrowing to the tensor's dtype for bf16 / fp16:
+ *     g' = g                       (coef given, c = *coef:  g' = rnd(c * g))
+ *     if wd != 0:  DECOUPLED:  p  = rnd(p * dec)
+ *                  coupled:    g' = rnd(fma(wd, p, g'))
+ *     d = g' - m                                     (fp32, not narrowed)
+ *     m = w < 0.5 ? rnd(fma(w, d, m)) : rnd(fma(-(1 - w), d, g'))     (both branches of torch's lerp)
+ *     v = rnd(v * b2);  t = omb2 * g';  v = rnd(fma(t, g', v))
+ *     den = rnd(sqrt(v));  den = rnd(den / bs);  den = rnd(den + e)   (a correctly rounded square
+ *                                                    root and division, never a reciprocal multiply)
+ *     q = m / den;  p_new = rnd(fma(nss, q, p))
+ * A skipped op (weight_decay == 0, tested on the double) is skipped.
+ *   choco_params_adam: p, g, m and v have the tensor's dtype.  flat (DEVICE, n fp32 elements,
+ *     or NULL) receives p_new; WRITE_PARAMS writes the parameters.  A CHOCO_ADAM_F_NOGRAD tensor
+ *     is pack-only: flat = p and nothing else written (passed over without flat).
+ *   choco_params_adam_master: p is master[i] (DEVICE, n fp32 elements, never NULL), updated in
+ *     place; exp_avg[s] and exp_avg_sq[s] hold FP32 elements whatever dtypes[s] is; g is the
+ *     gradient widened (exact); the lines are computed as for an fp32 tensor and nothing is
+ *     narrowed between them, the coefficient product included.  WRITE_PARAMS: params[s][j] =
+ *     p_new narrowed once to dtypes[s].  A NOGRAD tensor is passed over.
+ *   flags[s]: CHOCO_ADAM_F_DECOUPLED (AdamW's weight decay); CHOCO_ADAM_F_FIRST: the tensor has
+ *     no state yet, m = v = +0 -- the moments are written and never read;
+ *     CHOCO_ADAM_F_NOGRAD (p.grad is None).
+ *   mode: CHOCO_SGD_MODE_APPLY, optionally | CHOCO_SGD_MODE_WRITE_PARAMS |
+ *     CHOCO_SGD_MODE_WRITE_CLIPPED (needs coef: the product c * g, narrowed, goes back into
+ *     grads[s]).
+ *   coef_or_null: DEVICE, one float, choco_params_gradnorm's out + 1; one load per workgroup.
+ * Only the bytes of the layout's own elements are written.  Distinct tensors, and the flat
+ * buffer, must not overlap: this is NOT checked.  Every argument is checked before the first
+ * launch without a HIP call, in this order: null tables; nseg and n; the mode bits, a NULL
+ * master, nothing to write, the flat / master and coef alignment; then per tensor its length,
+ * dtype code and the running sum, unknown flag bits, the pointers' alignment to their element
+ * size, a NULL param, a NULL grad without NOGRAD, a NULL moment (FIRST or not: they are
+ * written), lr finite and >= 0, the betas in [0, 1), eps finite and >= 0, weight_decay finite
+ * and >= 0, step >= 1; last sum(lens) == n.  A bad call returns CHOCO_ERR_INVALID and launches
+ * nothing.  A layout takes choco_params_adam_launches(nseg) launches of "param_adam_kernel" /
+ * "param_adam_master_kernel" (four pointers a tensor: 54 tensors' table fits the 4 KB of kernel
+ * arguments). */
+#define CHOCO_ADAM_F_DECOUPLED 1
+#define CHOCO_ADAM_F_FIRST 2
+#define CHOCO_ADAM_F_NOGRAD 4
+int choco_params_adam_launches(int32_t nseg);
+/* torch.optim.adam._single_tensor_adam */
+int choco_params_adam(void* const* params, const void* const* grads, void* const* exp_avg,
+                      void* const* exp_avg_sq, const int64_t* lens, const int32_t* dtypes,
+                      const double* lr, const double* beta1, const double* beta2, const double* eps,
+                      const double* weight_decay, const double* step, const int32_t* flags,
+                      int32_t nseg, float* flat /* or NULL */, int64_t n, int32_t mode,
+                      const float* coef_or_null, void* stream);
+int choco_params_adam_master(void* const* params, const void* const* grads, void* const* exp_avg,
+                             void* const* exp_avg_sq, const int64_t* lens, const int32_t* dtypes,
+                             const double* lr, const double* beta1, const double* beta2,
+                             const double* eps, const double* weight_decay, const double* step,
+                             const int32_t* flags, int32_t nseg, float* master, int64_t n,
+                             int32_t mode, const float* coef_or_null, void* stream);
+
 /* ------------------------------------------- fused gossip step + compress
  * ParallelCHOCO_V.step's update_params_from_neighbor -> compress sequence
  * (pcode/optim/parallel_choco_v.py:116-142 -> :229-240, optim/utils.py:67-72) in
