@@ -184,6 +184,8 @@ SIGNATURES = {
                                    _p_i32, _c_i32, _vp, _c_i64, _c_i32, _vp, _vp]),
     "choco_params_adam_master": (_c_i32, [_pp, _pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64, _p_f64,
                                           _p_f64, _p_i32, _c_i32, _vp, _c_i64, _c_i32, _vp, _vp]),
+    "choco_params_adam_sr": (_c_i32, [_pp, _pp, _pp, _pp, _p_i64, _p_i32, _p_f64, _p_f64, _p_f64, _p_f64, _p_f64,
+                                      _p_f64, _p_i32, _c_i32, _vp, _c_i64, _c_i32, _vp, _c_u64, _c_u64, _vp]),
     "choco_gossip_topk_compress": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i64, _vp, _vp, _vp, _c_sz, _vp]),
     "choco_gossip_topk_compress_accumulate": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i64, _vp, _vp, _c_i32,
                                                        _c_f32, _vp, _c_sz, _vp]),

@@ -1762,7 +1762,7 @@ ADAM_F_DECOUPLED, ADAM_F_FIRST, ADAM_F_NOGRAD = 1, 2, 4                # CHOCO_A
 
 
 def params_adam_launches(nseg):
-    """Launches one params_adam / params_adam_master of `nseg` tensors takes."""
+    """Launches one params_adam / params_adam_master / params_adam(sr=) of `nseg` tensors takes."""
     return int(lib().choco_params_adam_launches(int(nseg)))
 
 
@@ -1788,7 +1788,7 @@ class ParamAdamPlan:
         self.holds, self.fits, self.fits_master_buf, self.gradnorm = (sgd.holds, sgd.fits, sgd.fits_master_buf,
                                                                       sgd.gradnorm)
 
-    def _adam(self, name, flat, mode, gclip, write_clipped):
+    def _adam(self, name, flat, mode, gclip, write_clipped, sr=()):
         if gclip is None and write_clipped:
             raise RuntimeError("write_clipped needs gclip (gradnorm()'s tensor)")
         sgd = self.sgd
@@ -1796,20 +1796,30 @@ class ParamAdamPlan:
         _lib.check(getattr(lib(), name)(self.param_ptrs, self.grad_ptrs, self.exp_avg_ptrs, self.exp_avg_sq_ptrs,
                                         sgd.lens, sgd.dts, self.lr, self.beta1, self.beta2, self.eps,
                                         self.weight_decay, self.step, self.flags, self.nseg, _ptr(flat), self.n, mode,
-                                        None if gclip is None else sgd._coef_ptr(gclip), _stream(self.device)), name)
+                                        None if gclip is None else sgd._coef_ptr(gclip), *sr, _stream(self.device)),
+                   name)
 
-    def run(self, flat=None, write=True, gclip=None, write_clipped=False):
+    def run(self, flat=None, write=True, gclip=None, write_clipped=False, sr=None):
         """One choco_params_adam over the tables as they stand: write -> the params are
         updated; flat (fp32, n elements, or None) receives the new params in the same pass (a
         tensor without a gradient is packed as it is).  gclip (gradnorm()'s tensor): every
         gradient is scaled by the global-norm clip coefficient as it is loaded, the product
         narrowed to the tensor's dtype; write_clipped: it is also stored into the grads'
-        storage."""
+        storage.
+
+        sr = (seed, step): choco_params_adam_sr -- on a bf16 tensor the lines run in fp32 with
+        nothing narrowed between them (gclip: coef_dtype=torch.float32's tensor, the product not
+        narrowed), exp_avg, exp_avg_sq and, where written, the parameter are stored through the
+        stochastic rounding with lanes 1, 2 and 0 of (seed, step, flat index), and flat receives
+        p_new unrounded; an fp32 tensor is updated as without; an fp16 tensor raises."""
         if flat is not None:
             _require(flat, torch.float32, "flat")
             if flat.device != self.device or flat.numel() != self.n:
                 raise RuntimeError(f"flat must hold {self.n} elements on {self.device}")
-        self._adam("choco_params_adam", flat, SGD_MODE_WRITE_PARAMS if write else 0, gclip, write_clipped)
+        mode = SGD_MODE_WRITE_PARAMS if write else 0
+        if sr is not None:
+            return self._adam("choco_params_adam_sr", flat, mode, gclip, write_clipped, _sr_words(sr))
+        self._adam("choco_params_adam", flat, mode, gclip, write_clipped)
 
     def run_master(self, master, write=True, gclip=None, write_clipped=False):
         """One choco_params_adam_master over the tables as they stand: the update runs on
@@ -1859,17 +1869,18 @@ def _adam_tables(params, grads, exp_avgs, exp_avg_sqs, lr, betas, eps, weight_de
 
 
 def params_adam(params, grads, exp_avgs, exp_avg_sqs, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step=1,
-                decoupled=False, first=False, flat=None, write=True, gclip=None, write_clipped=False, plan=None):
+                decoupled=False, first=False, flat=None, write=True, gclip=None, write_clipped=False, plan=None,
+                sr=None):
     """torch.optim.Adam.step / AdamW.step (decoupled) over a list of tensors in one batched
     launch per chunk (include/choco_codec.h, choco_params_adam).  grads[s] None: p.grad is None
     (the tensor is only packed into `flat`).  exp_avgs[s] / exp_avg_sqs[s]: the moments in the
     parameter's dtype, written, and read unless first[s].  step: the count after the increment.
     The hyperparameters, `betas` (a (beta1, beta2) pair), `step`, `decoupled` and `first` are
-    scalars or per-tensor lists.  gclip / write_clipped: ParamAdamPlan.run's.  Returns the plan
-    (pass it back in to reuse its tables)."""
+    scalars or per-tensor lists.  gclip / write_clipped / sr: ParamAdamPlan.run's.  Returns the
+    plan (pass it back in to reuse its tables)."""
     plan = _adam_tables(params, grads, exp_avgs, exp_avg_sqs, lr, betas, eps, weight_decay, step, decoupled, first,
                         plan, False)
-    plan.run(flat, write, gclip, write_clipped)
+    plan.run(flat, write, gclip, write_clipped, sr)
     return plan
 
 

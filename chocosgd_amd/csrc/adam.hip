@@ -28,7 +28,7 @@
 // of a chunk of tensors travels in the kernel arguments, tile_walk finds a tile's tensors, and
 // span_walk moves whole 8-element groups as 16-byte non-temporal vectors -- every load of a group
 // issued before its first store, one group in flight per thread: its four operands are 32 values
-// already -- and cut groups and incongruent tensors element by element (AdamBody).  Two
+// already -- and cut groups and incongruent tensors element by element (AdamBody).  Three
 // parameter sides:
 //     plain   param_adam_kernel: p, g, m and v in the tensor's own dtype, every line narrowed;
 //             an optional flat fp32 output receives p_new (the CHOCO pack), the parameters are
@@ -37,16 +37,28 @@
 //             whatever the tensor's dtype; nothing is narrowed between the lines, and the 16-bit
 //             parameter, where written, is the new master value narrowed once.  A NOGRAD tensor
 //             is passed over.
-// Both take `coef`, gradnorm's clip coefficient on the device or null: one uniform load per
+//     sr      param_adam_sr_kernel (choco_params_adam_sr): the plain kernel's sides -- p, g, m
+//             and v in the tensor's own dtype, the optional flat output, NOGRAD pack-only -- with
+//             the master kernel's arithmetic on a bf16 tensor: the lines run in fp32 on the
+//             widened operands, nothing is narrowed between them, and the three stores that
+//             leave the registers round stochastically (param_common.h st8_sr / st1_sr), each
+//             with a bit field of its own: p with lane 0, m with lane 1, v with lane 2 of
+//             (seed, step, flat index).  flat receives p_new unrounded.  An fp32 tensor of the
+//             same model is the plain kernel's update and draws no bits; the host refuses fp16.
+//             The launch carries lane 0's key; the other two are two uniform mixes a workgroup.
+// All take `coef`, gradnorm's clip coefficient on the device or null: one uniform load per
 // workgroup, the multiply on the load the update does anyway (narrowed in the plain kernel, not
-// in front of master arithmetic); WRITE_CLIPPED stores the narrowed product back into g.  A
-// launch writes only the bytes of its own elements; distinct tensors must not overlap, which is
-// not checked.
+// in front of master or sr arithmetic); WRITE_CLIPPED stores the narrowed product back into g.
+// A launch writes only the bytes of its own elements; distinct tensors must not overlap, which
+// is not checked.
 #include "param_common.h"
 
 #include <cmath>
 
 namespace choco {
+
+// the three kernels' sides (above)
+enum AdamSide { kAdamPlain, kAdamMaster, kAdamSr };
 
 constexpr uint32_t kAdamHasWd = 8u;  // derived on the host from the double, beside the ABI's three CHOCO_ADAM_F_* bits
 
@@ -66,8 +78,8 @@ struct AdamTable {
   uint8_t fl[kAdamCap];       // CHOCO_ADAM_F_* | kAdamHasWd
   int32_t nt;
 };
-// the table, the flat / master and coef pointers and four words: a launch carries at most 4 KB
-// of arguments
+// the table, the flat / master and coef pointers, four words and (sr) ONE 8-byte key -- 40 of
+// the 48 bytes: a launch carries at most 4 KB of arguments, and three keys would not fit
 static_assert(sizeof(AdamTable) + 48 <= 4096 - 256, "AdamTable must fit in the kernel arguments");
 
 // what one tensor's update needs (workgroup-uniform)
@@ -87,6 +99,7 @@ struct AdamTensor {
   bool wr_p;               // the parameter tensor is written
   bool clip, wr_c;         // g' = c * g on the load; the product goes back into g (WRITE_CLIPPED)
   float gc;
+  uint64_t key[3];         // param_adam_sr_kernel: the keys of the step's bit fields for p, m and v (lanes 0, 1, 2)
 };
 
 CHOCO_DEV AdamTensor adam_decode(const AdamTable& tb, int s) {
@@ -125,16 +138,19 @@ CHOCO_DEV void adam_math(const AdamTensor& t, float p, float g, float& m, float&
 }
 
 // The update of one element and of one group (span_walk's body, param_common.h).
-template <int DT, bool MASTER>
+template <int DT, int SIDE>
 struct AdamBody {
-  static constexpr int MDT = MASTER ? CHOCO_DT_F32 : DT;  // the arithmetic's and the moments' dtype
+  static constexpr bool MASTER = SIDE == kAdamMaster;
+  static constexpr bool SR = SIDE == kAdamSr && DT == CHOCO_DT_BF16;  // an fp32 tensor's sr update is the plain one
+  static constexpr int MDT = MASTER ? CHOCO_DT_F32 : DT;              // the moments' dtype
+  static constexpr int ADT = MASTER || SR ? CHOCO_DT_F32 : DT;        // the dtype every line is narrowed to
   const AdamTensor& t;
 
   // the gradient as the lines take it, from the loaded value
   CHOCO_DEV float grad(float g) const {
     if (!t.clip) return g;
     g = __fmul_rn(t.gc, g);
-    if (!MASTER) return rnd<DT>(g);
+    if (!MASTER && !SR) return rnd<DT>(g);
     if (DT != CHOCO_DT_F32) asm("" : "+v"(g));  // a narrowing below starts from the rounded fp32 (see rnd)
     return g;
   }
@@ -151,12 +167,19 @@ struct AdamBody {
     float v = t.first ? 0.0f : ld1<MDT>(t.v, j);
     float out;
     if (t.wr_c) st1<DT>(t.g, j, g);
-    adam_math<MDT>(t, p, g, m, v, out);
+    adam_math<ADT>(t, p, g, m, v, out);
     if (MASTER && DT != CHOCO_DT_F32) asm("" : "+v"(out));  // the narrowing below starts from the rounded fp32
-    st1<MDT>(t.m, j, m);
-    st1<MDT>(t.v, j, v);
+    if constexpr (SR) {
+      st1_sr(t.m, j, m, t.key[1], i);
+      st1_sr(t.v, j, v, t.key[2], i);
+    } else {
+      st1<MDT>(t.m, j, m);
+      st1<MDT>(t.v, j, v);
+    }
     if (MASTER || t.flat) t.flat[i] = out;
-    if (t.wr_p) st1<DT>(t.p, j, out);
+    if (!t.wr_p) return;
+    if constexpr (SR) st1_sr(t.p, j, out, t.key[0], i);
+    else st1<DT>(t.p, j, out);
   }
 
   CHOCO_DEV void group(int64_t e) const {
@@ -185,14 +208,21 @@ struct AdamBody {
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       g[k] = grad(g[k]);
-      adam_math<MDT>(t, p[k], g[k], m[k], v[k], out[k]);
+      adam_math<ADT>(t, p[k], g[k], m[k], v[k], out[k]);
       if (MASTER && DT != CHOCO_DT_F32) asm("" : "+v"(out[k]));
     }
     if (t.wr_c) st8<DT>(t.g, j, g);
-    st8<MDT>(t.m, j, m);
-    st8<MDT>(t.v, j, v);
+    if constexpr (SR) {
+      st8_sr(t.m, j, m, t.key[1], e);
+      st8_sr(t.v, j, v, t.key[2], e);
+    } else {
+      st8<MDT>(t.m, j, m);
+      st8<MDT>(t.v, j, v);
+    }
     if (MASTER || t.flat) st8<CHOCO_DT_F32>(t.flat, e, out);
-    if (t.wr_p) st8<DT>(t.p, j, out);
+    if (!t.wr_p) return;
+    if constexpr (SR) st8_sr(t.p, j, out, t.key[0], e);
+    else st8<DT>(t.p, j, out);
   }
 };
 
@@ -212,13 +242,17 @@ CHOCO_DEV bool adam_congruent(const AdamTensor& t) {
   return on_grid16(mis);
 }
 
-// workgroup tile0 + blockIdx.x of either kernel; flat: the plain kernel's flat output (or null),
-// the master kernel's fp32 copy; flat16: it is 16-byte aligned (or absent)
-template <bool MASTER>
+// workgroup tile0 + blockIdx.x of a kernel; flat: the plain and sr kernels' flat output (or
+// null), the master kernel's fp32 copy; flat16: it is 16-byte aligned (or absent); key0: the sr
+// kernel's qrng_key(seed, step)
+template <int SIDE>
 CHOCO_DEV void adam_tile(const AdamTable& tb, float* flat, int64_t tile0, int32_t flat16, int32_t mode,
-                         const float* coef) {
+                         const float* coef, uint64_t key0 = 0) {
+  constexpr bool MASTER = SIDE == kAdamMaster;
   const bool clip = coef != nullptr;
   const float gc = clip ? *coef : 1.0f;  // a uniform load
+  // the moments' keys: two uniform mixes a workgroup (three keys do not fit the arguments)
+  const uint64_t key1 = SIDE == kAdamSr ? sr_lane_key(key0, 1) : 0, key2 = SIDE == kAdamSr ? sr_lane_key(key0, 2) : 0;
   tile_walk(tb.off, tb.nt, tile0 + blockIdx.x, [&](int s, int64_t a, int64_t b) {
     AdamTensor t = adam_decode(tb, s);
     const bool nograd = (tb.fl[s] & CHOCO_ADAM_F_NOGRAD) != 0;
@@ -230,19 +264,32 @@ CHOCO_DEV void adam_tile(const AdamTable& tb, float* flat, int64_t tile0, int32_
     t.wr_c = t.clip && (mode & CHOCO_SGD_MODE_WRITE_CLIPPED) != 0;
     t.gc = gc;
     const bool vec = flat16 != 0 && adam_congruent<MASTER>(t);
-    for_dtype(t.dt, [&](auto DT) { span_walk(AdamBody<DT, MASTER>{t}, a, b, vec); });
+    if constexpr (SIDE == kAdamSr) {
+      t.key[0] = key0; t.key[1] = key1; t.key[2] = key2;
+      // the host has refused fp16
+      if (t.dt == CHOCO_DT_BF16) span_walk(AdamBody<CHOCO_DT_BF16, SIDE>{t}, a, b, vec);
+      else span_walk(AdamBody<CHOCO_DT_F32, SIDE>{t}, a, b, vec);
+    } else {
+      for_dtype(t.dt, [&](auto DT) { span_walk(AdamBody<DT, SIDE>{t}, a, b, vec); });
+    }
   });
 }
 
 __global__ __launch_bounds__(kPbThreads) void param_adam_kernel(const AdamTable tb, float* flat, int64_t tile0,
                                                                 int32_t flat16, int32_t mode, const float* coef) {
-  adam_tile<false>(tb, flat, tile0, flat16, mode, coef);
+  adam_tile<kAdamPlain>(tb, flat, tile0, flat16, mode, coef);
 }
 
 __global__ __launch_bounds__(kPbThreads) void param_adam_master_kernel(const AdamTable tb, float* master,
                                                                        int64_t tile0, int32_t master16, int32_t mode,
                                                                        const float* coef) {
-  adam_tile<true>(tb, master, tile0, master16, mode, coef);
+  adam_tile<kAdamMaster>(tb, master, tile0, master16, mode, coef);
+}
+
+__global__ __launch_bounds__(kPbThreads) void param_adam_sr_kernel(const AdamTable tb, float* flat, int64_t tile0,
+                                                                   int32_t flat16, int32_t mode, const float* coef,
+                                                                   uint64_t key0) {
+  adam_tile<kAdamSr>(tb, flat, tile0, flat16, mode, coef, key0);
 }
 
 // ------------------------------------------------------------------ the host side
@@ -266,6 +313,8 @@ struct AdamArgs {
   int32_t mode;
   const float* coef;  // device, the global-norm clip coefficient (choco_params_gradnorm's out + 1), or null
   bool master;
+  bool sr = false;       // choco_params_adam_sr
+  uint64_t sr_key = 0;   // sr: qrng_key(seed, step), lane 0's key
 };
 
 // the mode bits, the flat side and the coefficient
@@ -294,6 +343,9 @@ static int adam_check(const AdamArgs& a) {
         const int i = (int)s;
         constexpr int32_t kFlags = CHOCO_ADAM_F_DECOUPLED | CHOCO_ADAM_F_FIRST | CHOCO_ADAM_F_NOGRAD;
         CHOCO_REQUIRE((a.flags[s] & ~kFlags) == 0, "tensor %d: unknown flag bits 0x%x", i, (unsigned)a.flags[s]);
+        if (a.sr)
+          CHOCO_REQUIRE(a.dtypes[s] != CHOCO_DT_F16,
+                        "tensor %d: fp16 has no stochastic rounding (bf16 and fp32 tensors only)", i);
         const uintptr_t msz = a.master ? 4u : esz;  // a master update's moments are fp32
         CHOCO_REQUIRE(elem_aligned(a.params[s], esz) && elem_aligned(a.grads[s], esz) &&
                           elem_aligned(a.exp_avg[s], msz) && elem_aligned(a.exp_avg_sq[s], msz),
@@ -356,6 +408,10 @@ static int adam_run(const AdamArgs& a, hipStream_t st) {
       tb.nss[i] = nss; tb.bs[i] = bs; tb.wdc[i] = wdc; tb.w[i] = w; tb.b2[i] = b2; tb.omb2[i] = omb2; tb.e[i] = e;
       tb.fl[i] = (uint8_t)fl;
     }
+    if (a.sr)
+      return CHOCO_LAUNCH("param_adam_sr_kernel", "param_adam_sr_kernel", param_adam_sr_kernel,
+                          dim3((unsigned)c.tiles), dim3(kPbThreads), st, tb, a.flat, c.tile0, flat16, a.mode, a.coef,
+                          a.sr_key);
     return a.master ? CHOCO_LAUNCH("param_adam_master_kernel", "param_adam_master_kernel", param_adam_master_kernel,
                                    dim3((unsigned)c.tiles), dim3(kPbThreads), st, tb, a.flat, c.tile0, flat16, a.mode,
                                    a.coef)
@@ -389,5 +445,18 @@ CHOCO_API int choco_params_adam_master(void* const* params, const void* const* g
                                        void* stream) {
   const AdamArgs a{params, grads, exp_avg, exp_avg_sq, lens, dtypes, lr, beta1, beta2, eps,
                    weight_decay, step, flags, nseg,master, n, mode, coef_or_null, true};
+  return adam_run(a, as_stream(stream));
+}
+
+CHOCO_API int choco_params_adam_sr(void* const* params, const void* const* grads, void* const* exp_avg,
+                                   void* const* exp_avg_sq, const int64_t* lens, const int32_t* dtypes,
+                                   const double* lr, const double* beta1, const double* beta2, const double* eps,
+                                   const double* weight_decay, const double* step, const int32_t* flags, int32_t nseg,
+                                   float* flat, int64_t n, int32_t mode, const float* coef_or_null, uint64_t sr_seed,
+                                   uint64_t sr_step, void* stream) {
+  AdamArgs a{params, grads, exp_avg, exp_avg_sq, lens, dtypes, lr, beta1, beta2, eps,
+             weight_decay, step, flags, nseg, flat, n, mode, coef_or_null, false};
+  a.sr = true;
+  a.sr_key = qrng_key(sr_seed, sr_step);
   return adam_run(a, as_stream(stream));
 }

@@ -392,6 +392,13 @@ CHOCO_DEV __host__ uint64_t sr_word(uint64_t key, int64_t i) {
 CHOCO_DEV __host__ uint32_t sr_bits16(uint64_t w, int64_t i) {
   return (uint32_t)(w >> (16 * ((int)i & 3))) & 0xffffu;
 }
+// A step that rounds more than one value per element (adam.hip: the parameter and both moments)
+// draws each from a bit field of its own, a "lane": lane 0's key is the step's key itself -- the
+// parameter's lane everywhere, so an update and an unpack of one (seed, step) agree -- and lane
+// L > 0's is one mix away, mix(key + L * 0xD1B54A32D192ED03).  sr_word / sr_bits16 take either.
+CHOCO_DEV __host__ uint64_t sr_lane_key(uint64_t key, int lane) {
+  return lane == 0 ? key : splitmix64_mix(key + (uint64_t)lane * 0xD1B54A32D192ED03ull);
+}
 
 // The uniforms themselves come from xoroshiro128+ (Blackman & Vigna 2018, the
 // a=24 b=16 c=37 parameters) run for 8 steps per 16-element STREAM, its state

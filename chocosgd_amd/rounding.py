@@ -22,12 +22,26 @@ def sr_key(seed, step):
     return int(_mix(np.array([z], dtype=np.uint64))[0])
 
 
-def sr_bits(seed, step, start, n):
+def sr_lane_key(seed, step, lane=0):
+    """The key of bit field `lane` of (seed, step): lane 0's is sr_key(seed, step) itself, lane
+    L > 0's is mix(key_0 + L * 0xD1B54A32D192ED03), a Python int."""
+    key, lane = sr_key(seed, step), int(lane)
+    if lane < 0:
+        raise RuntimeError(f"sr_lane_key: lane must be >= 0, got {lane}")
+    if lane == 0:
+        return key
+    return int(_mix(np.array([(key + lane * 0xD1B54A32D192ED03) & _M64], dtype=np.uint64))[0])
+
+
+def sr_bits(seed, step, start, n, lane=0):
     """The 16 random bits of flat elements start .. start + n - 1 in step `step` of stream
     `seed`, a uint16 numpy array: w = mix(key + ((i >> 2) + 1) * gamma), bits
-    [16 (i & 3), 16 (i & 3) + 16) of it.  Element i's bits do not depend on `start`."""
+    [16 (i & 3), 16 (i & 3) + 16) of it.  Element i's bits do not depend on `start`.  lane: the
+    bit field of a step that rounds several values per element (the Adam update: 0 the
+    parameter, 1 exp_avg, 2 exp_avg_sq); key is sr_lane_key(seed, step, lane), lane 0 the stream
+    every other caller draws."""
     i = np.arange(int(start), int(start) + int(n), dtype=np.uint64)
-    w = _mix(np.uint64(sr_key(seed, step)) + ((i >> np.uint64(2)) + np.uint64(1)) * _GAMMA)
+    w = _mix(np.uint64(sr_lane_key(seed, step, lane)) + ((i >> np.uint64(2)) + np.uint64(1)) * _GAMMA)
     return ((w >> (np.uint64(16) * (i & np.uint64(3)))) & np.uint64(0xFFFF)).astype(np.uint16)
 
 

@@ -566,6 +566,12 @@ def _sr_args(what, rounding, param_groups, master=None, loss_scale=None, apply_g
     stochastic rounding does not take raise before anything is changed or the stream advanced."""
     if rounding is None:
         return None
+    _sr_refuse(what, param_groups, master, loss_scale, apply_grad_to_model)
+    return sr_pair(rounding)
+
+
+def _sr_refuse(what, param_groups, master=None, loss_scale=None, apply_grad_to_model=True):
+    """Raises for the combinations a step with rounding=... does not take; touches nothing."""
     if master is not None:
         raise RuntimeError(f"{what}: rounding= (stochastic rounding) with master= -- the master weights keep small "
                            "updates already, and the parameters are their round-to-nearest narrowing")
@@ -580,7 +586,6 @@ def _sr_args(what, rounding, param_groups, master=None, loss_scale=None, apply_g
             if p.dtype not in (torch.bfloat16, torch.float32):
                 raise RuntimeError(f"{what}: rounding= (stochastic rounding) takes bfloat16 parameters (and passes "
                                    f"float32 ones through), found {p.dtype}")
-    return sr_pair(rounding)
 
 
 def no_rounding(what, rounding):
@@ -834,12 +839,14 @@ def _adam_plan(params):
     return plan
 
 
-def _adam_batched(what, entries, hps, state, flat, master, write, clip):
+def _adam_batched(what, entries, hps, state, flat, master, write, clip, sr=None):
     """One batched launch (per chunk) for `entries`, a list of (group, param) in flat order:
     the plan's tables are written by index, missing state is created, the counts are
     incremented and the kernel runs -- after the norm pass where clip, a (clip_norm,
     write_clipped, total_norm) tuple, is given.  flat: the flat output or None; with master the
-    master's buffer.  Returns False, with nothing changed, where a tensor cannot take it."""
+    master's buffer.  sr, a (seed, step) pair: the stochastic-rounding update (no master); its
+    clip coefficient is computed in fp32, as the master update's is.  Returns False, with
+    nothing changed, where a tensor cannot take it."""
     if not entries:
         return False
     held = _adam_state(what, entries, state, master)
@@ -869,16 +876,19 @@ def _adam_batched(what, entries, hps, state, flat, master, write, clip):
             seen[i] = hp
     gclip = None
     if clip is not None:
-        gclip = plan.gradnorm(clip[0], coef_dtype=torch.float32 if master is not None else None, total_norm=clip[2])
+        fp32_coef = master is not None or sr is not None
+        gclip = plan.gradnorm(clip[0], coef_dtype=torch.float32 if fp32_coef else None, total_norm=clip[2])
     if master is not None:
         plan.run_master(flat, write, gclip=gclip, write_clipped=clip is not None and clip[1])
+    elif sr is not None:
+        plan.run(flat, write, gclip=gclip, write_clipped=clip is not None and clip[1], sr=sr)
     else:
         plan.run(flat, write, gclip=gclip, write_clipped=clip is not None and clip[1])
     return True
 
 
 def apply_adam(param_groups, state, flat_out=None, master=None, clip_norm=None, write_clipped=False,
-               total_norm=None):
+               total_norm=None, rounding=None):
     """Drop-in for torch.optim.Adam.step / AdamW.step on torch's own group keys (`lr`, `betas`,
     `eps`, `weight_decay`, `decoupled_weight_decay`, default False) and state keys
     (state[p]["step"], a CPU float32 0-dim tensor incremented on the host with no sync,
@@ -897,10 +907,26 @@ def apply_adam(param_groups, state, flat_out=None, master=None, clip_norm=None, 
     receives the new parameters in the same pass.  master (a MasterWeights of this model; no
     flat_out): the update runs in fp32 on the master copy, in place, with fp32 moments, and the
     parameters receive its values narrowed to their dtype.  clip_norm / write_clipped /
-    total_norm: apply_gradient's global-norm clipping, fused into the update the same way."""
+    total_norm: apply_gradient's global-norm clipping, fused into the update the same way.
+
+    rounding (a StochasticRounding, which advances by one step, or a (seed, step) pair; bf16 and
+    fp32 parameters, with or without flat_out and clip_norm, not with master): Adam for a bf16
+    model in the plain update's memory and traffic.  With round-to-nearest bf16 moments
+    exp_avg_sq * 0.999 is exp_avg_sq again and a step of lr below half an ulp of p is lost; here
+    a bf16 tensor's lines run in fp32 on the widened operands with nothing narrowed between them
+    (the clip coefficient is computed in fp32 and its product not narrowed), and the stores of
+    the parameter, exp_avg and exp_avg_sq round stochastically with bit fields ("lanes") 0, 1
+    and 2 of (seed, step, flat index in group order) (include/choco_codec.h; sr_bits(lane=) and
+    sr_narrow_bf16 restate it); flat_out receives p_new unrounded.  The moments stay bf16 under
+    torch's keys, so a state of plain apply_adam or torch.optim.AdamW continues here and the
+    reverse.  fp32 parameters get the same bits as without.  One launch of codec
+    ParamAdamPlan.run(sr=) per chunk; CPU tensors take apply_adam_sr_loop.  rounding=None is the
+    code path above, launch for launch."""
     what = "apply_adam"
     hps_of = {id(group): _adam_hp(what, group) for group in param_groups}
     clip = _clip_args(what, clip_norm, write_clipped, total_norm)
+    if rounding is not None:
+        _sr_refuse(what, param_groups, master)
     if master is not None:
         if flat_out is not None:
             raise RuntimeError("apply_adam(master=...): the master buffer is the flat copy; flat_out has no use")
@@ -909,6 +935,9 @@ def apply_adam(param_groups, state, flat_out=None, master=None, clip_norm=None, 
     entries = [(group, p) for group in param_groups for p in group["params"]]
     flat = getattr(flat_out, "buffer", flat_out)
     hps = [hps_of[id(group)] for group, _ in entries]
+    if rounding is not None:
+        _adam_sr(what, entries, hps, state, flat, True, clip, rounding)
+        return
     if _adam_batched(what, entries, hps, state, flat, None, True, clip):
         return
     apply_adam_loop(param_groups, state, None, clip_norm, write_clipped, total_norm)
@@ -939,6 +968,89 @@ def _adam_packed(param_groups, param_names, state, clip):
         return TensorBuffer.from_flat(flat, [p.size() for _, p in entries])
     apply_adam_loop(param_groups, state, None, *(clip or (None, False, None)))
     return None
+
+
+def _adam_sr(what, entries, hps, state, flat, write, clip, rounding):
+    """apply_adam(rounding=...) on `entries`, (group, param) in flat order: whatever can raise is
+    checked first, then the stream advances once, then the batched launch runs -- or the loop,
+    for tensors the kernel does not take.  Returns the (seed, step) pair it used."""
+    if flat is not None and (flat.dtype != torch.float32 or flat.dim() != 1
+                             or flat.numel() != sum(p.numel() for _, p in entries)):
+        raise RuntimeError(f"{what}(rounding=...): flat_out must be a flat float32 buffer over every parameter")
+    _adam_state(what, entries, state, None)
+    sr = sr_pair(rounding)
+    if not _adam_batched(what, entries, hps, state, flat, None, write, clip, sr=sr):
+        _adam_sr_entries(what, entries, hps, state, sr, clip, flat, write)
+    return sr
+
+
+def _adam_sr_entries(what, entries, hps, state, sr, clip, flat, write):
+    """apply_adam_sr_loop's body on (group, param) entries in flat order."""
+    held = _adam_state(what, entries, state, None)
+    for _, p in entries:
+        if p.dtype not in (torch.bfloat16, torch.float32):
+            raise RuntimeError(f"stochastic rounding takes bfloat16 and float32 parameters, found {p.dtype}")
+    rows = _adam_begin(entries, state, held, None)
+    with_grad = [p for _, p in entries if p.grad is not None]
+    coef = None
+    if clip is not None and with_grad:  # the coefficient in fp32, the product not narrowed: the master update's lines
+        coef = _clip_coef32(_total_norm([p.grad for p in with_grad], clip[2], torch.float32), clip[0])
+    off = 0
+    for (_, p), hp, row in zip(entries, hps, rows):
+        n = p.numel()
+        if row is None:
+            new = p.data.float()
+        else:
+            step, m, v, first = row
+            g = p.grad.data.float()
+            if coef is not None:
+                g = g * coef.to(g.device)
+                if clip[1]:
+                    p.grad.data.copy_(g)
+            if p.dtype == torch.float32:
+                new = p.data if write else p.data.clone()
+                _adam_lines(hp, new, g, m, v, step, first)
+            else:
+                new, m32, v32 = p.data.float(), m.float(), v.float()
+                _adam_lines(hp, new, g, m32, v32, step, first)
+                for t, t32, lane in ((m, m32, 1), (v, v32, 2)) + (((p.data, new, 0),) if write else ()):
+                    t.copy_(sr_narrow_bf16(t32, sr_bits(sr[0], sr[1], off, n, lane=lane)).view_as(t))
+        if flat is not None:
+            flat[off:off + n] = new.reshape(-1)
+        off += n
+
+
+def apply_adam_sr_loop(param_groups, state, seed, step, clip=None, flat=None, write=True):
+    """apply_adam(rounding=...) as one torch op per line and tensor: the path CPU tensors keep,
+    and what the kernel is compared against.  A bf16 tensor's p, g, exp_avg and exp_avg_sq are
+    widened, _adam_lines runs on the fp32 copies (nothing narrowed between the lines), and
+    exp_avg, exp_avg_sq and (write) the parameter are stored through sr_narrow_bf16 with
+    sr_bits(seed, step, its flat offset, its length, lane=1 / 2 / 0) -- the flat index in group
+    order, as `flat` (a flat fp32 tensor over every parameter, or None) lays the parameters out;
+    flat receives p_new unrounded.  An fp32 tensor takes apply_adam_loop's lines and draws no
+    bits; a parameter without a gradient puts its values into flat and is not written; any other
+    dtype raises.  `seed`, `step`: the rounding stream's, not the optimizer's count, which is
+    state[p]["step"] as ever.  clip, a (clip_norm, write_clipped, total_norm) tuple: the
+    coefficient in fp32 (_total_norm, _clip_coef32), one fp32 product per element, not narrowed
+    in front of the lines; write_clipped stores it, narrowed to the gradient's dtype."""
+    what = "apply_adam_sr_loop"
+    entries = [(group, p) for group in param_groups for p in group["params"]]
+    hps = [_adam_hp(what, group) for group, _ in entries]
+    _adam_sr_entries(what, entries, hps, state, (seed, step), clip, flat, write)
+
+
+def _adam_sr_packed(param_groups, param_names, state, clip, rounding):
+    """fused_step(state=..., update="adam_sr"): apply_adam(rounding=) with the parameters not
+    written and the pack of the unrounded p_new in one launch (the loop, for tensors the kernel
+    does not take, fills the flat buffer the same way).  Returns the flat TensorBuffer and the
+    (seed, step) pair the step's unpack rounds with."""
+    what = 'fused_step(update="adam_sr")'
+    entries = step_entries(param_groups, param_names, what)
+    hps = [_adam_hp(what, group) for group, _ in entries]
+    _sr_refuse(what, param_groups)
+    flat = torch.empty(sum(p.numel() for _, p in entries), dtype=torch.float32, device=entries[0][1].device)
+    sr = _adam_sr(what, entries, hps, state, flat, False, clip, rounding)
+    return TensorBuffer.from_flat(flat, [p.size() for _, p in entries]), sr
 
 
 def recover_params(param_groups, param_names, rank=None, neighbor_hat_params=None, get_hat_params=True):
@@ -1010,22 +1122,44 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
     with "adam" the groups and state are torch.optim.Adam's / AdamW's (apply_adam) and the
     step's first launch is the Adam update with the parameters not written and the flat x
     receiving p_new; with master it is the master update, and the master's buffer is x.
-    clip_norm works as above.  loss_scale and rounding have no Adam form yet (DESIGN.md section
-    8, the Adam update's scope) and raise."""
+    clip_norm works as above.  loss_scale has no Adam form (the Adam
+    update's scope) and raises, and so does rounding with "adam", whose arithmetic is torch's
+    per-line bf16.
+
+    update="adam_sr" (needs state and rounding; bf16 and fp32 parameters; not with master or
+    loss_scale): apply_adam(rounding=)'s arithmetic -- fp32 lines between stochastically
+    rounded bf16 stores.  The step's first launch is that update with the parameters not
+    written: exp_avg and exp_avg_sq are rounded there (lanes 1 and 2) and the flat x receives
+    the unrounded p_new; the consensus step, the compressor and the exchange see no rounding;
+    the unpack at the end stores each parameter once (lane 0), with the same (seed, step)."""
     flatten_params = None
-    if update not in ("sgd", "adam"):
-        raise RuntimeError(f"fused_step: update must be 'sgd' or 'adam', got {update!r}")
+    if update not in ("sgd", "adam", "adam_sr"):
+        raise RuntimeError(f"fused_step: update must be 'sgd', 'adam' or 'adam_sr', got {update!r}")
     if update == "adam":
         if loss_scale is not None or rounding is not None:
-            raise RuntimeError("fused_step(update='adam'): loss_scale= and rounding= have no Adam form -- a skipped "
-                               "step must not advance the step count, which is kept on the host (DESIGN.md section "
-                               "8, the Adam update's scope)")
+            raise RuntimeError("fused_step(update='adam'): loss_scale= has no Adam form -- a skipped step must not "
+                               "advance the step count, which is kept on the host -- and rounding= goes with "
+                               "update='adam_sr', whose fp32 lines between bf16 stores are another arithmetic than "
+                               "update='adam''s per-line bf16 (DESIGN.md section 8, the Adam update's scope)")
         if state is None:
             raise RuntimeError("fused_step(update='adam') runs apply_adam itself: pass state=optimizer.state")
+    if update == "adam_sr":
+        if rounding is None:
+            raise RuntimeError("fused_step(update='adam_sr') is the Adam update with stochastic rounding: pass "
+                               "rounding= (a StochasticRounding or a (seed, step) pair); without it the update is "
+                               "update='adam'")
+        if state is None:
+            raise RuntimeError("fused_step(update='adam_sr') runs apply_adam itself: pass state=optimizer.state")
+        if loss_scale is not None:
+            raise RuntimeError("fused_step(update='adam_sr'): loss_scale= has no Adam form -- a skipped step must not "
+                               "advance the step count, which is kept on the host (DESIGN.md section 8, the Adam "
+                               "update's scope)")
+        _sr_refuse("fused_step(update='adam_sr')", param_groups, master)
     if rounding is not None and state is None:
         raise RuntimeError("fused_step(rounding=...) rounds in the step's own apply_gradient and unpack: pass "
                            "state=optimizer.state (without it the caller's apply_gradient has already rounded)")
-    sr = _sr_args("fused_step", rounding, param_groups, master, loss_scale)
+    # update="adam_sr" advances the stream itself, once its own checks have passed (_adam_sr_packed)
+    sr = None if update == "adam_sr" else _sr_args("fused_step", rounding, param_groups, master, loss_scale)
     clip, ls = _scale_args("fused_step", loss_scale, clip_norm)
     if ls is not None and state is None:
         raise RuntimeError("fused_step(loss_scale=...) unscales in the step's own apply_gradient: pass "
@@ -1045,6 +1179,8 @@ def fused_step(compressor, param_groups, param_names, shapes, neighbor_hat_param
         flatten_params = master.flat
     elif update == "adam":
         flatten_params = _adam_packed(param_groups, param_names, state, clip)
+    elif update == "adam_sr":
+        flatten_params, sr = _adam_sr_packed(param_groups, param_names, state, clip, rounding)
     elif state is not None:
         flatten_params = _sgd_packed(param_groups, param_names, state, clip, ls, sr)
     if defer_receive:

@@ -894,6 +894,16 @@ int choco_params_sgd_master_gclip(void* const* params, const void* const* grads,
  *   `step` once per optimizer step and keeps `seed`; the same (seed, step) must not round
  *   the same parameter twice.  chocosgd_amd/rounding.py restates both in numpy.
  *
+ * Lanes.  A step that rounds more than one value per element (choco_params_adam_sr: the
+ * parameter and both moments) draws each from a bit field of its own, lane L of
+ * (seed, step, i):
+ *     key_0 = key                                                    (the stream above, unchanged)
+ *     key_L = mix(key_0 + L * 0xD1B54A32D192ED03)                    L = 1, 2
+ *     w, r16 as above with key_L in place of key
+ *   Lane 0 is the PARAMETER's lane in every entry point: an update that leaves the
+ *   parameters unwritten and a choco_params_unpack_sr of its flat output with the same
+ *   (seed, step) agree, and no field is used twice.  rounding.sr_bits(..., lane=) restates it.
+ *
  * choco_params_unpack_sr: choco_params_unpack's tables, tiles, walk, 16-byte rule, checks
  *   and launch count; a bf16 tensor receives the stochastic rounding of flat[i] with the
  *   bits of i, an fp32 tensor the copy.  Rejects an fp16 tensor (the message names it) in
@@ -1298,7 +1308,31 @@ int choco_params_consensus(const void* const* params, void* const* avg_out,
  * and >= 0, step >= 1; last sum(lens) == n.  A bad call returns CHOCO_ERR_INVALID and launches
  * nothing.  A layout takes choco_params_adam_launches(nseg) launches of "param_adam_kernel" /
  * "param_adam_master_kernel" (four pointers a tensor: 54 tensors' table fits the 4 KB of kernel
- * arguments). */
+ * arguments).
+ *
+ * choco_params_adam_sr: Adam for a bf16 model with stochastic rounding of the parameter AND of
+ * both moments (the section "stochastic rounding for bf16 models" above defines the rounding
+ * sr(x, r16), the bit stream and its lanes).  Round-to-nearest bf16 moments stall --
+ * v * 0.999 is v again -- and a step of lr below half an ulp of p is lost; this keeps both in
+ * expectation at choco_params_adam's memory and traffic.  choco_params_adam's arguments,
+ * tables, tiles, walk, 16-byte rule, flags, mode bits, coef and launch count, plus
+ * (sr_seed, sr_step).  For a BF16 tensor, element j at flat index i:
+ *     p, g, m, v are loaded as bf16 and widened to fp32 (FIRST: m = v = +0, not read);
+ *     the lines above run as for an fp32 tensor (choco_params_adam_master's arithmetic):
+ *       every line fp32, nothing narrowed between the lines, the same host scalars, with
+ *       coef g' = c * g not narrowed; den and q use the UNROUNDED v_new and m_new;
+ *     exp_avg[s][j]    = sr(m_new, lane 1's r16 of i)
+ *     exp_avg_sq[s][j] = sr(v_new, lane 2's r16 of i)
+ *     params[s][j]     = sr(p_new, lane 0's r16 of i)        (WRITE_PARAMS only)
+ *     flat[i]          = p_new, the unrounded fp32            (flat != NULL)
+ *     grads[s][j]      = rnd_bf16(c * g), round-to-nearest    (WRITE_CLIPPED only)
+ *   With WRITE_PARAMS unset and flat given, a later choco_params_unpack_sr of flat with the
+ *   same (seed, step) stores the parameters this call would have.  For an F32 tensor the
+ *   update is choco_params_adam's, bit for bit, and no bits are drawn; a NOGRAD tensor is
+ *   pack-only as there.  Rejects, in addition to choco_params_adam's list and at the place
+ *   of the per-tensor flag check: an F16 tensor ("fp16 has no stochastic rounding").
+ *   Launches: choco_params_adam_launches(nseg) of "param_adam_sr_kernel", an instantiation
+ *   of its own: the two kernels above carry neither the key nor the mixes. */
 #define CHOCO_ADAM_F_DECOUPLED 1
 #define CHOCO_ADAM_F_FIRST 2
 #define CHOCO_ADAM_F_NOGRAD 4
@@ -1316,6 +1350,12 @@ int choco_params_adam_master(void* const* params, const void* const* grads, void
                              const double* eps, const double* weight_decay, const double* step,
                              const int32_t* flags, int32_t nseg, float* master, int64_t n,
                              int32_t mode, const float* coef_or_null, void* stream);
+int choco_params_adam_sr(void* const* params, const void* const* grads, void* const* exp_avg,
+                         void* const* exp_avg_sq, const int64_t* lens, const int32_t* dtypes,
+                         const double* lr, const double* beta1, const double* beta2, const double* eps,
+                         const double* weight_decay, const double* step, const int32_t* flags,
+                         int32_t nseg, float* flat /* or NULL */, int64_t n, int32_t mode,
+                         const float* coef_or_null, uint64_t sr_seed, uint64_t sr_step, void* stream);
 
 /* ------------------------------------------- fused gossip step + compress
  * ParallelCHOCO_V.step's update_params_from_neighbor -> compress sequence

@@ -1,7 +1,7 @@
 """Time of one Adam / AdamW update of a whole model: the batched kernels (csrc/adam.hip) against
 torch's own optimizers on the same tensors, in the same process.
 
-    python tools/adam_time.py [--out FILE] [--updates 20] [--warmup 5] [--reps 5]
+    python tools/adam_time.py [--out FILE] [--updates 20] [--warmup 5] [--reps 5] [--sr]
 
 One JSON line per layout (ResNet-50's 161 tensors in bf16 and in fp32; each parameter its own
 allocation).  A window is `updates` updates between two device events after `warmup` updates;
@@ -20,6 +20,14 @@ spread (min, max) beside them:
 once and written once), *_tbps their quotient, *_hbm that over the 8.0 TB/s of the data sheet.
 kernel_us_*: the dispatch-attached time of the kernel's launches alone (the library's profile
 hooks), in a window of its own.  Needs a ROCm device; there is no fall-back.
+
+--sr: the three ways to run Adam on a bf16 model instead, ResNet-50 in bf16 only, same windows:
+  plain_write   param_adam_kernel, parameters written, no flat output (14 B per element)
+  sr_write      param_adam_sr_kernel (ParamAdamPlan.run(sr=)), parameters written, no flat (14 B)
+  master        param_adam_master_kernel, parameters written (28 B)
+  plain, sr     the CHOCO form of the first two: flat written, parameters not (16 B)
+with the ratios sr_write_vs_plain_write, sr_vs_plain and sr_write_vs_master (the last one must
+be below 1: the stochastic kernel moves half the master kernel's bytes).
 """
 import argparse
 import json
@@ -90,6 +98,14 @@ class Ours:
         self._advance()
         self.plan.run_master(self.flat, write=True)
 
+    def sr(self):
+        self._advance()
+        self.plan.run(self.flat, write=False, sr=(7, self.count))
+
+    def sr_write(self):
+        self._advance()
+        self.plan.run(None, write=True, sr=(7, self.count))
+
 
 def measure(name, lens, dtype, updates, warmup, reps):
     n, esz = sum(lens), torch.empty(0, dtype=dtype).element_size()
@@ -137,17 +153,57 @@ def measure(name, lens, dtype, updates, warmup, reps):
     return row
 
 
+def measure_sr(name, lens, updates, warmup, reps):
+    """The three ways on the bf16 layout, every way on a model of its own."""
+    dtype = torch.bfloat16
+    n = sum(lens)
+    ways = {"plain_write": Ours(lens, dtype, False).plain_write, "sr_write": Ours(lens, dtype, False).sr_write,
+            "master": Ours(lens, dtype, True).master, "plain": Ours(lens, dtype, False).plain,
+            "sr": Ours(lens, dtype, False).sr}
+    nbytes = {"plain_write": n * 14, "sr_write": n * 14, "master": n * 28, "plain": n * 16, "sr": n * 16}
+    kernels = {"plain_write": "param_adam_kernel", "sr_write": "param_adam_sr_kernel",
+               "master": "param_adam_master_kernel", "plain": "param_adam_kernel", "sr": "param_adam_sr_kernel"}
+    row = {"layout": name, "tensors": len(lens), "elements": n, "param_dtype": "bfloat16", "updates": updates,
+           "warmup": warmup, "reps": reps}
+    for fn in ways.values():
+        P.events(fn, warmup)
+    runs = {tag: [] for tag in ways}
+    for _ in range(reps):
+        for tag, fn in ways.items():
+            runs[tag].append(P.events(fn, updates)[1])
+    for tag in ways:
+        t = statistics.median(runs[tag])
+        row[f"{tag}_us"] = round(t, 1)
+        row[f"{tag}_us_min_max"] = [round(min(runs[tag]), 1), round(max(runs[tag]), 1)]
+        row[f"{tag}_bytes"] = nbytes[tag]
+        row[f"{tag}_tbps"] = round(nbytes[tag] / t / 1e6, 3)
+    for tag, fn in ways.items():
+        t, launches = P.kernel_time(fn, kernels[tag], updates)
+        if t:
+            row.update({f"kernel_us_{tag}": round(t, 2), f"kernel_launches_{tag}": launches})
+    row["sr_write_vs_plain_write"] = round(row["sr_write_us"] / row["plain_write_us"], 3)
+    row["sr_vs_plain"] = round(row["sr_us"] / row["plain_us"], 3)
+    row["sr_write_vs_master"] = round(row["sr_write_us"] / row["master_us"], 3)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--updates", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sr", action="store_true", help="plain, stochastic and master Adam on the bf16 layout")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "the timer needs a ROCm device"
     rows = []
     for name, lens, dtype in layouts():
-        rows.append(measure(name, lens, dtype, args.updates, args.warmup, args.reps))
+        if args.sr and dtype != torch.bfloat16:
+            continue
+        if args.sr:
+            rows.append(measure_sr(name, lens, args.updates, args.warmup, args.reps))
+        else:
+            rows.append(measure(name, lens, dtype, args.updates, args.warmup, args.reps))
         print(json.dumps(rows[-1]), flush=True)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
