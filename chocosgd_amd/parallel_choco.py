@@ -27,6 +27,7 @@ What changes underneath:
     (include/choco_codec.h "deferred receive"); x_hat / memory lag by one step until that
     compress or `flush_receive()` (utils.fused_step(defer_receive=True) drives it).
 """
+import contextlib
 import inspect
 
 import torch
@@ -49,8 +50,30 @@ class _CHOCOBase(_Compressor):
     def _draw_seed(self):
         return _draw_seed()  # this module's name, looked up per call: callers pin per-worker seeds through it
 
+    @contextlib.contextmanager
+    def _on_gossip_stream(self):
+        """Run the body on the gossip stream, ordered after everything the caller's current
+        stream holds so far, and make the caller's stream wait for it on the way out (an error
+        included).  The reference binds the gossip stream at construction; a caller that steps
+        under another stream hands x / x_hat / memory over in both directions.  With the
+        caller already on the gossip stream nothing is queued at all."""
+        caller = torch.cuda.current_stream(self.gossip_stream.device)
+        if caller == self.gossip_stream:
+            yield
+            return
+        self.gossip_stream.wait_stream(caller)
+        try:
+            with torch.cuda.stream(self.gossip_stream):
+                yield
+        finally:
+            caller.wait_stream(self.gossip_stream)
+
     def pipeline(self, sync_buffer, neighbor_hat_params, neighbors_info):
-        with torch.cuda.stream(self.gossip_stream):
+        # misuse, not a transport error: raised to the caller with nothing launched and the
+        # pending receive kept (inside the try it would be printed, and every later step would
+        # print it again and train without gossip)
+        self._require_fused_consensus(self._gossip(sync_buffer))
+        with self._on_gossip_stream():
             try:
                 self.compress(sync_buffer)
                 self.sync(sync_buffer)
@@ -134,10 +157,11 @@ class _CHOCOBase(_Compressor):
 
     def flush_receive(self):
         """Apply a deferred receive now (before reading x_hat / memory between steps).  It runs
-        on the gossip stream, where the pending messages, memory and x_hat were written."""
+        on the gossip stream, where the pending messages, memory and x_hat were written; the
+        caller's current stream waits for it, so x_hat / memory may be read there right after."""
         pend, self._pending = self._pending, None
         if pend is not None:
-            with torch.cuda.stream(self.gossip_stream):
+            with self._on_gossip_stream():
                 self._apply(*pend)
 
     @staticmethod
