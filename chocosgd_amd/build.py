@@ -26,6 +26,13 @@ HIPCC_FLAGS = [
     "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
 ]
 
+# Per-source flags.  The packed-sign step and the vote are built without the packed fp32
+# instructions (v_pk_add_f32 and kin): the step's one fp32 add per element must stay a plain
+# v_add_f32 next to its narrowing, and four of them packed in pairs gain nothing in a kernel
+# that waits for memory.
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"signstep.hip": NO_PACKED_FP32, "vote.hip": NO_PACKED_FP32}
+
 
 def _hipcc():
     for c in ("/opt/rocm/bin/hipcc", shutil.which("hipcc")):
@@ -77,7 +84,8 @@ def build_library(force=False, verbose=False, jobs=None, defines=(), lib=None):
             t = os.path.getmtime(obj)
             if all(os.path.getmtime(d) <= t for d in [src] + headers):
                 return obj
-        cmd = [hipcc, *HIPCC_FLAGS, *[f"-D{d}" for d in defines], "-I", INCLUDE, "-c", src, "-o", obj]
+        cmd = [hipcc, *HIPCC_FLAGS, *EXTRA_FLAGS.get(os.path.basename(src), []), *[f"-D{d}" for d in defines],
+               "-I", INCLUDE, "-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{r.stderr[-8000:]}")

@@ -1477,6 +1477,11 @@ class ParamSgdPlan:
         describes the arguments)."""
         _ef_call(self.param_ptrs, self.lens, self.dts, self.nseg, self.n, self.device, flat, mode, lr, divisor)
 
+    def sign_step(self, verdict):
+        """One choco_params_sign_step over the plan's parameter pointers and per-tensor `lr` as
+        they stand (params_sign_step describes the arguments)."""
+        plan_sign_step(self, verdict)
+
     def consensus(self, xsum, divisor, avg_out=None, master=None, dists=None, want_dist=True):
         """One choco_params_consensus over the plan's parameter pointers as they stand
         (params_consensus describes the arguments).  The workspace and the two-element fp32
@@ -2074,3 +2079,10 @@ def seg_host_state(plan, dev=None):
 
 def is_pow2_minus1(s):
     return s >= 1 and (s + 1) & s == 0 and int(math.log2(s + 1)) <= 16
+
+
+# ----------------------------------------------------------------------------- majority-vote signSGD
+# codec.sign_vote, codec.params_sign_step(_launches) and ParamSgdPlan.sign_step's body stand in
+# _signvote.py (it needs the names above, hence the import down here)
+from ._signvote import (MAX_VOTERS, params_sign_step, params_sign_step_launches, plan_sign_step,  # noqa: E402,F401
+                        sign_vote)

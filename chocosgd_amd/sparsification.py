@@ -144,16 +144,11 @@ class SignCompressor(object):
         return _home(out.view(src_tensor_size), home)
 
     def majority_vote(self, src_tensor_list):
-        """Per (row, word) majority of the voters' decoded signs; a tie encodes as "+"."""
-        n = 32 * src_tensor_list[0].numel()
+        """Per (row, word) majority of the voters' signs; a tie encodes as "+".  One launch on the
+        packed words (codec.sign_vote): the words that packing the sum of the decoded tensors gives."""
         home = None if src_tensor_list[0].is_cuda else src_tensor_list[0].device
-        total = None
-        for t in src_tensor_list:
-            t, _ = _on_device(t)
-            dec = codec.sign_unpack(t.int().contiguous(), n)
-            total = dec if total is None else total + dec
-        packed, _ = codec.sign_compress(total, want_norms=False)
-        return _home(packed, home)
+        messages = [_on_device(t)[0].int().contiguous().reshape(-1) for t in src_tensor_list]
+        return _home(codec.sign_vote(messages), home)
 
     def element_num(self, size):
         num = 1

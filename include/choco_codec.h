@@ -1194,6 +1194,45 @@ int choco_params_ef_launches(int32_t nseg);
 int choco_params_ef(void* const* params, const int64_t* lens, const int32_t* dtypes, int32_t nseg,
                     float* flat, int64_t n, int32_t mode, double lr, double divisor, void* stream);
 
+/* ------------------------------------------- majority-vote signSGD
+ * signSGD with majority vote (Bernstein et al. 2019; the reference's
+ * SignCompressor.majority_vote, pcode/utils/sparsification.py:165-181, and its
+ * --majority_vote flag), on the packed words end to end.
+ *
+ * choco_sign_vote: packed_list is a HOST array of nvoters DEVICE pointers to nwords packed
+ * sign words each (choco_sign_compress's); out receives the verdict,
+ *     out[j] bit b = 1  <=>  2 * #{q : packed_list[q][j] bit b} > nvoters,
+ * a tie (even nvoters) gives 0, which decodes as "+": the words that packing the sum of the
+ * decoded +-1 tensors gives.  All 32 bits of every word are voted.  out may be one of the
+ * inputs.  nvoters in [1, 64] (1: a copy; a vote of partial votes is not the vote of all, so
+ * there is no chaining), nwords in [0, 2^26] (0 launches nothing); pointers need 4-byte
+ * alignment (16-byte aligned ones take 16-byte loads).  One launch of "sign_vote_kernel".
+ *
+ * choco_params_sign_step: the update p -= lr * sign from a packed verdict, straight into the
+ * parameter tensors.  The tensor tables are those of choco_params_sgd (tensor s: lens[s]
+ * elements of dtype dtypes[s] in params[s], flat elements [sum(lens[0..s)), + lens[s])), lr[s]
+ * its learning rate; verdict holds ceil(n / 32) words in the (32, N') layout.  Per flat
+ * element i, element j of tensor s:
+ *     bit = (verdict[i mod N'] >> (i div N')) & 1
+ *     params[s][j] = rn(x + (bit ? +a : -a)) narrowed round-to-nearest-even, x = params[s][j]
+ *                    widened: one fp32 add, one narrowing; a = (float)lr[s], for a bf16 / fp16
+ *                    tensor rounded on to that dtype (torch converts alpha to the tensors' dtype)
+ * -- torch's p.add_(sign, alpha=-lr) on a tensor of p's dtype with sign = 1 - 2 bit.  NaN and
+ * inf propagate.  The padding bits (elements >= n), zero-length tensors and bytes outside the
+ * layout are neither read nor written.  Takes choco_params_sign_step_launches(nseg) launches
+ * of "param_sign_step_kernel" (0 for nseg <= 0).
+ *
+ * Both check every argument before the first launch without a HIP call -- null pointers and
+ * tables, nvoters or nwords out of range, a null voter, nseg <= 0, negative lengths or
+ * lengths that do not sum to n, an unknown dtype code, a NULL param of a non-empty tensor,
+ * misaligned pointers, a non-finite lr, verdict == NULL -- and a bad call returns
+ * CHOCO_ERR_INVALID and launches nothing. */
+int choco_sign_vote(const int32_t* const* packed_list, int32_t nvoters, int64_t nwords, int32_t* out,
+                    void* stream);
+int choco_params_sign_step_launches(int32_t nseg);
+int choco_params_sign_step(void* const* params, const int64_t* lens, const int32_t* dtypes, const double* lr,
+                           int32_t nseg, const int32_t* verdict, int64_t n, void* stream);
+
 /* ------------------------------------------- consensus evaluation
  * The reference's --evaluate_consensus (pcode/distributed_running_cv.py:110-115, :239-243):
  * the model averaged over the workers (agg_model(copy, op="avg"),

@@ -15,6 +15,9 @@ VARIANTS = {
     "poll1": ["CHOCO_POLL_BUDGET=1"],
     # the per-tensor norm pass with non-temporal loads: tools/dgc_step_probe.py --norm-ab
     "sqnorm_nt": ["CHOCO_SQNORM_NT=1"],
+    # the packed-sign step with wide accesses only at 16-byte aligned run starts (element
+    # accesses elsewhere): CHOCO_CODEC_LIB=... tools/sign_vote_time.py
+    "signstep_aligned": ["CHOCO_SIGNSTEP_ALIGNED=1"],
 }
 
 
