@@ -29,9 +29,10 @@ HIPCC_FLAGS = [
 # Per-source flags.  The packed-sign step and the vote are built without the packed fp32
 # instructions (v_pk_add_f32 and kin): the step's one fp32 add per element must stay a plain
 # v_add_f32 next to its narrowing, and four of them packed in pairs gain nothing in a kernel
-# that waits for memory.
+# that waits for memory.  The low-rank kernels likewise: their fmaf chains are written out one
+# accumulator at a time, in the order the contract fixes.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"signstep.hip": NO_PACKED_FP32, "vote.hip": NO_PACKED_FP32}
+EXTRA_FLAGS = {"signstep.hip": NO_PACKED_FP32, "vote.hip": NO_PACKED_FP32, "lowrank.hip": NO_PACKED_FP32}
 
 
 def _hipcc():

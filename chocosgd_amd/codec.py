@@ -2086,3 +2086,5 @@ def is_pow2_minus1(s):
 # _signvote.py (it needs the names above, hence the import down here)
 from ._signvote import (MAX_VOTERS, params_sign_step, params_sign_step_launches, plan_sign_step,  # noqa: E402,F401
                         sign_vote)
+# ----------------------------------------------------------------------------- low-rank (PowerSGD)
+from ._lowrank import LOWRANK_RANKS, LowRankPlan  # noqa: E402,F401

@@ -1233,6 +1233,71 @@ int choco_params_sign_step_launches(int32_t nseg);
 int choco_params_sign_step(void* const* params, const int64_t* lens, const int32_t* dtypes, const double* lr,
                            int32_t nseg, const int32_t* verdict, int64_t n, void* stream);
 
+/* ------------------------------------------- low-rank compression (PowerSGD)
+ * Rank-r PowerSGD (Vogels, Karimireddy, Jaggi, NeurIPS 2019) between choco_params_pack of the
+ * gradients and choco_params_sgd_flatgrad: two messages that are SUMMED by a plain all-reduce.
+ *
+ * The layout: tensor t holds lens[t] flat fp32 elements; rows[t] is its first dimension, or 0
+ * for a tensor of fewer than two dimensions (lens[t] must be whole rows).  With cols = lens[t] /
+ * rows[t], tensor t is COMPRESSED iff rows[t] > 0, cols > 0 and rows * cols > rank * (rows +
+ * cols); it is then the row-major matrix M_t (rows x cols) at its flat offset.  Every other
+ * tensor is uncompressed.  rank is 1, 2 or 4.
+ *   message 1 = [P_0 | P_1 | .. | the uncompressed tensors' elements, in layout order],
+ *               P_t rows x rank row-major, compressed tensors in layout order
+ *   message 2 = [Q_0 | Q_1 | ..], Q_t cols x rank row-major
+ *
+ * choco_lowrank_plan_len / choco_lowrank_plan (host only): the length in int64 words of the
+ * table of a layout, and the table itself (returned: its length; negative on a bad argument).
+ * The table is passed to every call twice: the host copy (the checks, the grids) and a device
+ * copy (16-byte aligned) the kernels read their work items from.  Its first words:
+ *   [0] a magic number  [1] n  [2] nseg  [3] rank  [4] compressed tensors  [5] message 1 length
+ *   [6] message 2 length  [7] the tail's start in message 1  [8..15] item counts, workspace
+ *   floats and section offsets
+ * and from word 16 one row per tensor: {compressed (0 / 1), its P offset in message 1 (the
+ * tail offset of an uncompressed tensor), its Q offset in message 2 (-1), its flat offset}.
+ * choco_lowrank_workspace_size(table): bytes of scratch choco_lowrank_backproject needs (the
+ * row-slab partials); it holds nothing between calls.
+ *
+ * One step, g the flat gradient, e the flat error memory (n elements each, 16-byte aligned):
+ *   choco_lowrank_project        M = fl(g + e), one rounding, stored over e; P_t = M_t Q_t with
+ *                                q = message 2's layout; the uncompressed tensors' g into the
+ *                                tail (their e is neither read nor written).
+ *                                One launch of "lowrank_project_kernel".
+ *   (all-reduce message 1)
+ *   choco_lowrank_orthogonalize  modified Gram-Schmidt in place on the columns of every P_t in
+ *                                column order: col /= (||col||_2 + 1e-8), later -= (col^T later)
+ *                                col; norms and dots are fp64 sums in a fixed order, the
+ *                                quotient and the difference are formed in fp64 and rounded
+ *                                once.  A zero column stays zero.  "lowrank_orth_kernel".
+ *   choco_lowrank_backproject    Q_t = M_t^T P_t (M from e) into message 2.
+ *                                "lowrank_backproject_kernel", and one launch of
+ *                                "lowrank_slabsum_kernel" where a matrix has more than 256 rows.
+ *   (all-reduce message 2)
+ *   choco_lowrank_decode         compressed: flat_out = P_t Q_t^T, e = fl(M - fl(flat_out /
+ *                                (float)divisor)), a true division; uncompressed: flat_out =
+ *                                the tail's elements, e untouched.  "lowrank_decode_kernel".
+ * Every sum runs in an order fixed by the table and the rank (fmaf accumulation, no atomics):
+ * the same inputs give the same bits.  Everything runs on `stream`; nothing is allocated.
+ *
+ * Every call checks its arguments before the first launch without a HIP call -- null
+ * pointers, a rank outside {1, 2, 4}, a table that is not one or was built for another n or
+ * rank, message lengths that are not the table's, misaligned pointers, a workspace too small,
+ * divisor <= 0 -- and a bad call returns CHOCO_ERR_INVALID and launches nothing. */
+int64_t choco_lowrank_plan_len(const int64_t* rows, const int64_t* lens, int32_t nseg, int32_t rank);
+int64_t choco_lowrank_plan(const int64_t* rows, const int64_t* lens, int32_t nseg, int32_t rank, int64_t* plan);
+size_t choco_lowrank_workspace_size(const int64_t* plan_host);
+int choco_lowrank_project(const float* g, float* e, const float* q, float* msg1, int64_t msg1_len,
+                          int64_t msg2_len, const int64_t* plan_host, const int64_t* plan_dev, int64_t n,
+                          int32_t rank, void* stream);
+int choco_lowrank_orthogonalize(float* msg1, int64_t msg1_len, const int64_t* plan_host, const int64_t* plan_dev,
+                                int64_t n, int32_t rank, void* stream);
+int choco_lowrank_backproject(const float* e, const float* msg1, int64_t msg1_len, float* msg2, int64_t msg2_len,
+                              void* ws, size_t ws_bytes, const int64_t* plan_host, const int64_t* plan_dev,
+                              int64_t n, int32_t rank, void* stream);
+int choco_lowrank_decode(float* e, const float* msg1, int64_t msg1_len, const float* msg2, int64_t msg2_len,
+                         float* flat_out, double divisor, const int64_t* plan_host, const int64_t* plan_dev,
+                         int64_t n, int32_t rank, void* stream);
+
 /* ------------------------------------------- consensus evaluation
  * The reference's --evaluate_consensus (pcode/distributed_running_cv.py:110-115, :239-243):
  * the model averaged over the workers (agg_model(copy, op="avg"),
