@@ -1,4 +1,5 @@
-"""The Python side of the low-rank (PowerSGD) entry points (csrc/lowrank.hip).  codec.py re-exports
+"""The Python side of the low-rank (PowerSGD) entry points (csrc/lowrank.hip; ranks 8, 16 and 32 run
+csrc/lowrank_mfma.hip's matrix-instruction kernels behind the same calls).  codec.py re-exports
 `LowRankPlan` and `LOWRANK_RANKS`; powersgd.py is the step built on them."""
 import ctypes
 
@@ -7,7 +8,7 @@ import torch
 from . import _lib
 from . import codec as _c
 
-LOWRANK_RANKS = (1, 2, 4)
+LOWRANK_RANKS = (1, 2, 4, 8, 16, 32)
 _HDR = 16  # header words of the table; then one {compressed, P / tail offset, Q offset, flat offset} row per tensor
 
 

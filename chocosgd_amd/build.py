@@ -30,9 +30,13 @@ HIPCC_FLAGS = [
 # instructions (v_pk_add_f32 and kin): the step's one fp32 add per element must stay a plain
 # v_add_f32 next to its narrowing, and four of them packed in pairs gain nothing in a kernel
 # that waits for memory.  The low-rank kernels likewise: their fmaf chains are written out one
-# accumulator at a time, in the order the contract fixes.
+# accumulator at a time, in the order the contract fixes.  lowrank_mfma.hip: its M = g + e and
+# e = M - out / W lines sit between 16-byte loads and stores as four-wide expressions, which the
+# compiler would otherwise pair up; they stay the same plain v_add_f32 / v_sub_f32 as lowrank.hip's,
+# so the error memory is produced by the same instructions at every rank.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"signstep.hip": NO_PACKED_FP32, "vote.hip": NO_PACKED_FP32, "lowrank.hip": NO_PACKED_FP32}
+EXTRA_FLAGS = {"signstep.hip": NO_PACKED_FP32, "vote.hip": NO_PACKED_FP32, "lowrank.hip": NO_PACKED_FP32,
+               "lowrank_mfma.hip": NO_PACKED_FP32}
 
 
 def _hipcc():

@@ -30,40 +30,14 @@
 //     in place in global memory; a thread keeps to its own rows, so only the fp64 reductions
 //     (butterfly, then the waves in order) need barriers.
 // No atomics anywhere: every output is a function of the inputs in an order the table fixes.
-#include "choco_common.h"
+// The table's layout, its builder and the launch check are in lowrank.h, shared with lowrank_mfma.hip:
+// ranks 8, 16 and 32 run project, back-project and decode there on the fp32 matrix instruction, behind
+// the entry points below, and orthogonalise here with kLrHiOrthStage staged rows.
+#include "lowrank.h"
 
 #include <cmath>
 
 namespace choco {
-
-constexpr int kLrThreads = 256;
-constexpr int kLrWaves = kLrThreads / 64;
-constexpr int kLrColBlock = 2048;      // columns of the r-column factor staged in LDS at a time
-constexpr int kLrRowCap = 256;         // rows of a row item
-constexpr int64_t kLrItemElems = 32768;  // elements a row item aims at
-constexpr int64_t kLrCopyChunk = 8192;   // elements of an uncompressed tensor per item
-constexpr int kLrStrip = 64;           // back-project: columns of an item
-constexpr int kLrSlab = 256;           // back-project: rows of an item
-constexpr int kLrOrthStage = 2048;     // orthogonalise: rows of P held in LDS
-
-// the table's header words
-enum LrHdr {
-  kLrMagic = 0, kLrN, kLrNseg, kLrRank, kLrNcomp, kLrMsg1, kLrMsg2, kLrPTotal, kLrNRow, kLrNBp, kLrNSum, kLrWsFloats,
-  kLrOffMat, kLrOffRow, kLrOffBp, kLrOffSum, kLrHdrLen
-};
-constexpr int64_t kLrMagicValue = 0x4c52504c414eLL;  // "LRPLAN"
-// a matrix row: {flat offset, rows, cols, P offset in message 1, Q offset in message 2, slabs,
-// workspace offset, tensor}
-constexpr int kLrMatRow = 8;
-constexpr int kLrItemRow = 4;
-
-struct LrMat {
-  int64_t off, rows, cols, poff, qoff, nslab, wsoff;
-};
-CHOCO_DEV LrMat lr_mat(const int64_t* __restrict__ plan, int64_t m) {
-  const int64_t* r = plan + plan[kLrOffMat] + kLrMatRow * m;
-  return LrMat{r[0], r[1], r[2], r[3], r[4], r[5], r[6]};
-}
 
 // a row of up to four columns' factors from the LDS planes: one 16-byte read where j is on the
 // 16-byte grid, else four words
@@ -299,19 +273,19 @@ CHOCO_DEV void lr_block_sum(double (&v)[K], double (*red)[K]) {
   for (int k = 0; k < K; ++k) v[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
 }
 
-template <int R>
+template <int R, int STAGE = kLrOrthStage>
 __global__ __launch_bounds__(kLrThreads) void lowrank_orth_kernel(float* __restrict__ msg1,
                                                                   const int64_t* __restrict__ plan) {
-  __shared__ float Ps[kLrOrthStage * R];
+  __shared__ float Ps[STAGE * R];
   __shared__ double red[kLrWaves][R];
   const LrMat M = lr_mat(plan, blockIdx.x);
   float* P = msg1 + M.poff;
   const int64_t rows = M.rows;
-  const int ns = (int)(rows < kLrOrthStage ? rows : kLrOrthStage);
+  const int ns = (int)(rows < STAGE ? rows : STAGE);
   for (int i = threadIdx.x; i < ns * R; i += kLrThreads) Ps[i] = P[i];
   __syncthreads();
   // thread t owns rows t, t + 256, ...: the staged ones in LDS, the others in place
-  auto at = [&](int64_t i) -> float* { return i < kLrOrthStage ? Ps + i * R : P + i * R; };
+  auto at = [&](int64_t i) -> float* { return i < STAGE ? Ps + i * R : P + i * R; };
 #pragma unroll
   for (int k = 0; k < R; ++k) {
     double s[1] = {0.0};
@@ -329,14 +303,16 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_orth_kernel(float* __restr
       const float v = (float)((double)r[k] / den);
       r[k] = v;
 #pragma unroll
-      for (int l = k + 1; l < R; ++l) dot[l] += (double)v * (double)r[l];
+      for (int l = 0; l < R; ++l)  // l > k as a predicate: dot[] keeps constant indices where k is not unrolled
+        if (l > k) dot[l] += (double)v * (double)r[l];
     }
     if (k + 1 < R) {
       lr_block_sum<R>(dot, red);
       for (int64_t i = threadIdx.x; i < rows; i += kLrThreads) {
         float* r = at(i);
 #pragma unroll
-        for (int l = k + 1; l < R; ++l) r[l] = (float)((double)r[l] - dot[l] * (double)r[k]);
+        for (int l = 0; l < R; ++l)
+          if (l > k) r[l] = (float)((double)r[l] - dot[l] * (double)r[k]);
       }
     }
   }
@@ -344,118 +320,27 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_orth_kernel(float* __restr
   for (int i = threadIdx.x; i < ns * R; i += kLrThreads) P[i] = Ps[i];
 }
 
-// ---------------------------------------------------------------- the table (host)
-static bool lr_rank_ok(int32_t r) { return r == 1 || r == 2 || r == 4; }
-
-// Counts (plan == nullptr) or writes the table; returns its length, or a negative status.
-static int64_t lr_build(const int64_t* rows, const int64_t* lens, int32_t nseg, int32_t rank, int64_t* plan) {
-  CHOCO_REQUIRE(rows && lens, "null pointer");
-  CHOCO_REQUIRE(nseg >= 1, "nseg must be at least 1");
-  CHOCO_REQUIRE(lr_rank_ok(rank), "rank must be 1, 2 or 4, got %d", (int)rank);
-  int64_t n = 0;
-  for (int32_t t = 0; t < nseg; ++t) {
-    CHOCO_REQUIRE(rows[t] >= 0 && lens[t] >= 0, "tensor %d: negative size", (int)t);
-    CHOCO_REQUIRE(rows[t] == 0 || lens[t] % rows[t] == 0, "tensor %d: %lld elements are not whole rows of %lld",
-                  (int)t, (long long)lens[t], (long long)rows[t]);
-    n += lens[t];
-    CHOCO_REQUIRE(n < (int64_t)INT32_MAX, "n out of range");
-  }
-  CHOCO_REQUIRE(n > 0, "n out of range");
-  const int64_t R = rank;
-  auto compressed = [&](int32_t t) {
-    if (rows[t] == 0 || lens[t] == 0) return false;
-    const int64_t c = lens[t] / rows[t];
-    return rows[t] * c > R * (rows[t] + c);
-  };
-  auto item_rows = [&](int64_t c) {
-    const int64_t want = kLrItemElems / c;
-    return want < kLrWaves ? (int64_t)kLrWaves : want > kLrRowCap ? (int64_t)kLrRowCap : want;
-  };
-  int64_t ncomp = 0, nrow = 0, nbp = 0, nsum = 0;
-  for (int32_t t = 0; t < nseg; ++t) {
-    if (!compressed(t)) {
-      nrow += (lens[t] + kLrCopyChunk - 1) / kLrCopyChunk;
-      continue;
-    }
-    const int64_t r = rows[t], c = lens[t] / r, nslab = (r + kLrSlab - 1) / kLrSlab;
-    ++ncomp;
-    nrow += (r + item_rows(c) - 1) / item_rows(c);
-    nbp += nslab * ((c + kLrStrip - 1) / kLrStrip);
-    if (nslab > 1) nsum += (c * R + kLrThreads - 1) / kLrThreads;
-  }
-  const int64_t off_tensor = kLrHdrLen, off_mat = off_tensor + 4 * (int64_t)nseg, off_row = off_mat + kLrMatRow * ncomp,
-                off_bp = off_row + kLrItemRow * nrow, off_sum = off_bp + kLrItemRow * nbp,
-                total = off_sum + kLrItemRow * nsum;
-  if (!plan) return total;
-  int64_t p_total = 0;
-  for (int32_t t = 0; t < nseg; ++t)
-    if (compressed(t)) p_total += rows[t] * R;
-  int64_t *tr = plan + off_tensor, *mr = plan + off_mat, *ri = plan + off_row, *bi = plan + off_bp, *si = plan + off_sum;
-  int64_t off = 0, poff = 0, qoff = 0, tail = p_total, wsoff = 0, m = 0;
-  for (int32_t t = 0; t < nseg; ++t, tr += 4) {
-    if (!compressed(t)) {
-      tr[0] = 0; tr[1] = tail; tr[2] = -1; tr[3] = off;
-      for (int64_t o = 0; o < lens[t]; o += kLrCopyChunk, ri += kLrItemRow) {
-        ri[0] = -1; ri[1] = off + o; ri[2] = lens[t] - o < kLrCopyChunk ? lens[t] - o : kLrCopyChunk; ri[3] = tail + o;
-      }
-      tail += lens[t];
-      off += lens[t];
-      continue;
-    }
-    const int64_t r = rows[t], c = lens[t] / r, nslab = (r + kLrSlab - 1) / kLrSlab, ir = item_rows(c);
-    tr[0] = 1; tr[1] = poff; tr[2] = qoff; tr[3] = off;
-    mr[0] = off; mr[1] = r; mr[2] = c; mr[3] = poff; mr[4] = qoff; mr[5] = nslab; mr[6] = nslab > 1 ? wsoff : 0;
-    mr[7] = t;
-    mr += kLrMatRow;
-    for (int64_t r0 = 0; r0 < r; r0 += ir, ri += kLrItemRow) {
-      ri[0] = m; ri[1] = r0; ri[2] = r - r0 < ir ? r - r0 : ir; ri[3] = 0;
-    }
-    for (int64_t sl = 0; sl < nslab; ++sl)
-      for (int64_t c0 = 0; c0 < c; c0 += kLrStrip, bi += kLrItemRow) {
-        bi[0] = m; bi[1] = c0; bi[2] = sl; bi[3] = 0;
-      }
-    if (nslab > 1) {
-      for (int64_t e0 = 0; e0 < c * R; e0 += kLrThreads, si += kLrItemRow) {
-        si[0] = m; si[1] = e0; si[2] = c * R - e0 < kLrThreads ? c * R - e0 : kLrThreads; si[3] = 0;
-      }
-      wsoff += nslab * c * R;
-    }
-    poff += r * R;
-    qoff += c * R;
-    off += lens[t];
-    ++m;
-  }
-  int64_t* h = plan;
-  h[kLrMagic] = kLrMagicValue; h[kLrN] = n; h[kLrNseg] = nseg; h[kLrRank] = rank; h[kLrNcomp] = ncomp;
-  h[kLrMsg1] = tail; h[kLrMsg2] = qoff; h[kLrPTotal] = p_total; h[kLrNRow] = nrow; h[kLrNBp] = nbp; h[kLrNSum] = nsum;
-  h[kLrWsFloats] = wsoff; h[kLrOffMat] = off_mat; h[kLrOffRow] = off_row; h[kLrOffBp] = off_bp; h[kLrOffSum] = off_sum;
-  return total;
-}
-
-// What every launch checks first, with no HIP call: the host copy of the table against the
-// call's n, rank and message lengths (a null or zero length is a message the call does not use).
-static int lr_check(const int64_t* plan_host, const void* plan_dev, int64_t n, int32_t rank, int64_t msg1_len,
-                    int64_t msg2_len) {
-  CHOCO_REQUIRE(plan_host && plan_dev, "null table");
-  CHOCO_REQUIRE(lr_rank_ok(rank), "rank must be 1, 2 or 4, got %d", (int)rank);
-  CHOCO_REQUIRE(plan_host[kLrMagic] == kLrMagicValue, "plan_host is not a choco_lowrank_plan table");
-  CHOCO_REQUIRE(plan_host[kLrN] == n && n > 0 && n < (int64_t)INT32_MAX, "the table was built for n = %lld, got %lld",
-                (long long)plan_host[kLrN], (long long)n);
-  CHOCO_REQUIRE(plan_host[kLrRank] == rank, "the table was built for rank %lld, got %d", (long long)plan_host[kLrRank],
-                (int)rank);
-  CHOCO_REQUIRE(msg1_len == plan_host[kLrMsg1], "message 1 holds %lld elements in the table, got %lld",
-                (long long)plan_host[kLrMsg1], (long long)msg1_len);
-  CHOCO_REQUIRE(msg2_len < 0 || msg2_len == plan_host[kLrMsg2], "message 2 holds %lld elements in the table, got %lld",
-                (long long)plan_host[kLrMsg2], (long long)msg2_len);
-  CHOCO_REQUIRE(aligned16(plan_dev), "the device table must be 16-byte aligned");
-  return CHOCO_OK;
-}
-
 // rank -> the kernel's instance
 #define LR_BY_RANK(rank, KERNEL, ...)                                                                             \
   ((rank) == 1 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<1>, __VA_ARGS__)                                           \
                : (rank) == 2 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<2>, __VA_ARGS__)                             \
                              : CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<4>, __VA_ARGS__))
+// Diagnostic build only (tools/build_variants.py "lowrank_vector8"): rank 8 on the vector templates,
+// whose 64 KB Q stage still fits -- the A/B against the matrix-instruction kernels.
+#ifdef CHOCO_LOWRANK_VECTOR8
+#define LR_VECTOR8(rank, KERNEL, ...) \
+  if ((rank) == 8) return CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<8>, __VA_ARGS__)
+#else
+#define LR_VECTOR8(rank, KERNEL, ...)
+#endif
+// orthogonalise is the one kernel both families share: the same structure with fewer staged rows
+#define LR_ORTH_HI(rank, ...)                                                                                     \
+  ((rank) == 8 ? CHOCO_LAUNCH("lowrank_orth_kernel", "lowrank_orth_kernel", (lowrank_orth_kernel<8, kLrHiOrthStage>), \
+                              __VA_ARGS__)                                                                        \
+               : (rank) == 16 ? CHOCO_LAUNCH("lowrank_orth_kernel", "lowrank_orth_kernel",                        \
+                                             (lowrank_orth_kernel<16, kLrHiOrthStage>), __VA_ARGS__)              \
+                              : CHOCO_LAUNCH("lowrank_orth_kernel", "lowrank_orth_kernel",                        \
+                                             (lowrank_orth_kernel<32, kLrHiOrthStage>), __VA_ARGS__))
 
 }  // namespace choco
 
@@ -485,6 +370,8 @@ CHOCO_API int choco_lowrank_project(const float* g, float* e, const float* q, fl
   CHOCO_REQUIRE(aligned16(g) && aligned16(e), "g and e must be 16-byte aligned");
   CHOCO_REQUIRE(aligned4(q) && aligned4(msg1), "q and msg1 must be 4-byte aligned");
   const dim3 grid((unsigned)plan_host[kLrNRow]), block(kLrThreads);
+  LR_VECTOR8(rank, lowrank_project_kernel, grid, block, as_stream(stream), g, e, q, msg1, plan_dev);
+  if (lr_rank_hi(rank)) return lr_hi_project(rank, grid, as_stream(stream), g, e, q, msg1, plan_dev);
   return LR_BY_RANK(rank, lowrank_project_kernel, grid, block, as_stream(stream), g, e, q, msg1, plan_dev);
 }
 
@@ -495,6 +382,7 @@ CHOCO_API int choco_lowrank_orthogonalize(float* msg1, int64_t msg1_len, const i
   CHOCO_REQUIRE(aligned4(msg1), "msg1 must be 4-byte aligned");
   if (plan_host[kLrNcomp] == 0) return CHOCO_OK;
   const dim3 grid((unsigned)plan_host[kLrNcomp]), block(kLrThreads);
+  if (lr_rank_hi(rank)) return LR_ORTH_HI(rank, grid, block, as_stream(stream), msg1, plan_dev);
   return LR_BY_RANK(rank, lowrank_orth_kernel, grid, block, as_stream(stream), msg1, plan_dev);
 }
 
@@ -512,7 +400,16 @@ CHOCO_API int choco_lowrank_backproject(const float* e, const float* msg1, int64
   const hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)plan_host[kLrNBp]), block(kLrThreads);
   float* wsf = reinterpret_cast<float*>(ws);
-  CHOCO_TRY(LR_BY_RANK(rank, lowrank_backproject_kernel, grid, block, st, e, msg1, msg2, wsf, plan_dev));
+#ifdef CHOCO_LOWRANK_VECTOR8
+  if (rank == 8)
+    CHOCO_TRY(CHOCO_LAUNCH("lowrank_backproject_kernel", "lowrank_backproject_kernel", lowrank_backproject_kernel<8>, grid,
+                           block, st, e, msg1, msg2, wsf, plan_dev));
+  else
+#endif
+  if (lr_rank_hi(rank))
+    CHOCO_TRY(lr_hi_backproject(rank, grid, st, e, msg1, msg2, wsf, plan_dev));
+  else
+    CHOCO_TRY(LR_BY_RANK(rank, lowrank_backproject_kernel, grid, block, st, e, msg1, msg2, wsf, plan_dev));
   if (plan_host[kLrNSum] == 0) return CHOCO_OK;
   return CHOCO_LAUNCH("lowrank_slabsum_kernel", "lowrank_slabsum_kernel", lowrank_slabsum_kernel,
                       dim3((unsigned)plan_host[kLrNSum]), block, st, (const float*)wsf, msg2, plan_dev);
@@ -530,6 +427,9 @@ CHOCO_API int choco_lowrank_decode(float* e, const float* msg1, int64_t msg1_len
   CHOCO_REQUIRE(aligned16(e) && aligned16(flat_out), "e and flat_out must be 16-byte aligned");
   CHOCO_REQUIRE(aligned4(msg1) && aligned4(msg2), "msg1 and msg2 must be 4-byte aligned");
   const dim3 grid((unsigned)plan_host[kLrNRow]), block(kLrThreads);
+  LR_VECTOR8(rank, lowrank_decode_kernel, grid, block, as_stream(stream), e, msg1, msg2, flat_out, (float)divisor, plan_dev);
+  if (lr_rank_hi(rank))
+    return lr_hi_decode(rank, grid, as_stream(stream), e, msg1, msg2, flat_out, (float)divisor, plan_dev);
   return LR_BY_RANK(rank, lowrank_decode_kernel, grid, block, as_stream(stream), e, msg1, msg2, flat_out,
                     (float)divisor, plan_dev);
 }

@@ -22,8 +22,9 @@ One step (g: the flat fp32 gradient; W: the divisor, the world size):
   6. decode         compressed: sum = P^ Q^T, e = M - sum / W;  uncompressed: sum = the tail
   7. the plain SGD update from the flat summed gradient (ParamSgdPlan.run_flatgrad, unchanged)
 
-`fused_step(...)` runs it as codec.LowRankPlan's four launches (csrc/lowrank.hip) between the
-gradient pack and the flat-gradient update.  `step_loop(...)` is the same step as one torch op
+`fused_step(...)` runs it as codec.LowRankPlan's four launches (csrc/lowrank.hip at rank 1, 2 and
+4; csrc/lowrank_mfma.hip's matrix-instruction kernels at rank 8, 16 and 32) between the gradient
+pack and the flat-gradient update.  Any other rank raises.  `step_loop(...)` is the same step as one torch op
 per line and tensor, in the tensors' own precision (fp64 models stay fp64): the readable
 contract, and the path for CPU tensors and anything the batched kernels do not take.
 """
@@ -154,7 +155,8 @@ def fused_step(compressor, param_groups, param_names, state, distributed=True, w
     """One PowerSGD step end to end: utils.step_entries, ONE pack launch per chunk of the
     gradients into a flat fp32 buffer (16-bit gradients are widened), lowrank_project_kernel,
     the all-reduce of message 1, lowrank_orth_kernel, lowrank_backproject_kernel (and the
-    slab-sum launch), the all-reduce of message 2, lowrank_decode_kernel, and the flat-gradient
+    slab-sum launch), the all-reduce of message 2, lowrank_decode_kernel (at rank 8, 16 and 32
+    the lowrank_*_mfma_kernel of project, back-project and decode), and the flat-gradient
     SGD update (ParamSgdPlan.run_flatgrad, which divides by the same divisor and narrows).
     Returns n_bits = 32 * (msg1_len + msg2_len).  write_grads: p.grad receives the decoded
     average.  Tensors the kernels do not take run step_loop.

@@ -1241,7 +1241,9 @@ int choco_params_sign_step(void* const* params, const int64_t* lens, const int32
  * for a tensor of fewer than two dimensions (lens[t] must be whole rows).  With cols = lens[t] /
  * rows[t], tensor t is COMPRESSED iff rows[t] > 0, cols > 0 and rows * cols > rank * (rows +
  * cols); it is then the row-major matrix M_t (rows x cols) at its flat offset.  Every other
- * tensor is uncompressed.  rank is 1, 2 or 4.
+ * tensor is uncompressed.  rank is 1, 2, 4, 8, 16 or 32: ranks 1, 2 and 4 run on the vector ALUs,
+ * ranks 8, 16 and 32 run project, back-project and decode on the fp32 matrix instruction
+ * (v_mfma_f32_16x16x4_f32; the inputs stay fp32), the kernels named "*_mfma_kernel" below.
  *   message 1 = [P_0 | P_1 | .. | the uncompressed tensors' elements, in layout order],
  *               P_t rows x rank row-major, compressed tensors in layout order
  *   message 2 = [Q_0 | Q_1 | ..], Q_t cols x rank row-major
@@ -1262,7 +1264,8 @@ int choco_params_sign_step(void* const* params, const int64_t* lens, const int32
  *   choco_lowrank_project        M = fl(g + e), one rounding, stored over e; P_t = M_t Q_t with
  *                                q = message 2's layout; the uncompressed tensors' g into the
  *                                tail (their e is neither read nor written).
- *                                One launch of "lowrank_project_kernel".
+ *                                One launch of "lowrank_project_kernel" (rank >= 8:
+ *                                "lowrank_project_mfma_kernel").
  *   (all-reduce message 1)
  *   choco_lowrank_orthogonalize  modified Gram-Schmidt in place on the columns of every P_t in
  *                                column order: col /= (||col||_2 + 1e-8), later -= (col^T later)
@@ -1270,17 +1273,20 @@ int choco_params_sign_step(void* const* params, const int64_t* lens, const int32
  *                                quotient and the difference are formed in fp64 and rounded
  *                                once.  A zero column stays zero.  "lowrank_orth_kernel".
  *   choco_lowrank_backproject    Q_t = M_t^T P_t (M from e) into message 2.
- *                                "lowrank_backproject_kernel", and one launch of
+ *                                "lowrank_backproject_kernel" (rank >= 8:
+ *                                "lowrank_backproject_mfma_kernel"), and one launch of
  *                                "lowrank_slabsum_kernel" where a matrix has more than 256 rows.
  *   (all-reduce message 2)
  *   choco_lowrank_decode         compressed: flat_out = P_t Q_t^T, e = fl(M - fl(flat_out /
  *                                (float)divisor)), a true division; uncompressed: flat_out =
- *                                the tail's elements, e untouched.  "lowrank_decode_kernel".
- * Every sum runs in an order fixed by the table and the rank (fmaf accumulation, no atomics):
+ *                                the tail's elements, e untouched.  "lowrank_decode_kernel"
+ *                                (rank >= 8: "lowrank_decode_mfma_kernel").
+ * Every sum runs in an order fixed by the table and the rank (fmaf accumulation, or the matrix
+ * instruction's own sum over its four k at rank >= 8; no atomics):
  * the same inputs give the same bits.  Everything runs on `stream`; nothing is allocated.
  *
  * Every call checks its arguments before the first launch without a HIP call -- null
- * pointers, a rank outside {1, 2, 4}, a table that is not one or was built for another n or
+ * pointers, a rank outside {1, 2, 4, 8, 16, 32}, a table that is not one or was built for another n or
  * rank, message lengths that are not the table's, misaligned pointers, a workspace too small,
  * divisor <= 0 -- and a bad call returns CHOCO_ERR_INVALID and launches nothing. */
 int64_t choco_lowrank_plan_len(const int64_t* rows, const int64_t* lens, int32_t nseg, int32_t rank);

@@ -18,6 +18,9 @@ VARIANTS = {
     # the packed-sign step with wide accesses only at 16-byte aligned run starts (element
     # accesses elsewhere): CHOCO_CODEC_LIB=... tools/sign_vote_time.py
     "signstep_aligned": ["CHOCO_SIGNSTEP_ALIGNED=1"],
+    # rank-8 PowerSGD on the vector templates of lowrank.hip instead of the matrix-instruction
+    # kernels: CHOCO_CODEC_LIB=... tools/powersgd_time.py --ranks 8
+    "lowrank_vector8": ["CHOCO_LOWRANK_VECTOR8=1"],
 }
 
 

@@ -1,17 +1,18 @@
-"""Time of the PowerSGD kernels (csrc/lowrank.hip) and of the whole step, against the plain
+"""Time of the PowerSGD kernels (csrc/lowrank.hip, csrc/lowrank_mfma.hip) and of the whole step, against the plain
 all-reduce SGD step on the same layout in the same process and against each stage's compulsory
 bytes at 8 TB/s.
 
-    python tools/powersgd_time.py [--out profiles/powersgd_time.json] [--iters 20] [--warmup 5] [--reps 5]
+    python tools/powersgd_time.py [--out profiles/powersgd_time.json] [--iters 20] [--warmup 5] [--reps 5] [--ranks 8,16]
 
-One JSON line per rank r = 1, 2, 4 on ResNet-50's layout (161 tensors, 25,557,032 fp32 elements,
+One JSON line per rank of codec.LOWRANK_RANKS (or --ranks) on ResNet-50's layout (161 tensors, 25,557,032 fp32 elements,
 each parameter its own allocation; the shapes are written out below and checked against
 tests/golden/layouts.json), with a loopback aggregator (the all-reduces return their buffer):
   step_us / allreduce_us   device time per call of powersgd.fused_step and of
              utils.allreduce_sgd_step between two events (`iters` calls a window after `warmup`,
              the two alternating window by window; the median over `reps` windows, min and max)
   kernel_us_*    the dispatch-attached time of each kernel's launches alone (the library's
-             profile hooks), in a window of its own
+             profile hooks), in a window of its own; ranks 8, 16 and 32 run the *_mfma_kernel
+             of a stage and are reported under the stage's one name
   bytes_* / floor_us_* / tbps_*   the stage's compulsory traffic (project: 12 B per compressed
              element, read g and e, write M; back-project: 4 B; decode: 12 B, read M, write the
              sum and e; the uncompressed tensors' copy: 8 B per element in project and decode),
@@ -78,6 +79,8 @@ def measure(shapes, r, iters, warmup, reps):
     total = 0.0
     for kernel in list(STAGES) + OTHERS:
         t, launches = P.kernel_time(ways["step"], kernel, iters)
+        if not t and kernel in STAGES:  # the matrix-instruction kernel of the stage
+            t, launches = P.kernel_time(ways["step"], kernel.replace("_kernel", "_mfma_kernel"), iters)
         if not t:
             continue
         total += t
@@ -100,13 +103,14 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--ranks", default=",".join(str(r) for r in codec.LOWRANK_RANKS))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "the timer needs a ROCm device"
     shapes = resnet50_shapes()
     with open(os.path.join(ROOT, "tests", "golden", "layouts.json")) as f:
         assert [int(torch.Size(s).numel()) for s in shapes] == json.load(f)["resnet50_imagenet"]
     rows = []
-    for r in codec.LOWRANK_RANKS:
+    for r in (int(x) for x in args.ranks.split(",")):
         rows.append(measure(shapes, r, args.iters, args.warmup, args.reps))
         print(json.dumps(rows[-1]), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
