@@ -183,6 +183,8 @@ SIGNATURES = {
     "choco_lowrank_workspace_size": (_c_sz, [_p_i64]),
     "choco_lowrank_project": (_c_i32, [_vp, _vp, _vp, _vp, _c_i64, _c_i64, _p_i64, _vp, _c_i64, _c_i32, _vp]),
     "choco_lowrank_orthogonalize": (_c_i32, [_vp, _c_i64, _p_i64, _vp, _c_i64, _c_i32, _vp]),
+    "choco_lowrank_orth_workspace_size": (_c_sz, [_p_i64]),
+    "choco_lowrank_orthogonalize_cholqr": (_c_i32, [_vp, _c_i64, _vp, _c_sz, _p_i64, _vp, _c_i64, _c_i32, _vp]),
     "choco_lowrank_backproject": (_c_i32, [_vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_sz, _p_i64, _vp, _c_i64, _c_i32,
                                            _vp]),
     "choco_lowrank_decode": (_c_i32, [_vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_f64, _p_i64, _vp, _c_i64, _c_i32, _vp]),

@@ -9,6 +9,7 @@ from . import _lib
 from . import codec as _c
 
 LOWRANK_RANKS = (1, 2, 4, 8, 16, 32)
+LOWRANK_ORTH_METHODS = ("mgs", "cholqr")
 _HDR = 16  # header words of the table; then one {compressed, P / tail offset, Q offset, flat offset} row per tensor
 
 
@@ -53,6 +54,7 @@ class LowRankPlan:
         self.p_off = [r[1] for r in rows]
         self.q_off = [r[2] for r in rows]
         self.ws_bytes = int(L.choco_lowrank_workspace_size(self.plan_host))
+        self.orth_ws_bytes = int(L.choco_lowrank_orth_workspace_size(self.plan_host))  # 0 under rank 8
         self.plan_dev = torch.tensor(table, dtype=torch.int64, device=self.device)
 
     def _flat(self, t, numel, name):
@@ -72,10 +74,20 @@ class LowRankPlan:
                                                   self._flat(msg1, self.msg1_len, "msg1"), self.msg1_len,
                                                   self.msg2_len, *self._tail()), "choco_lowrank_project")
 
-    def orthogonalize(self, msg1):
-        """Modified Gram-Schmidt in place on every (summed) P of msg1."""
-        _lib.check(_c.lib().choco_lowrank_orthogonalize(self._flat(msg1, self.msg1_len, "msg1"), self.msg1_len,
-                                                        *self._tail()), "choco_lowrank_orthogonalize")
+    def orthogonalize(self, msg1, method="mgs"):
+        """Orthogonalise every (summed) P of msg1 in place.  "mgs": modified Gram-Schmidt, one workgroup a
+        matrix.  "cholqr" (ranks 8, 16 and 32): Cholesky-QR on the fp64 matrix instruction, three launches
+        over every 256-row block (csrc/lowrank_cholqr.hip), with a workspace of its own."""
+        if method == "mgs":
+            _lib.check(_c.lib().choco_lowrank_orthogonalize(self._flat(msg1, self.msg1_len, "msg1"), self.msg1_len,
+                                                            *self._tail()), "choco_lowrank_orthogonalize")
+        elif method == "cholqr":
+            ws = _c.workspace(self.plan_dev.device, "lowrank_orth", self.orth_ws_bytes)
+            _lib.check(_c.lib().choco_lowrank_orthogonalize_cholqr(self._flat(msg1, self.msg1_len, "msg1"), self.msg1_len,
+                                                                   _c._ptr(ws), ws.numel(), *self._tail()),
+                       "choco_lowrank_orthogonalize_cholqr")
+        else:
+            raise RuntimeError(f"LowRankPlan.orthogonalize: method must be one of {LOWRANK_ORTH_METHODS}, got {method!r}")
 
     def backproject(self, e, msg1, msg2):
         """Q = M^T P^ into msg2 (M: what project left in e)."""

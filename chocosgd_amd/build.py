@@ -33,10 +33,11 @@ HIPCC_FLAGS = [
 # accumulator at a time, in the order the contract fixes.  lowrank_mfma.hip: its M = g + e and
 # e = M - out / W lines sit between 16-byte loads and stores as four-wide expressions, which the
 # compiler would otherwise pair up; they stay the same plain v_add_f32 / v_sub_f32 as lowrank.hip's,
-# so the error memory is produced by the same instructions at every rank.
+# so the error memory is produced by the same instructions at every rank.  lowrank_cholqr.hip is
+# fp64 throughout but for its one narrowing store; it is built like the rest of the family.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"signstep.hip": NO_PACKED_FP32, "vote.hip": NO_PACKED_FP32, "lowrank.hip": NO_PACKED_FP32,
-               "lowrank_mfma.hip": NO_PACKED_FP32}
+               "lowrank_mfma.hip": NO_PACKED_FP32, "lowrank_cholqr.hip": NO_PACKED_FP32}
 
 
 def _hipcc():

@@ -1,7 +1,7 @@
 // Shared device/host helpers for the CHOCO codec (gfx950 / CDNA4, wave64).
 //
-// Everything here is memory-bound per-element work: no MFMA (the one exception in the library
-// is lowrank_mfma.hip).  Conventions used
+// Everything here is memory-bound per-element work: no MFMA (the exceptions in the library
+// are lowrank_mfma.hip and lowrank_cholqr.hip).  Conventions used
 // by every kernel in this library:
 //   * `key(v)` = IEEE-754 bits of |v| (sign bit cleared).  For non-NaN floats the
 //     unsigned order of keys equals the order of magnitudes, so top-k by |v|

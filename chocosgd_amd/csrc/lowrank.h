@@ -1,6 +1,7 @@
 // What the two low-rank kernel families share (lowrank.hip: ranks 1, 2 and 4 on the vector ALUs;
 // lowrank_mfma.hip: ranks 8, 16 and 32 on the fp32 matrix instruction): the tile table's layout,
 // its builder, the check every launch makes first, and the high-rank launches' declarations.
+// lowrank_cholqr.hip (Cholesky-QR orthogonalisation at ranks 8, 16 and 32) reads the same table.
 #pragma once
 
 #include "choco_common.h"

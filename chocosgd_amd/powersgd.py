@@ -5,7 +5,7 @@ all-reduce path: the one compressor of this family whose messages can be SUMMED,
 A tensor of at least two dimensions with rows * cols > r * (rows + cols) (rows = shape[0], cols
 = numel / rows) is compressed: it is the row-major matrix M (rows x cols) of the flat gradient
 buffer.  Every other tensor -- vectors, scalars, empty tensors, matrices too small to save
-anything -- travels as it is.  `PowerSGDCompressor(rank, aggregator, seed=0)` owns the state of one
+anything -- travels as it is.  `PowerSGDCompressor(rank, aggregator, seed=0, orthogonalize="mgs")` owns the state of one
 worker: the flat error memory `e` (zero at first) and, per compressed tensor, `Q` (cols x r), drawn
 with torch.randn from a CPU generator seeded with `seed`, in layout order, so every rank starts
 from the same Q.
@@ -16,6 +16,9 @@ One step (g: the flat fp32 gradient; W: the divisor, the world size):
   2. all-reduce (sum) message 1
   3. orthogonalise  modified Gram-Schmidt on the columns of every summed P, in column order:
                     col /= (||col|| + 1e-8), later -= (col . later) col
+                    (orthogonalize="cholqr", ranks 8, 16 and 32: the same P^ by Cholesky-QR --
+                    G = P^T P in fp64, G = L L^T with a pivot rule, P^ = P L^-T D, one rounding;
+                    `orthogonalize_cholqr_loop`)
   4. back-project   Q = M^T P^;  message 2 = [Q_0 | Q_1 | ..]
   5. all-reduce (sum) message 2; the summed Q is what the next step starts from (step 3
      normalises, so it is not divided)
@@ -48,11 +51,17 @@ def is_compressed(shape, rank):
 
 
 class PowerSGDCompressor(object):
-    def __init__(self, rank, aggregator, seed=0):
+    def __init__(self, rank, aggregator, seed=0, orthogonalize="mgs"):
         if rank not in codec.LOWRANK_RANKS:
             raise RuntimeError(f"PowerSGDCompressor: rank must be one of {codec.LOWRANK_RANKS}, got {rank} "
                                "(DESIGN.md section 8)")
-        self.rank, self.aggregator_fn, self.seed = rank, aggregator, seed
+        if orthogonalize not in codec.LOWRANK_ORTH_METHODS:
+            raise RuntimeError(f"PowerSGDCompressor: orthogonalize must be one of {codec.LOWRANK_ORTH_METHODS}, got "
+                               f"{orthogonalize!r}")
+        if orthogonalize == "cholqr" and rank < 8:
+            raise RuntimeError(f"PowerSGDCompressor: orthogonalize=\"cholqr\" is built for ranks 8, 16 and 32, got {rank}; "
+                               "ranks 1, 2 and 4 keep modified Gram-Schmidt (DESIGN.md section 8)")
+        self.rank, self.aggregator_fn, self.seed, self.orthogonalize = rank, aggregator, seed, orthogonalize
         self.shapes = self.e = self.q = self.plan = None
 
     def state(self, shapes, device, dtype=torch.float32):
@@ -86,6 +95,28 @@ def orthogonalize_loop(P):
     return P
 
 
+TAU = 2.0 ** -30  # a Cholesky pivot at or under TAU G_kk drops its column
+
+
+def orthogonalize_cholqr_loop(P):
+    """Cholesky-QR in place on the columns of P: the P^ of orthogonalize_loop (the thin QR factorisation
+    with a positive diagonal is unique) from an fp64 Gram matrix, whatever P's dtype, and one cast."""
+    P64, r = P.double(), P.shape[1]
+    G = P64.t() @ P64
+    L = torch.zeros_like(G)
+    for k in range(r):
+        d = G[k, k] - (L[k, :k] * L[k, :k]).sum()
+        if d <= TAU * G[k, k]:  # nothing new in this column (a zero column too): dropped
+            continue
+        L[k, k] = d.sqrt()
+        L[k + 1:, k] = (G[k + 1:, k] - L[k + 1:, :k] @ L[k, :k]) / L[k, k]
+    keep = (L.diagonal() > 0).nonzero().reshape(-1)
+    T = torch.zeros_like(G)  # T = L^-T D over the kept columns, D_kk = L_kk / (L_kk + EPS): Gram-Schmidt's divisor
+    T[keep[:, None], keep] = torch.linalg.inv(L[keep][:, keep]).t() * (L.diagonal() / (L.diagonal() + EPS))[keep]
+    P.copy_((P64 @ T).to(P.dtype))
+    return P
+
+
 def step_loop(compressor, param_groups, param_names, state, distributed=True, write_grads=True):
     """The PowerSGD step as one torch op per line and tensor.  Returns n_bits of the two messages."""
     entries = utils.step_entries(param_groups, param_names, "powersgd.step_loop", need_grads=True)
@@ -113,8 +144,9 @@ def step_loop(compressor, param_groups, param_names, state, distributed=True, wr
     msg1 = agg._agg(msg1, op="sum", distributed=distributed)
     # 3. orthogonalise, 4. back-project
     po, Phs, Qs = 0, [], []
+    orth = orthogonalize_cholqr_loop if compressor.orthogonalize == "cholqr" else orthogonalize_loop
     for M in Ms:
-        Phs.append(orthogonalize_loop(msg1[po:po + M.shape[0] * r].view(M.shape[0], r).clone()))
+        Phs.append(orth(msg1[po:po + M.shape[0] * r].view(M.shape[0], r).clone()))
         Qs.append(M.t() @ Phs[-1])
         po += M.shape[0] * r
     msg2 = torch.cat([Q.reshape(-1) for Q in Qs] + [torch.empty(0, dtype=dt, device=msg1.device)])
@@ -154,7 +186,8 @@ def fused_step(compressor, param_groups, param_names, state, distributed=True, w
                clip_norm=None, loss_scale=None, rounding=None):
     """One PowerSGD step end to end: utils.step_entries, ONE pack launch per chunk of the
     gradients into a flat fp32 buffer (16-bit gradients are widened), lowrank_project_kernel,
-    the all-reduce of message 1, lowrank_orth_kernel, lowrank_backproject_kernel (and the
+    the all-reduce of message 1, lowrank_orth_kernel (the compressor's orthogonalize="cholqr":
+    lowrank_gram_kernel, lowrank_chol_kernel, lowrank_orthapply_kernel), lowrank_backproject_kernel (and the
     slab-sum launch), the all-reduce of message 2, lowrank_decode_kernel (at rank 8, 16 and 32
     the lowrank_*_mfma_kernel of project, back-project and decode), and the flat-gradient
     SGD update (ParamSgdPlan.run_flatgrad, which divides by the same divisor and narrows).
@@ -181,7 +214,7 @@ def fused_step(compressor, param_groups, param_names, state, distributed=True, w
     msg1 = torch.empty(lr.msg1_len, dtype=torch.float32, device=plan.device)
     lr.project(flat, st.e, st.q, msg1)
     msg1 = agg._agg(msg1, op="sum", distributed=distributed)
-    lr.orthogonalize(msg1)
+    lr.orthogonalize(msg1, compressor.orthogonalize)
     msg2 = torch.empty(lr.msg2_len, dtype=torch.float32, device=plan.device)
     lr.backproject(st.e, msg1, msg2)
     msg2 = st.q = agg._agg(msg2, op="sum", distributed=distributed)

@@ -1272,7 +1272,26 @@ int choco_params_sign_step(void* const* params, const int64_t* lens, const int32
  *                                col; norms and dots are fp64 sums in a fixed order, the
  *                                quotient and the difference are formed in fp64 and rounded
  *                                once.  A zero column stays zero.  "lowrank_orth_kernel".
- *   choco_lowrank_backproject    Q_t = M_t^T P_t (M from e) into message 2.
+ *   choco_lowrank_orthogonalize_cholqr   the same P^ by Cholesky-QR (the thin QR factorisation with a
+ *                                positive diagonal is unique; only the roundings differ), ranks 8,
+ *                                16 and 32, in place of the call above where the caller opts in:
+ *                                1. G = P^T P, products and sums in fp64, one partial per block
+ *                                   of 256 rows ("lowrank_gram_kernel", v_mfma_f64_16x16x4_f64),
+ *                                   the partials added in ascending block order;
+ *                                2. G = L L^T in column order with d_k = G_kk - sum_{j<k} L_kj^2;
+ *                                   d_k <= 2^-30 G_kk drops column k (its output is zero and it
+ *                                   adds nothing to later columns; a zero column is the case G_kk =
+ *                                   0), else L_kk = sqrt(d_k); T = L^-T D, upper triangular, D_kk =
+ *                                   L_kk / (L_kk + 1e-8), 0 for a dropped column
+ *                                   ("lowrank_chol_kernel", one workgroup a matrix);
+ *                                3. P^ = P T in fp64, each element rounded to fp32 once, in place
+ *                                   ("lowrank_orthapply_kernel", the same instruction).
+ *                                One launch each; the tail is not touched; a zero matrix stays zero.
+ *                                ws: choco_lowrank_orth_workspace_size(table) bytes (0 for a table
+ *                                of rank 1, 2 or 4), the block partials and T; it holds nothing
+ *                                between calls.  msg1 and ws 16-byte aligned.  Refused, each by
+ *                                name: rank 1, 2 or 4, a null msg1 or ws, a short workspace.
+ *   choco_lowrank_backproject   Q_t = M_t^T P_t (M from e) into message 2.
  *                                "lowrank_backproject_kernel" (rank >= 8:
  *                                "lowrank_backproject_mfma_kernel"), and one launch of
  *                                "lowrank_slabsum_kernel" where a matrix has more than 256 rows.
@@ -1297,6 +1316,10 @@ int choco_lowrank_project(const float* g, float* e, const float* q, float* msg1,
                           int32_t rank, void* stream);
 int choco_lowrank_orthogonalize(float* msg1, int64_t msg1_len, const int64_t* plan_host, const int64_t* plan_dev,
                                 int64_t n, int32_t rank, void* stream);
+size_t choco_lowrank_orth_workspace_size(const int64_t* plan_host);
+int choco_lowrank_orthogonalize_cholqr(float* msg1, int64_t msg1_len, void* ws, size_t ws_bytes,
+                                       const int64_t* plan_host, const int64_t* plan_dev, int64_t n, int32_t rank,
+                                       void* stream);
 int choco_lowrank_backproject(const float* e, const float* msg1, int64_t msg1_len, float* msg2, int64_t msg2_len,
                               void* ws, size_t ws_bytes, const int64_t* plan_host, const int64_t* plan_dev,
                               int64_t n, int32_t rank, void* stream);

@@ -3,6 +3,7 @@ all-reduce SGD step on the same layout in the same process and against each stag
 bytes at 8 TB/s.
 
     python tools/powersgd_time.py [--out profiles/powersgd_time.json] [--iters 20] [--warmup 5] [--reps 5] [--ranks 8,16]
+                                  [--orth {mgs,cholqr}]
 
 One JSON line per rank of codec.LOWRANK_RANKS (or --ranks) on ResNet-50's layout (161 tensors, 25,557,032 fp32 elements,
 each parameter its own allocation; the shapes are written out below and checked against
@@ -17,6 +18,10 @@ tests/golden/layouts.json), with a loopback aggregator (the all-reduces return t
              element, read g and e, write M; back-project: 4 B; decode: 12 B, read M, write the
              sum and e; the uncompressed tensors' copy: 8 B per element in project and decode),
              the time it takes at 8 TB/s, and the rate the kernel reached
+  --orth cholqr  the step orthogonalises by Cholesky-QR (csrc/lowrank_cholqr.hip; ranks 8, 16 and 32): its three
+             launches are timed one by one and summed as kernel_us_cholqr, and the modified Gram-Schmidt step of a
+             second compressor on a model of its own runs in the same process, its windows alternating with the
+             others: step_mgs_us and kernel_us_mgs (lowrank_orth_kernel in that step)
   msg_elements   what is sent (message 1 + message 2) against the layout's elements
 Needs a ROCm device; there is no fall-back.
 """
@@ -38,6 +43,7 @@ from chocosgd_amd import codec, powersgd, utils  # noqa: E402
 PEAK_TBPS = 8.0
 STAGES = {"lowrank_project_kernel": 12, "lowrank_backproject_kernel": 4, "lowrank_decode_kernel": 12}
 OTHERS = ["lowrank_orth_kernel", "lowrank_slabsum_kernel", "param_pack_kernel", "param_sgd_flatgrad_kernel"]
+CHOLQR = ["lowrank_gram_kernel", "lowrank_chol_kernel", "lowrank_orthapply_kernel"]
 
 
 def resnet50_shapes():
@@ -53,19 +59,23 @@ def resnet50_shapes():
     return s + [(1000, 2048), (1000,)]
 
 
-def measure(shapes, r, iters, warmup, reps):
+def measure(shapes, r, iters, warmup, reps, orth="mgs"):
     agg = P._Loopback()
     _, ga, na = P.model(shapes, torch.float32)
     _, gb, nb = P.model(shapes, torch.float32)
     sa, sb = collections.defaultdict(dict), collections.defaultdict(dict)
-    comp = powersgd.PowerSGDCompressor(r, agg)
+    comp = powersgd.PowerSGDCompressor(r, agg, orthogonalize=orth)
     ways = {"step": lambda: powersgd.fused_step(comp, ga, na, sa),
             "allreduce": lambda: utils.allreduce_sgd_step(gb, nb, sb, agg)}
+    if orth == "cholqr":  # the parent's method beside it, window by window
+        _, gc, nc = P.model(shapes, torch.float32)
+        sc, comp_mgs = collections.defaultdict(dict), powersgd.PowerSGDCompressor(r, agg)
+        ways["step_mgs"] = lambda: powersgd.fused_step(comp_mgs, gc, nc, sc)
     for fn in ways.values():
         P.events(fn, warmup)
     plan = comp.plan
     n_comp = sum(m for m, c in zip(plan.lens, plan.compressed) if c)
-    row = {"layout": "resnet50_fp32", "rank": r, "tensors": len(shapes), "elements": plan.n,
+    row = {"layout": "resnet50_fp32", "rank": r, "orth": orth, "tensors": len(shapes), "elements": plan.n,
            "compressed_tensors": sum(plan.compressed), "compressed_elements": n_comp,
            "msg_elements": plan.msg1_len + plan.msg2_len, "iters": iters, "warmup": warmup, "reps": reps}
     runs = {tag: [] for tag in ways}
@@ -77,7 +87,7 @@ def measure(shapes, r, iters, warmup, reps):
         row[f"{tag}_us_min_max"] = [round(min(runs[tag]), 1), round(max(runs[tag]), 1)]
     row["step_vs_allreduce"] = round(row["step_us"] / row["allreduce_us"], 2)
     total = 0.0
-    for kernel in list(STAGES) + OTHERS:
+    for kernel in list(STAGES) + OTHERS + (CHOLQR if orth == "cholqr" else []):
         t, launches = P.kernel_time(ways["step"], kernel, iters)
         if not t and kernel in STAGES:  # the matrix-instruction kernel of the stage
             t, launches = P.kernel_time(ways["step"], kernel.replace("_kernel", "_mfma_kernel"), iters)
@@ -90,6 +100,10 @@ def measure(shapes, r, iters, warmup, reps):
             row[f"bytes_{kernel}"], row[f"floor_us_{kernel}"] = nbytes, round(nbytes / PEAK_TBPS / 1e6, 2)
             row[f"tbps_{kernel}"] = round(nbytes / t / 1e6, 3)
     row["kernel_us_step"] = round(total, 2)
+    if orth == "cholqr":
+        row["kernel_us_cholqr"] = round(sum(row[f"kernel_us_{k}"] for k in CHOLQR), 2)
+        row["kernel_us_mgs"] = round(P.kernel_time(ways["step_mgs"], "lowrank_orth_kernel", iters)[0], 2)
+        row["cholqr_vs_mgs"] = round(row["kernel_us_cholqr"] / row["kernel_us_mgs"], 3)
     t, _ = P.kernel_time(ways["allreduce"], "param_sgd_flatgrad_kernel", iters)
     t2, _ = P.kernel_time(ways["allreduce"], "param_pack_kernel", iters)
     if t and t2:
@@ -104,6 +118,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--ranks", default=",".join(str(r) for r in codec.LOWRANK_RANKS))
+    ap.add_argument("--orth", choices=codec.LOWRANK_ORTH_METHODS, default="mgs")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "the timer needs a ROCm device"
     shapes = resnet50_shapes()
@@ -111,7 +126,7 @@ def main():
         assert [int(torch.Size(s).numel()) for s in shapes] == json.load(f)["resnet50_imagenet"]
     rows = []
     for r in (int(x) for x in args.ranks.split(",")):
-        rows.append(measure(shapes, r, args.iters, args.warmup, args.reps))
+        rows.append(measure(shapes, r, args.iters, args.warmup, args.reps, args.orth))
         print(json.dumps(rows[-1]), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
