@@ -103,3 +103,74 @@ class LowRankPlan:
                                                  self.msg1_len, self._flat(msg2, self.msg2_len, "msg2"), self.msg2_len,
                                                  self._flat(flat_out, self.n, "flat_out"), float(divisor),
                                                  *self._tail()), "choco_lowrank_decode")
+
+
+GOSSIP_MAX_WIDTH = 8  # n_edges * rank the batched PowerGossip kernels serve
+
+
+class LowRankGossipPlan:
+    """PowerGossip's five launches for a worker with `n_edges` neighbours (include/choco_codec.h, "low-rank
+    gossip"; csrc/lowrank_gossip.hip): every pass over the flat parameters x serves all edges.  It owns the
+    LowRankPlan table of the layout at `rank` (.table: lengths and offsets).  Per-edge buffers are flat,
+    edge-major: q, dq, msg2 hold n_edges * msg2_len elements, msg1 n_edges * msg1_len, phat n_edges * p_total.
+    lo_mask: bit e set where this worker is the low end of edge e.  n_edges * rank > 8 raises."""
+
+    def __init__(self, shapes, rank, n_edges, device):
+        self.table = LowRankPlan(shapes, rank, device)
+        self.rank, self.n_edges = self.table.rank, int(n_edges)
+        if self.rank > 4 or not 1 <= self.n_edges or self.n_edges * self.rank > GOSSIP_MAX_WIDTH:
+            raise RuntimeError(f"LowRankGossipPlan: n_edges * rank must be in [1, {GOSSIP_MAX_WIDTH}] at rank 1, 2 or 4, got "
+                               f"{n_edges} edges at rank {rank} (DESIGN.md section 8)")
+        t = self.table
+        self.n, self.msg1_len, self.msg2_len, self.p_total = t.n, t.msg1_len, t.msg2_len, t.tail_off
+        self.ws_bytes = int(_c.lib().choco_lowrank_gossip_workspace_size(t.plan_host, self.n_edges))
+
+    def _e(self, t, per_edge, name):
+        return self.table._flat(t, self.n_edges * per_edge, name)
+
+    def _tail(self):
+        t = self.table
+        return t.plan_host, _c._ptr(t.plan_dev), t.n, t.rank, self.n_edges, _c._stream(t.plan_dev.device)
+
+    def project(self, x, q, msg1):
+        """msg1[e] = [X Q_e | the uncompressed tensors of x] for every edge; x is read once."""
+        _lib.check(_c.lib().choco_lowrank_gossip_project(self.table._flat(x, self.n, "x"), self._e(q, self.msg2_len, "q"),
+                                                         self._e(msg1, self.msg1_len, "msg1"), self.msg1_len,
+                                                         self.msg2_len, *self._tail()), "choco_lowrank_gossip_project")
+
+    def orthogonalize(self, msg1_own, msg1_recv, phat, lo_mask):
+        """phat[e] = Gram-Schmidt of P_e(lo end) - P_e(hi end)."""
+        _lib.check(_c.lib().choco_lowrank_gossip_orthogonalize(self._e(msg1_own, self.msg1_len, "msg1_own"),
+                                                               self._e(msg1_recv, self.msg1_len, "msg1_recv"),
+                                                               self.msg1_len, self._e(phat, self.p_total, "phat"),
+                                                               int(lo_mask), *self._tail()),
+                   "choco_lowrank_gossip_orthogonalize")
+
+    def backproject(self, x, phat, msg2):
+        """msg2[e] = X^T phat[e] for every edge; x is read once."""
+        ws = _c.workspace(self.table.plan_dev.device, "lowrank_gossip", self.ws_bytes)
+        _lib.check(_c.lib().choco_lowrank_gossip_backproject(self.table._flat(x, self.n, "x"),
+                                                             self._e(phat, self.p_total, "phat"), self.msg1_len,
+                                                             self._e(msg2, self.msg2_len, "msg2"), self.msg2_len,
+                                                             _c._ptr(ws), ws.numel(), *self._tail()),
+                   "choco_lowrank_gossip_backproject")
+
+    def diff(self, msg2_own, msg2_recv, q, dq, lo_mask):
+        """dq[e] = Q'_e(lo end) - Q'_e(hi end); q[e] takes it, matrix by matrix, unless it is all zeros."""
+        _lib.check(_c.lib().choco_lowrank_gossip_diff(self._e(msg2_own, self.msg2_len, "msg2_own"),
+                                                      self._e(msg2_recv, self.msg2_len, "msg2_recv"), self.msg1_len,
+                                                      self.msg2_len, self._e(q, self.msg2_len, "q"),
+                                                      self._e(dq, self.msg2_len, "dq"), int(lo_mask), *self._tail()),
+                   "choco_lowrank_gossip_diff")
+
+    def apply(self, x, phat, dq, msg1_recv, weights, lo_mask):
+        """x += sum_e c_e phat[e] dq[e]^T (c_e = -w_e at the low end, +w_e at the high end); uncompressed
+        tensors: x += sum_e w_e (msg1_recv[e]'s tail - x).  One read-modify-write pass over x."""
+        if len(weights) != self.n_edges:
+            raise RuntimeError(f"LowRankGossipPlan.apply: {self.n_edges} weights expected, got {len(weights)}")
+        w = (ctypes.c_double * self.n_edges)(*[float(v) for v in weights])
+        _lib.check(_c.lib().choco_lowrank_gossip_apply(self.table._flat(x, self.n, "x"), self._e(phat, self.p_total, "phat"),
+                                                       self._e(dq, self.msg2_len, "dq"),
+                                                       self._e(msg1_recv, self.msg1_len, "msg1_recv"), self.msg1_len,
+                                                       self.msg2_len, w, int(lo_mask), *self._tail()),
+                   "choco_lowrank_gossip_apply")

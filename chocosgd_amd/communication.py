@@ -84,6 +84,23 @@ class DecentralizedAggregation(object):
             return reqs, local_data
         raise NotImplementedError("op {} is not supported yet.".format(op))
 
+    def exchange_edges(self, messages, out=None):
+        """Per-edge exchange (this drop-in's addition; powergossip.py): messages = {rank: tensor}, one
+        per neighbour.  ONE grouped batch sends every neighbour its own tensor and receives one of the
+        same shape and dtype from it; blocking; returns {rank: received}.  out: {rank: buffer} to
+        receive into (e.g. the rows of one edge-major buffer)."""
+        if sorted(messages) != sorted(self.neighbor_ranks):
+            raise RuntimeError(f"exchange_edges needs one message per neighbour {sorted(self.neighbor_ranks)}, got "
+                               f"{sorted(messages)}")
+        received = {r: out[r] if out is not None else torch.empty_like(messages[r]) for r in self.neighbor_ranks}
+        ops = []
+        for r in self.neighbor_ranks:
+            ops.append(dist.P2POp(dist.isend, messages[r], r))
+            ops.append(dist.P2POp(dist.irecv, received[r], r))
+        if ops:
+            _Works(dist.batch_isend_irecv(ops)).wait()
+        return received
+
     def _weighted(self, local_data):
         """sum(t * w_r) in local_data's order (communication.py:271-277).  Contiguous fp32 ROCm
         tensors take one codec.params_mix call, with the same bits as the expression; CPU

@@ -1,7 +1,9 @@
 // What the two low-rank kernel families share (lowrank.hip: ranks 1, 2 and 4 on the vector ALUs;
 // lowrank_mfma.hip: ranks 8, 16 and 32 on the fp32 matrix instruction): the tile table's layout,
 // its builder, the check every launch makes first, and the high-rank launches' declarations.
-// lowrank_cholqr.hip (Cholesky-QR orthogonalisation at ranks 8, 16 and 32) reads the same table.
+// lowrank_cholqr.hip (Cholesky-QR orthogonalisation at ranks 8, 16 and 32) reads the same table, and so
+// does lowrank_gossip.hip (PowerGossip, batched over a worker's edges), which also shares the
+// Gram-Schmidt sweep below with lowrank.hip.
 #pragma once
 
 #include "choco_common.h"
@@ -39,6 +41,63 @@ struct LrMat {
 CHOCO_DEV LrMat lr_mat(const int64_t* __restrict__ plan, int64_t m) {
   const int64_t* r = plan + plan[kLrOffMat] + kLrMatRow * m;
   return LrMat{r[0], r[1], r[2], r[3], r[4], r[5], r[6]};
+}
+
+// ---------------------------------------------------------------- orthogonalise (device)
+// the sum of K doubles per thread over the workgroup, in every thread: a butterfly in the wave,
+// then the waves in order
+template <int K>
+CHOCO_DEV void lr_block_sum(double (&v)[K], double (*red)[K]) {
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+  __syncthreads();  // red is free again
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[w][k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+}
+
+// Modified Gram-Schmidt on the columns of one P (rows x R) by one workgroup: rows [0, STAGE) are in
+// Ps (LDS, already loaded and barriered), the others in place in P.  Thread t owns rows t, t + 256,
+// ...: only the fp64 reductions need barriers.  lowrank_orth_kernel and lowrank_gossip_orth_kernel
+// both run exactly this.
+template <int R, int STAGE>
+CHOCO_DEV void lr_mgs(float* __restrict__ P, int64_t rows, float* Ps, double (*red)[R]) {
+  auto at = [&](int64_t i) -> float* { return i < STAGE ? Ps + i * R : P + i * R; };
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    double s[1] = {0.0};
+    for (int64_t i = threadIdx.x; i < rows; i += kLrThreads) {
+      const double v = (double)at(i)[k];
+      s[0] += v * v;
+    }
+    lr_block_sum<1>(s, reinterpret_cast<double(*)[1]>(&red[0][0]));
+    const double den = sqrt(s[0]) + 1e-8;
+    double dot[R];
+#pragma unroll
+    for (int l = 0; l < R; ++l) dot[l] = 0.0;
+    for (int64_t i = threadIdx.x; i < rows; i += kLrThreads) {
+      float* r = at(i);
+      const float v = (float)((double)r[k] / den);
+      r[k] = v;
+#pragma unroll
+      for (int l = 0; l < R; ++l)  // l > k as a predicate: dot[] keeps constant indices where k is not unrolled
+        if (l > k) dot[l] += (double)v * (double)r[l];
+    }
+    if (k + 1 < R) {
+      lr_block_sum<R>(dot, red);
+      for (int64_t i = threadIdx.x; i < rows; i += kLrThreads) {
+        float* r = at(i);
+#pragma unroll
+        for (int l = 0; l < R; ++l)
+          if (l > k) r[l] = (float)((double)r[l] - dot[l] * (double)r[k]);
+      }
+    }
+  }
 }
 
 // ---------------------------------------------------------------- the table (host)

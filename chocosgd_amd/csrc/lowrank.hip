@@ -256,23 +256,7 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_slabsum_kernel(const float
 }
 
 // ---------------------------------------------------------------- orthogonalise
-// the sum of K doubles per thread over the workgroup, in every thread: a butterfly in the wave,
-// then the waves in order
-template <int K>
-CHOCO_DEV void lr_block_sum(double (&v)[K], double (*red)[K]) {
-  const int lane = lane_id(), w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-  __syncthreads();  // red is free again
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[w][k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-}
-
+// the Gram-Schmidt sweep itself (lr_mgs) is in lowrank.h, shared with lowrank_gossip.hip
 template <int R, int STAGE = kLrOrthStage>
 __global__ __launch_bounds__(kLrThreads) void lowrank_orth_kernel(float* __restrict__ msg1,
                                                                   const int64_t* __restrict__ plan) {
@@ -280,42 +264,10 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_orth_kernel(float* __restr
   __shared__ double red[kLrWaves][R];
   const LrMat M = lr_mat(plan, blockIdx.x);
   float* P = msg1 + M.poff;
-  const int64_t rows = M.rows;
-  const int ns = (int)(rows < STAGE ? rows : STAGE);
+  const int ns = (int)(M.rows < STAGE ? M.rows : STAGE);
   for (int i = threadIdx.x; i < ns * R; i += kLrThreads) Ps[i] = P[i];
   __syncthreads();
-  // thread t owns rows t, t + 256, ...: the staged ones in LDS, the others in place
-  auto at = [&](int64_t i) -> float* { return i < STAGE ? Ps + i * R : P + i * R; };
-#pragma unroll
-  for (int k = 0; k < R; ++k) {
-    double s[1] = {0.0};
-    for (int64_t i = threadIdx.x; i < rows; i += kLrThreads) {
-      const double v = (double)at(i)[k];
-      s[0] += v * v;
-    }
-    lr_block_sum<1>(s, reinterpret_cast<double(*)[1]>(&red[0][0]));
-    const double den = sqrt(s[0]) + 1e-8;
-    double dot[R];
-#pragma unroll
-    for (int l = 0; l < R; ++l) dot[l] = 0.0;
-    for (int64_t i = threadIdx.x; i < rows; i += kLrThreads) {
-      float* r = at(i);
-      const float v = (float)((double)r[k] / den);
-      r[k] = v;
-#pragma unroll
-      for (int l = 0; l < R; ++l)  // l > k as a predicate: dot[] keeps constant indices where k is not unrolled
-        if (l > k) dot[l] += (double)v * (double)r[l];
-    }
-    if (k + 1 < R) {
-      lr_block_sum<R>(dot, red);
-      for (int64_t i = threadIdx.x; i < rows; i += kLrThreads) {
-        float* r = at(i);
-#pragma unroll
-        for (int l = 0; l < R; ++l)
-          if (l > k) r[l] = (float)((double)r[l] - dot[l] * (double)r[k]);
-      }
-    }
-  }
+  lr_mgs<R, STAGE>(P, M.rows, Ps, red);
   __syncthreads();
   for (int i = threadIdx.x; i < ns * R; i += kLrThreads) P[i] = Ps[i];
 }

@@ -1,0 +1,500 @@
+// PowerGossip (Vogels, Karimireddy, Jaggi, NeurIPS 2020): the low-rank kernels of a decentralized
+// worker, batched over its E edges (include/choco_codec.h, "low-rank gossip").
+//
+// Edge e = (me, j_e) runs a warm-started power iteration on X_me - X_j without either end forming
+// the difference: both ends multiply their own X by the edge's shared Q_e and swap the thin
+// products.  A worker with E neighbours holds E different Qs against the SAME X, so every pass
+// over X here serves all edges at once, K = E r columns wide (K <= 8):
+//     project        P_e = X Q_e for every e                      reads X:            4 B / element
+//     orthogonalise  P^_e = MGS(P_e(lo end) - P_e(hi end))       one workgroup per (edge, matrix)
+//     back-project   Q'_e = X^T P^_e for every e                  reads X:            4 B / element
+//     diff           dQ_e = Q'_e(lo end) - Q'_e(hi end); the edge's next Q unless it is all zero
+//     apply          X += sum_e c_e P^_e dQ_e^T                   reads and writes X: 8 B / element
+// against PowerSGD's 12 + 4 + 12 B / element per Q (lowrank.hip), which a per-edge loop would pay E
+// times.  The kernels read codec.LowRankPlan's tile table at rank r unchanged (lowrank.h: row items,
+// back-project items, slab-sum items); the E edges' buffers are contiguous [E][msg1_len],
+// [E][msg2_len] and [E][P_total] arrays, and the slab workspace is E times PowerSGD's.
+//
+// Templated on (ES, R): ES = E rounded up to 1, 2, 4 or 8 edge slots, R the rank, K = ES R <= 8
+// planes / accumulators.  A padded slot's planes are zeros in LDS and nothing of it is ever stored.
+//   * project: the wave-per-row walk of lowrank_project_kernel (16-byte loads on the flat buffer's
+//     16-byte grid, scalar head and tail, a fixed butterfly, the column blocks' sums added in
+//     ascending order) with all E Qs' column blocks in LDS as K planes; the block is 2048 columns
+//     up to K = 4 and 1024 at K = 8 (K planes x block x 4 B = 32 KB beside the 8 KB of row sums).
+//   * back-project: 64 columns x one 256-row slab an item, the slab's P^ rows of all edges in LDS
+//     (a broadcast read), K accumulators a lane, the four waves joined in wave order, slab partials
+//     summed in ascending slab order by lowrank_gossip_slabsum_kernel.
+//   * apply: K planes of dQ through LDS in the same column blocks, the item's P^ rows of all edges
+//     in LDS; per element each edge's product is lr_dec1's column-order fmaf chain, then
+//     u = c_0 o_0, u = u + c_e o_e in ascending e (a multiply and an add, not fused), x = x + u.
+//     c_e = -w_e at the edge's low end and +w_e at its high end: with bit-identical P^_e and dQ_e at
+//     both ends (orthogonalise and diff see the same operands in the same order) the two ends'
+//     updates are exact negations.  Tail items mix the uncompressed tensors plainly.
+// No atomics: every output is a fixed-order function of its inputs, the same bits every call.
+#include "lowrank.h"
+
+#include <cmath>
+
+namespace choco {
+
+constexpr int kLgMaxK = 8;
+constexpr int lg_colblock(int K) { return K <= 4 ? kLrColBlock : 1024; }
+constexpr int lg_slots(int E) { return E <= 1 ? 1 : E <= 2 ? 2 : E <= 4 ? 4 : 8; }
+
+// the signed weights of apply's matrix items (c) and the plain ones of its tail items (w)
+struct LgWeights {
+  float c[kLgMaxK], w[kLgMaxK];
+};
+
+// up to four columns of all K planes: one 16-byte LDS read a plane where j is on the 16-byte grid
+template <int K, int CB>
+CHOCO_DEV void lg_q4(const float* Qs, int j, bool al, float (&q)[K][4]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (al) {
+      const float4 t = *reinterpret_cast<const float4*>(Qs + k * CB + j);
+      q[k][0] = t.x; q[k][1] = t.y; q[k][2] = t.z; q[k][3] = t.w;
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) q[k][u] = Qs[k * CB + j + u];
+    }
+  }
+}
+
+// the workgroup stages columns [cb0, cb0 + nb) of every edge's (cols x R) row-major factor at
+// `src + e * stride` as planes e R .. e R + R - 1
+template <int R, int CB>
+CHOCO_DEV void lg_stage(float* Qs, const float* __restrict__ src, int64_t stride, int E, int nb) {
+  for (int e = 0; e < E; ++e) {
+    const float* __restrict__ s = src + e * stride;
+    for (int i = threadIdx.x; i < nb * R; i += kLrThreads) Qs[(e * R + i % R) * CB + i / R] = s[i];
+  }
+}
+
+// rows [row0, row0 + nrows) of every edge's P^ of matrix M as Ps[row][K]; a padded slot's are zeros
+template <int ES, int R>
+CHOCO_DEV void lg_stage_rows(float* Ps, const float* __restrict__ phat, int64_t p_total, const LrMat& M, int64_t row0,
+                             int nrows, int E) {
+  constexpr int K = ES * R;
+  for (int i = threadIdx.x; i < nrows * K; i += kLrThreads) {
+    const int rl = i / K, k = i % K, e = k / R;
+    Ps[i] = e < E ? phat[e * p_total + M.poff + (row0 + rl) * R + k % R] : 0.0f;
+  }
+}
+
+// ---------------------------------------------------------------- project
+template <int ES, int R>
+__global__ __launch_bounds__(kLrThreads) void lowrank_gossip_project_kernel(const float* __restrict__ x,
+                                                                            const float* __restrict__ q,
+                                                                            float* __restrict__ msg1, int E,
+                                                                            const int64_t* __restrict__ plan) {
+  constexpr int K = ES * R, CB = lg_colblock(K);
+  __shared__ __attribute__((aligned(16))) float Qs[K * CB];
+  __shared__ float psum[kLrRowCap * K];
+  const int64_t m1 = plan[kLrMsg1], m2 = plan[kLrMsg2];
+  const int64_t* it = plan + plan[kLrOffRow] + kLrItemRow * (int64_t)blockIdx.x;
+  if (it[0] < 0) {  // a piece of an uncompressed tensor: into every edge's message tail
+    const int64_t off = it[1], tail = it[3];
+    const int cnt = (int)it[2];
+    for (int i = threadIdx.x; i < cnt; i += kLrThreads) {
+      const float v = x[off + i];
+      for (int e = 0; e < E; ++e) msg1[e * m1 + tail + i] = v;
+    }
+    return;
+  }
+  const LrMat M = lr_mat(plan, it[0]);
+  const int64_t row0 = it[1];
+  const int nrows = (int)it[2];
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  for (int i = E * R * CB + threadIdx.x; i < K * CB; i += kLrThreads) Qs[i] = 0.0f;  // the padded slots' planes
+  for (int i = threadIdx.x; i < nrows * K; i += kLrThreads) psum[i] = 0.0f;
+  for (int64_t cb0 = 0; cb0 < M.cols; cb0 += CB) {
+    const int nb = (int)(M.cols - cb0 < CB ? M.cols - cb0 : CB);
+    __syncthreads();
+    lg_stage<R, CB>(Qs, q + M.qoff + cb0 * R, m2, E, nb);
+    __syncthreads();
+    for (int rl = w; rl < nrows; rl += kLrWaves) {
+      const int64_t a = M.off + (row0 + rl) * M.cols + cb0;
+      const int head0 = (int)((4 - (a & 3)) & 3), head = head0 < nb ? head0 : nb;
+      float acc[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] = 0.0f;
+      if (lane < head) {
+        const float m = x[a + lane];
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] = fmaf(m, Qs[k * CB + lane], acc[k]);
+      }
+      const int nvec = (nb - head) >> 2;
+      const bool al = head == 0;
+#pragma unroll 2
+      for (int v = lane; v < nvec; v += 64) {
+        const int j = head + 4 * v;
+        const float4 m = *reinterpret_cast<const float4*>(x + a + j);
+        float qq[K][4];
+        lg_q4<K, CB>(Qs, j, al, qq);
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          acc[k] = fmaf(m.w, qq[k][3], fmaf(m.z, qq[k][2], fmaf(m.y, qq[k][1], fmaf(m.x, qq[k][0], acc[k]))));
+      }
+      const int j0 = head + 4 * nvec;
+      if (lane < nb - j0) {
+        const float m = x[a + j0 + lane];
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] = fmaf(m, Qs[k * CB + j0 + lane], acc[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] = wave_sum(acc[k]);
+      if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) psum[rl * K + k] += acc[k];
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nrows * K; i += kLrThreads) {
+    const int rl = i / K, k = i % K, e = k / R;
+    if (e < E) msg1[e * m1 + M.poff + (row0 + rl) * R + k % R] = psum[i];
+  }
+}
+
+// ---------------------------------------------------------------- orthogonalise
+// one workgroup per (matrix, edge): dP = P(lo end) - P(hi end), one fp32 subtraction per element
+// formed by the thread that owns the row in lr_mgs, then lowrank_orth_kernel's sweep
+template <int R>
+__global__ __launch_bounds__(kLrThreads) void lowrank_gossip_orth_kernel(const float* __restrict__ own,
+                                                                         const float* __restrict__ recv,
+                                                                         float* __restrict__ phat, uint32_t lo_mask,
+                                                                         const int64_t* __restrict__ plan) {
+  __shared__ float Ps[kLrOrthStage * R];
+  __shared__ double red[kLrWaves][R];
+  const LrMat M = lr_mat(plan, blockIdx.x);
+  const int e = blockIdx.y;
+  const bool lo = (lo_mask >> e) & 1u;
+  const int64_t at1 = e * plan[kLrMsg1] + M.poff;
+  const float* __restrict__ a = (lo ? own : recv) + at1;
+  const float* __restrict__ b = (lo ? recv : own) + at1;
+  float* P = phat + e * plan[kLrPTotal] + M.poff;
+  for (int64_t i = threadIdx.x; i < M.rows; i += kLrThreads) {
+    float* r = i < kLrOrthStage ? Ps + i * R : P + i * R;
+#pragma unroll
+    for (int c = 0; c < R; ++c) r[c] = a[i * R + c] - b[i * R + c];
+  }
+  __syncthreads();
+  lr_mgs<R, kLrOrthStage>(P, M.rows, Ps, red);
+  __syncthreads();
+  const int ns = (int)(M.rows < kLrOrthStage ? M.rows : kLrOrthStage);
+  for (int i = threadIdx.x; i < ns * R; i += kLrThreads) P[i] = Ps[i];
+}
+
+// ---------------------------------------------------------------- back-project
+template <int ES, int R>
+__global__ __launch_bounds__(kLrThreads) void lowrank_gossip_backproject_kernel(const float* __restrict__ x,
+                                                                                const float* __restrict__ phat,
+                                                                                float* __restrict__ msg2,
+                                                                                float* __restrict__ ws, int E,
+                                                                                const int64_t* __restrict__ plan) {
+  constexpr int K = ES * R;
+  __shared__ __attribute__((aligned(16))) float Ps[kLrSlab * K];
+  __shared__ float red[kLrWaves][K][kLrStrip];
+  const int64_t* it = plan + plan[kLrOffBp] + kLrItemRow * (int64_t)blockIdx.x;
+  const LrMat M = lr_mat(plan, it[0]);
+  const int64_t col0 = it[1], slab = it[2];
+  const int64_t row0 = slab * kLrSlab;
+  const int nrows = (int)(M.rows - row0 < kLrSlab ? M.rows - row0 : kLrSlab);
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  lg_stage_rows<ES, R>(Ps, phat, plan[kLrPTotal], M, row0, nrows, E);
+  __syncthreads();
+  const int64_t col = col0 + lane;
+  const bool active = col < M.cols;
+  float acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = 0.0f;
+  if (active) {
+    const float* __restrict__ p = x + M.off + row0 * M.cols + col;
+#pragma unroll 4
+    for (int rl = w; rl < nrows; rl += kLrWaves) {
+      const float m = p[rl * M.cols];
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] = fmaf(m, Ps[rl * K + k], acc[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) red[w][k][lane] = acc[k];
+  __syncthreads();
+  if (w == 0 && active) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e = k / R;
+      if (e >= E) continue;
+      float* dst = M.nslab == 1 ? msg2 + e * plan[kLrMsg2] + M.qoff + col * R
+                                : ws + e * plan[kLrWsFloats] + M.wsoff + (slab * M.cols + col) * R;
+      dst[k % R] = ((red[0][k][lane] + red[1][k][lane]) + red[2][k][lane]) + red[3][k][lane];
+    }
+  }
+}
+
+// Q' of the matrices of more than one slab, per edge (blockIdx.y): the slab partials in ascending order
+__global__ __launch_bounds__(kLrThreads) void lowrank_gossip_slabsum_kernel(const float* __restrict__ ws,
+                                                                            float* __restrict__ msg2,
+                                                                            const int64_t* __restrict__ plan) {
+  const int64_t* it = plan + plan[kLrOffSum] + kLrItemRow * (int64_t)blockIdx.x;
+  const LrMat M = lr_mat(plan, it[0]);
+  const int64_t ne = M.cols * plan[kLrRank], i = it[1] + threadIdx.x;
+  if ((int)threadIdx.x >= (int)it[2]) return;
+  const float* __restrict__ src = ws + blockIdx.y * plan[kLrWsFloats] + M.wsoff;
+  float s = src[i];
+  for (int64_t sl = 1; sl < M.nslab; ++sl) s += src[sl * ne + i];
+  msg2[blockIdx.y * plan[kLrMsg2] + M.qoff + i] = s;
+}
+
+// ---------------------------------------------------------------- diff
+// one workgroup per (matrix, edge): dQ = Q'(lo end) - Q'(hi end) into dq; the edge's Q state takes
+// it unless every element is zero (an edge that once agrees exactly would otherwise be dead for good)
+template <int R>
+__global__ __launch_bounds__(kLrThreads) void lowrank_gossip_diff_kernel(const float* __restrict__ own,
+                                                                         const float* __restrict__ recv,
+                                                                         float* __restrict__ q, float* __restrict__ dq,
+                                                                         uint32_t lo_mask,
+                                                                         const int64_t* __restrict__ plan) {
+  const LrMat M = lr_mat(plan, blockIdx.x);
+  const int e = blockIdx.y;
+  const bool lo = (lo_mask >> e) & 1u;
+  const int64_t at2 = e * plan[kLrMsg2] + M.qoff, ne = M.cols * R;
+  const float* __restrict__ a = (lo ? own : recv) + at2;
+  const float* __restrict__ b = (lo ? recv : own) + at2;
+  int nz = 0;
+  for (int64_t i = threadIdx.x; i < ne; i += kLrThreads) {
+    const float d = a[i] - b[i];
+    dq[at2 + i] = d;
+    nz |= d != 0.0f;
+  }
+  if (!__syncthreads_or(nz)) return;
+  for (int64_t i = threadIdx.x; i < ne; i += kLrThreads) q[at2 + i] = a[i] - b[i];
+}
+
+// ---------------------------------------------------------------- apply
+// u = sum_e c_e (p_e . dq_e): each edge's product in column order, the edges in ascending order
+template <int ES, int R>
+CHOCO_DEV float lg_update(const float (&p)[ES * R], const float (&qc)[ES * R], const LgWeights& W, int E) {
+  float u = 0.0f;
+#pragma unroll
+  for (int e = 0; e < ES; ++e) {
+    if (e < E) {
+      float o = p[e * R] * qc[e * R];
+#pragma unroll
+      for (int c = 1; c < R; ++c) o = fmaf(p[e * R + c], qc[e * R + c], o);
+      const float t = W.c[e] * o;
+      u = e == 0 ? t : u + t;
+    }
+  }
+  return u;
+}
+
+template <int ES, int R>
+__global__ __launch_bounds__(kLrThreads) void lowrank_gossip_apply_kernel(float* __restrict__ x,
+                                                                          const float* __restrict__ phat,
+                                                                          const float* __restrict__ dq,
+                                                                          const float* __restrict__ recv1, LgWeights W,
+                                                                          int E, const int64_t* __restrict__ plan) {
+  constexpr int K = ES * R, CB = lg_colblock(K);
+  __shared__ __attribute__((aligned(16))) float Qs[K * CB];
+  __shared__ float Ps[kLrRowCap * K];
+  const int64_t* it = plan + plan[kLrOffRow] + kLrItemRow * (int64_t)blockIdx.x;
+  if (it[0] < 0) {  // an uncompressed tensor: x + sum_e w_e (x_received,e - x) from the received tails
+    const int64_t off = it[1], tail = it[3], m1 = plan[kLrMsg1];
+    const int cnt = (int)it[2];
+    for (int i = threadIdx.x; i < cnt; i += kLrThreads) {
+      const float xv = x[off + i];
+      float u = W.w[0] * (recv1[tail + i] - xv);
+#pragma unroll
+      for (int e = 1; e < ES; ++e)
+        if (e < E) u = u + W.w[e] * (recv1[e * m1 + tail + i] - xv);
+      x[off + i] = xv + u;
+    }
+    return;
+  }
+  const LrMat M = lr_mat(plan, it[0]);
+  const int64_t row0 = it[1];
+  const int nrows = (int)it[2];
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  for (int i = E * R * CB + threadIdx.x; i < K * CB; i += kLrThreads) Qs[i] = 0.0f;  // the padded slots' planes
+  lg_stage_rows<ES, R>(Ps, phat, plan[kLrPTotal], M, row0, nrows, E);
+  for (int64_t cb0 = 0; cb0 < M.cols; cb0 += CB) {
+    const int nb = (int)(M.cols - cb0 < CB ? M.cols - cb0 : CB);
+    __syncthreads();
+    lg_stage<R, CB>(Qs, dq + M.qoff + cb0 * R, plan[kLrMsg2], E, nb);
+    __syncthreads();
+    for (int rl = w; rl < nrows; rl += kLrWaves) {
+      const int64_t a = M.off + (row0 + rl) * M.cols + cb0;
+      const int head0 = (int)((4 - (a & 3)) & 3), head = head0 < nb ? head0 : nb;
+      float p[K], qc[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) p[k] = Ps[rl * K + k];
+      if (lane < head) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) qc[k] = Qs[k * CB + lane];
+        x[a + lane] = x[a + lane] + lg_update<ES, R>(p, qc, W, E);
+      }
+      const int nvec = (nb - head) >> 2;
+      const bool al = head == 0;
+#pragma unroll 2
+      for (int v = lane; v < nvec; v += 64) {
+        const int j = head + 4 * v;
+        const float4 m = *reinterpret_cast<const float4*>(x + a + j);
+        float qq[K][4], o[4];
+        lg_q4<K, CB>(Qs, j, al, qq);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+          for (int k = 0; k < K; ++k) qc[k] = qq[k][u];
+          o[u] = lg_update<ES, R>(p, qc, W, E);
+        }
+        *reinterpret_cast<float4*>(x + a + j) = make_float4(m.x + o[0], m.y + o[1], m.z + o[2], m.w + o[3]);
+      }
+      const int j0 = head + 4 * nvec;
+      if (lane < nb - j0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) qc[k] = Qs[k * CB + j0 + lane];
+        x[a + j0 + lane] = x[a + j0 + lane] + lg_update<ES, R>(p, qc, W, E);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- launches
+// (edge slots, rank) -> the kernel's instance; the nine pairs with ES R <= 8
+#define LG_CASE(ES_, R_, KERNEL, ...) \
+  if (es == ES_ && rank == R_) return CHOCO_LAUNCH(#KERNEL, #KERNEL, (KERNEL<ES_, R_>), __VA_ARGS__)
+#define LG_LAUNCH(KERNEL, ...)                 \
+  do {                                         \
+    const int es = lg_slots(E);                \
+    LG_CASE(1, 1, KERNEL, __VA_ARGS__);        \
+    LG_CASE(2, 1, KERNEL, __VA_ARGS__);        \
+    LG_CASE(4, 1, KERNEL, __VA_ARGS__);        \
+    LG_CASE(8, 1, KERNEL, __VA_ARGS__);        \
+    LG_CASE(1, 2, KERNEL, __VA_ARGS__);        \
+    LG_CASE(2, 2, KERNEL, __VA_ARGS__);        \
+    LG_CASE(4, 2, KERNEL, __VA_ARGS__);        \
+    LG_CASE(1, 4, KERNEL, __VA_ARGS__);        \
+    LG_CASE(2, 4, KERNEL, __VA_ARGS__);        \
+    return fail(CHOCO_ERR_INVALID, "no instance for %d edges at rank %d", (int)E, (int)rank); \
+  } while (0)
+#define LG_BY_RANK(rank, KERNEL, ...)                                                   \
+  ((rank) == 1 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<1>, __VA_ARGS__)                 \
+               : (rank) == 2 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<2>, __VA_ARGS__)   \
+                             : CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<4>, __VA_ARGS__))
+
+static int lg_project(int32_t rank, int E, dim3 grid, hipStream_t st, const float* x, const float* q, float* msg1,
+                      const int64_t* plan) {
+  LG_LAUNCH(lowrank_gossip_project_kernel, grid, dim3(kLrThreads), st, x, q, msg1, E, plan);
+}
+static int lg_backproject(int32_t rank, int E, dim3 grid, hipStream_t st, const float* x, const float* phat, float* msg2,
+                          float* ws, const int64_t* plan) {
+  LG_LAUNCH(lowrank_gossip_backproject_kernel, grid, dim3(kLrThreads), st, x, phat, msg2, ws, E, plan);
+}
+static int lg_apply(int32_t rank, int E, dim3 grid, hipStream_t st, float* x, const float* phat, const float* dq,
+                    const float* recv1, LgWeights W, const int64_t* plan) {
+  LG_LAUNCH(lowrank_gossip_apply_kernel, grid, dim3(kLrThreads), st, x, phat, dq, recv1, W, E, plan);
+}
+
+// what every gossip launch checks first: lr_check, then the width
+static int lg_check(const int64_t* plan_host, const void* plan_dev, int64_t n, int32_t rank, int32_t n_edges,
+                    int64_t msg1_len, int64_t msg2_len) {
+  CHOCO_TRY(lr_check(plan_host, plan_dev, n, rank, msg1_len, msg2_len));
+  CHOCO_REQUIRE(n_edges >= 1, "n_edges must be at least 1, got %d", (int)n_edges);
+  CHOCO_REQUIRE(rank <= 4 && (int64_t)n_edges * rank <= kLgMaxK,
+                "n_edges * rank must be at most %d at rank 1, 2 or 4, got %d edges at rank %d", kLgMaxK, (int)n_edges,
+                (int)rank);
+  return CHOCO_OK;
+}
+
+}  // namespace choco
+
+using namespace choco;
+
+CHOCO_API size_t choco_lowrank_gossip_workspace_size(const int64_t* plan_host, int32_t n_edges) {
+  if (!plan_host || plan_host[kLrMagic] != kLrMagicValue || n_edges < 1 || n_edges > kLgMaxK) return 0;
+  return align_up((size_t)n_edges * (size_t)plan_host[kLrWsFloats] * sizeof(float), 256) + 256;
+}
+
+CHOCO_API int choco_lowrank_gossip_project(const float* x, const float* q, float* msg1, int64_t msg1_len,
+                                           int64_t msg2_len, const int64_t* plan_host, const int64_t* plan_dev,
+                                           int64_t n, int32_t rank, int32_t n_edges, void* stream) {
+  CHOCO_REQUIRE(x && msg1, "null pointer");
+  CHOCO_TRY(lg_check(plan_host, plan_dev, n, rank, n_edges, msg1_len, msg2_len));
+  CHOCO_REQUIRE(msg2_len >= 0, "message 2 needs its length");
+  CHOCO_REQUIRE(q || plan_host[kLrMsg2] == 0, "null pointer");
+  CHOCO_REQUIRE(aligned16(x), "x must be 16-byte aligned");
+  CHOCO_REQUIRE(aligned4(q) && aligned4(msg1), "q and msg1 must be 4-byte aligned");
+  return lg_project(rank, n_edges, dim3((unsigned)plan_host[kLrNRow]), as_stream(stream), x, q, msg1, plan_dev);
+}
+
+CHOCO_API int choco_lowrank_gossip_orthogonalize(const float* msg1_own, const float* msg1_recv, int64_t msg1_len,
+                                                 float* phat, uint32_t lo_mask, const int64_t* plan_host,
+                                                 const int64_t* plan_dev, int64_t n, int32_t rank, int32_t n_edges,
+                                                 void* stream) {
+  CHOCO_REQUIRE(msg1_own && msg1_recv, "null pointer");
+  CHOCO_TRY(lg_check(plan_host, plan_dev, n, rank, n_edges, msg1_len, -1));
+  if (plan_host[kLrNcomp] == 0) return CHOCO_OK;
+  CHOCO_REQUIRE(phat, "null pointer");
+  CHOCO_REQUIRE(aligned4(msg1_own) && aligned4(msg1_recv) && aligned4(phat), "misaligned pointer");
+  const dim3 grid((unsigned)plan_host[kLrNcomp], (unsigned)n_edges), block(kLrThreads);
+  return LG_BY_RANK(rank, lowrank_gossip_orth_kernel, grid, block, as_stream(stream), msg1_own, msg1_recv, phat, lo_mask,
+                    plan_dev);
+}
+
+CHOCO_API int choco_lowrank_gossip_backproject(const float* x, const float* phat, int64_t msg1_len, float* msg2,
+                                               int64_t msg2_len, void* ws, size_t ws_bytes, const int64_t* plan_host,
+                                               const int64_t* plan_dev, int64_t n, int32_t rank, int32_t n_edges,
+                                               void* stream) {
+  CHOCO_REQUIRE(x, "null pointer");
+  CHOCO_TRY(lg_check(plan_host, plan_dev, n, rank, n_edges, msg1_len, msg2_len));
+  CHOCO_REQUIRE(msg2_len >= 0, "message 2 needs its length");
+  if (plan_host[kLrNcomp] == 0) return CHOCO_OK;
+  CHOCO_REQUIRE(phat && msg2 && ws, "null pointer");
+  CHOCO_REQUIRE(ws_bytes >= choco_lowrank_gossip_workspace_size(plan_host, n_edges),
+                "workspace too small: %zu bytes, need %zu", ws_bytes,
+                choco_lowrank_gossip_workspace_size(plan_host, n_edges));
+  CHOCO_REQUIRE(aligned4(x) && aligned4(phat) && aligned4(msg2) && aligned16(ws), "misaligned pointer");
+  const hipStream_t st = as_stream(stream);
+  float* wsf = reinterpret_cast<float*>(ws);
+  CHOCO_TRY(lg_backproject(rank, n_edges, dim3((unsigned)plan_host[kLrNBp]), st, x, phat, msg2, wsf, plan_dev));
+  if (plan_host[kLrNSum] == 0) return CHOCO_OK;
+  return CHOCO_LAUNCH("lowrank_gossip_slabsum_kernel", "lowrank_gossip_slabsum_kernel", lowrank_gossip_slabsum_kernel,
+                      dim3((unsigned)plan_host[kLrNSum], (unsigned)n_edges), dim3(kLrThreads), st, (const float*)wsf,
+                      msg2, plan_dev);
+}
+
+CHOCO_API int choco_lowrank_gossip_diff(const float* msg2_own, const float* msg2_recv, int64_t msg1_len,
+                                        int64_t msg2_len, float* q, float* dq, uint32_t lo_mask,
+                                        const int64_t* plan_host, const int64_t* plan_dev, int64_t n, int32_t rank,
+                                        int32_t n_edges, void* stream) {
+  CHOCO_TRY(lg_check(plan_host, plan_dev, n, rank, n_edges, msg1_len, msg2_len));
+  CHOCO_REQUIRE(msg2_len >= 0, "message 2 needs its length");
+  if (plan_host[kLrNcomp] == 0) return CHOCO_OK;
+  CHOCO_REQUIRE(msg2_own && msg2_recv && q && dq, "null pointer");
+  CHOCO_REQUIRE(aligned4(msg2_own) && aligned4(msg2_recv) && aligned4(q) && aligned4(dq), "misaligned pointer");
+  const dim3 grid((unsigned)plan_host[kLrNcomp], (unsigned)n_edges), block(kLrThreads);
+  return LG_BY_RANK(rank, lowrank_gossip_diff_kernel, grid, block, as_stream(stream), msg2_own, msg2_recv, q, dq, lo_mask,
+                    plan_dev);
+}
+
+CHOCO_API int choco_lowrank_gossip_apply(float* x, const float* phat, const float* dq, const float* msg1_recv,
+                                         int64_t msg1_len, int64_t msg2_len, const double* weights, uint32_t lo_mask,
+                                         const int64_t* plan_host, const int64_t* plan_dev, int64_t n, int32_t rank,
+                                         int32_t n_edges, void* stream) {
+  CHOCO_REQUIRE(x && msg1_recv && weights, "null pointer");
+  CHOCO_TRY(lg_check(plan_host, plan_dev, n, rank, n_edges, msg1_len, msg2_len));
+  CHOCO_REQUIRE(msg2_len >= 0, "message 2 needs its length");
+  CHOCO_REQUIRE((phat && dq) || plan_host[kLrNcomp] == 0, "null pointer");
+  CHOCO_REQUIRE(aligned16(x), "x must be 16-byte aligned");
+  CHOCO_REQUIRE(aligned4(phat) && aligned4(dq) && aligned4(msg1_recv), "misaligned pointer");
+  LgWeights W = {};
+  for (int e = 0; e < n_edges; ++e) {
+    CHOCO_REQUIRE(std::isfinite((float)weights[e]), "weight %d is not finite as an fp32 value", e);
+    W.w[e] = (float)weights[e];
+    W.c[e] = (lo_mask >> e) & 1u ? -W.w[e] : W.w[e];
+  }
+  return lg_apply(rank, n_edges, dim3((unsigned)plan_host[kLrNRow]), as_stream(stream), x, phat, dq, msg1_recv, W,
+                  plan_dev);
+}

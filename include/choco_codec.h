@@ -1327,6 +1327,60 @@ int choco_lowrank_decode(float* e, const float* msg1, int64_t msg1_len, const fl
                          float* flat_out, double divisor, const int64_t* plan_host, const int64_t* plan_dev,
                          int64_t n, int32_t rank, void* stream);
 
+/* ------------------------------------------- low-rank gossip (PowerGossip)
+ * PowerGossip (Vogels, Karimireddy, Jaggi, NeurIPS 2020) for a decentralized worker with n_edges
+ * neighbours: edge e runs a warm-started power iteration on X_me - X_je with a Q_e both ends share.
+ * The five calls read the choco_lowrank_plan table of the layout at `rank` (1, 2 or 4) unchanged and
+ * serve all edges in ONE pass over x each; n_edges >= 1 and n_edges * rank <= 8.  x is the flat fp32
+ * parameter buffer (n elements, 16-byte aligned).  Per edge, in ascending edge order:
+ *   q, dq, msg2_*  [n_edges][msg2_len]   message 2's layout        msg1_*  [n_edges][msg1_len]
+ *   phat           [n_edges][P_total]    message 1's P part (table word 7)
+ * lo_mask: bit e is set where this worker is the LOW end of edge e (its rank is the smaller one).
+ *   choco_lowrank_gossip_project        P_e = X Q_e into msg1[e]; the uncompressed tensors' x into every
+ *                                       msg1[e]'s tail.  x is only read.  "lowrank_gossip_project_kernel".
+ *   (exchange message 1 per edge)
+ *   choco_lowrank_gossip_orthogonalize  dP_e = P_e(lo end) - P_e(hi end): own - recv where bit e is set,
+ *                                       recv - own elsewhere, one fp32 subtraction per element; phat[e] =
+ *                                       choco_lowrank_orthogonalize's Gram-Schmidt of dP_e (the same
+ *                                       arithmetic).  Neither message is written.
+ *                                       "lowrank_gossip_orth_kernel", one workgroup per (matrix, edge).
+ *   choco_lowrank_gossip_backproject    Q'_e = X^T P^_e into msg2[e].  "lowrank_gossip_backproject_kernel"
+ *                                       and, where a matrix has more than 256 rows,
+ *                                       "lowrank_gossip_slabsum_kernel".  ws:
+ *                                       choco_lowrank_gossip_workspace_size(table, n_edges) bytes.
+ *   (exchange message 2 per edge)
+ *   choco_lowrank_gossip_diff           dq[e] = Q'_e(lo end) - Q'_e(hi end), in lo_mask's order; q[e]'s
+ *                                       matrix t takes dq[e]'s unless every element of it compares equal
+ *                                       to zero (then q keeps its bits).  "lowrank_gossip_diff_kernel".
+ *   choco_lowrank_gossip_apply          compressed, per element: o_e = the column-order fmaf chain of P^_e's
+ *                                       row and dQ_e's row (choco_lowrank_decode's), u = c_0 o_0, u = fl(u +
+ *                                       fl(c_e o_e)) for e = 1.., x = fl(x + u); c_e = -(float)weights[e]
+ *                                       where bit e is set, +(float)weights[e] elsewhere.  Uncompressed:
+ *                                       u = w_0 (r_0 - x), u = fl(u + fl(w_e fl(r_e - x))), x = fl(x + u)
+ *                                       with r_e = msg1_recv[e]'s tail.  weights: n_edges doubles on the host.
+ *                                       "lowrank_gossip_apply_kernel".
+ * With both ends of an edge passing each other's messages and complementary lo_mask bits, phat[e], dq[e]
+ * and q[e] are bit-identical at the two ends and the compressed updates u are exact negations.
+ * No atomics; the same inputs give the same bits.  Every call checks its arguments before the first launch
+ * without a HIP call (choco_lowrank_project's checks, n_edges, n_edges * rank) and a bad call returns
+ * CHOCO_ERR_INVALID and launches nothing. */
+size_t choco_lowrank_gossip_workspace_size(const int64_t* plan_host, int32_t n_edges);
+int choco_lowrank_gossip_project(const float* x, const float* q, float* msg1, int64_t msg1_len, int64_t msg2_len,
+                                 const int64_t* plan_host, const int64_t* plan_dev, int64_t n, int32_t rank,
+                                 int32_t n_edges, void* stream);
+int choco_lowrank_gossip_orthogonalize(const float* msg1_own, const float* msg1_recv, int64_t msg1_len, float* phat,
+                                       uint32_t lo_mask, const int64_t* plan_host, const int64_t* plan_dev, int64_t n,
+                                       int32_t rank, int32_t n_edges, void* stream);
+int choco_lowrank_gossip_backproject(const float* x, const float* phat, int64_t msg1_len, float* msg2, int64_t msg2_len,
+                                     void* ws, size_t ws_bytes, const int64_t* plan_host, const int64_t* plan_dev,
+                                     int64_t n, int32_t rank, int32_t n_edges, void* stream);
+int choco_lowrank_gossip_diff(const float* msg2_own, const float* msg2_recv, int64_t msg1_len, int64_t msg2_len,
+                              float* q, float* dq, uint32_t lo_mask, const int64_t* plan_host, const int64_t* plan_dev,
+                              int64_t n, int32_t rank, int32_t n_edges, void* stream);
+int choco_lowrank_gossip_apply(float* x, const float* phat, const float* dq, const float* msg1_recv, int64_t msg1_len,
+                               int64_t msg2_len, const double* weights, uint32_t lo_mask, const int64_t* plan_host,
+                               const int64_t* plan_dev, int64_t n, int32_t rank, int32_t n_edges, void* stream);
+
 /* ------------------------------------------- consensus evaluation
  * The reference's --evaluate_consensus (pcode/distributed_running_cv.py:110-115, :239-243):
  * the model averaged over the workers (agg_model(copy, op="avg"),
