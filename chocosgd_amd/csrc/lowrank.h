@@ -1,12 +1,15 @@
-// What the two low-rank kernel families share (lowrank.hip: ranks 1, 2 and 4 on the vector ALUs;
-// lowrank_mfma.hip: ranks 8, 16 and 32 on the fp32 matrix instruction): the tile table's layout,
-// its builder, the check every launch makes first, and the high-rank launches' declarations.
-// lowrank_cholqr.hip (Cholesky-QR orthogonalisation at ranks 8, 16 and 32) reads the same table, and so
-// does lowrank_gossip.hip (PowerGossip, batched over a worker's edges), which also shares the
-// Gram-Schmidt sweep below with lowrank.hip.
+// What the low-rank files share.  All of them (lowrank.hip: PowerSGD at ranks 1, 2 and 4 on the vector ALUs;
+// lowrank_mfma.hip: ranks 8, 16 and 32 on the fp32 matrix instruction; lowrank_cholqr.hip: Cholesky-QR
+// orthogonalisation at ranks 8, 16 and 32; lowrank_gossip.hip: PowerGossip, batched over a worker's edges)
+// read one tile table: its layout, the check every launch makes first and the rank lists are here.
+// lowrank.hip and lowrank_gossip.hip are one kernel family, and what they have in common stands here once:
+// the Gram-Schmidt sweep, the LDS staging, the wave-per-row walk over a column block, project's matrix item,
+// the per-element product chain, and the back-project kernel, which both launch (as they do lowrank.hip's
+// slab-sum kernel).
 #pragma once
 
 #include "choco_common.h"
+#include "dispatch.h"
 
 namespace choco {
 
@@ -41,6 +44,13 @@ struct LrMat {
 CHOCO_DEV LrMat lr_mat(const int64_t* __restrict__ plan, int64_t m) {
   const int64_t* r = plan + plan[kLrOffMat] + kLrMatRow * m;
   return LrMat{r[0], r[1], r[2], r[3], r[4], r[5], r[6]};
+}
+
+// A row item that is a piece of an uncompressed tensor (it[0] < 0): project copies it into message 1's
+// tail, decode copies the summed elements back -- at every rank, so lowrank_mfma.hip calls this too.
+CHOCO_DEV void lr_copy_item(float* __restrict__ dst, int64_t doff, const float* __restrict__ src, int64_t soff,
+                            int cnt) {
+  for (int i = threadIdx.x; i < cnt; i += kLrThreads) dst[doff + i] = src[soff + i];
 }
 
 // ---------------------------------------------------------------- orthogonalise (device)
@@ -100,98 +110,198 @@ CHOCO_DEV void lr_mgs(float* __restrict__ P, int64_t rows, float* Ps, double (*r
   }
 }
 
-// ---------------------------------------------------------------- the table (host)
+// ---------------------------------------------------------------- ranks 1, 2 and 4 (device)
+// lowrank.hip and lowrank_gossip.hip: K planes of an r-column factor in LDS, CB columns at a time.  PowerSGD
+// has one factor (E = 1, K = R, CB = kLrColBlock); PowerGossip has one per edge (K = ES R, lowrank_gossip.hip).
+
+// up to four columns of all K planes: one 16-byte LDS read a plane where j is on the 16-byte grid, else
+// four words
+template <int K, int CB>
+CHOCO_DEV void lr_q4(const float* Qs, int j, bool al, float (&q)[K][4]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (al) {
+      const float4 t = *reinterpret_cast<const float4*>(Qs + k * CB + j);
+      q[k][0] = t.x; q[k][1] = t.y; q[k][2] = t.z; q[k][3] = t.w;
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) q[k][u] = Qs[k * CB + j + u];
+    }
+  }
+}
+
+// the workgroup stages columns [cb0, cb0 + nb) of every edge's (cols x R) row-major factor at
+// `src + e * stride` as planes e R .. e R + R - 1
+template <int R, int CB>
+CHOCO_DEV void lr_stage(float* Qs, const float* __restrict__ src, int64_t stride, int E, int nb) {
+  for (int e = 0; e < E; ++e) {
+    const float* __restrict__ s = src + e * stride;
+    for (int i = threadIdx.x; i < nb * R; i += kLrThreads) Qs[(e * R + i % R) * CB + i / R] = s[i];
+  }
+}
+
+// rows [row0, row0 + nrows) of every edge's P^ of matrix M (at `phat + e * stride`) as Ps[row][K]; a padded
+// slot's are zeros
+template <int ES, int R>
+CHOCO_DEV void lr_stage_rows(float* Ps, const float* __restrict__ phat, int64_t stride, const LrMat& M, int64_t row0,
+                             int nrows, int E) {
+  constexpr int K = ES * R;
+  for (int i = threadIdx.x; i < nrows * K; i += kLrThreads) {
+    const int rl = i / K, k = i % K, e = k / R;
+    Ps[i] = e < E ? phat[e * stride + M.poff + (row0 + rl) * R + k % R] : 0.0f;
+  }
+}
+
+// A wave walks the nb elements of a row from flat address a on, LDS columns 0 .. nb - 1: a scalar head up to
+// the flat buffer's 16-byte grid, 16-byte groups, a scalar tail.  one(flat index, LDS column) takes a single
+// element; group(flat index, LDS column, al) takes four on the grid and fetches their K x 4 factors itself,
+// lr_q4<K, CB>(Qs, column, al, ..), AFTER it has issued its global load (the LDS reads ahead of the load cost
+// PowerGossip's project 6 to 10 %).  The lane that gets an element depends on a and nb alone, which is what
+// fixes the order of every sum built on this walk.  The callables are lambdas marked LR_INLINE: inlined with
+// the CHOCO_DEV functions around them, before the loops are optimised, as when the walk was written out.
+#define LR_INLINE __attribute__((always_inline))
+template <typename One, typename Group>
+CHOCO_DEV void lr_row_walk(int64_t a, int nb, One one, Group group) {
+  const int lane = lane_id();
+  const int head0 = (int)((4 - (a & 3)) & 3), head = head0 < nb ? head0 : nb;
+  if (lane < head) one(a + lane, lane);
+  const int nvec = (nb - head) >> 2;
+  const bool al = head == 0;
+#pragma unroll 2
+  for (int v = lane; v < nvec; v += 64) {
+    const int j = head + 4 * v;
+    group(a + j, j, al);
+  }
+  const int j0 = head + 4 * nvec;
+  if (lane < nb - j0) one(a + j0 + lane, j0 + lane);
+}
+
+// Project's matrix item: psum[row][K] = M Q_e for the item's rows and every edge's Q (at `q + e * stride`).
+// The column blocks go through LDS in ascending order; a wave owns a row at a time, K accumulators a lane, a
+// fixed butterfly across the wave, and the blocks' sums are added in ascending order.  ld1(flat index) and
+// ld4(flat index) give one and four elements of M.  Ends on a barrier: psum is ready to be stored.
+template <int R, int K, int CB, typename Ld1, typename Ld4>
+CHOCO_DEV void lr_project_rows(float* Qs, float* psum, const float* __restrict__ q, int64_t stride, int E,
+                               const LrMat& M, int64_t row0, int nrows, Ld1 ld1, Ld4 ld4) {
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < nrows * K; i += kLrThreads) psum[i] = 0.0f;
+  for (int64_t cb0 = 0; cb0 < M.cols; cb0 += CB) {
+    const int nb = (int)(M.cols - cb0 < CB ? M.cols - cb0 : CB);
+    __syncthreads();
+    lr_stage<R, CB>(Qs, q + M.qoff + cb0 * R, stride, E, nb);
+    __syncthreads();
+    for (int rl = w; rl < nrows; rl += kLrWaves) {
+      float acc[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] = 0.0f;
+      lr_row_walk(
+          M.off + (row0 + rl) * M.cols + cb0, nb,
+          [&](int64_t i, int j) LR_INLINE {
+            const float m = ld1(i);
+#pragma unroll
+            for (int k = 0; k < K; ++k) acc[k] = fmaf(m, Qs[k * CB + j], acc[k]);
+          },
+          [&](int64_t i, int j, bool al) LR_INLINE {
+            const float4 m = ld4(i);
+            float qq[K][4];
+            lr_q4<K, CB>(Qs, j, al, qq);
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+              acc[k] = fmaf(m.w, qq[k][3], fmaf(m.z, qq[k][2], fmaf(m.y, qq[k][1], fmaf(m.x, qq[k][0], acc[k]))));
+          });
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] = wave_sum(acc[k]);
+      if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) psum[rl * K + k] += acc[k];
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// One element of P^ Q^T: the product of column 0, then one fmaf per column in ascending order -- the rounding
+// order of the contract.  q's columns are QS words apart.
+template <int R, int QS = 1>
+CHOCO_DEV float lr_chain(const float* p, const float* q) {
+  float o = p[0] * q[0];
+#pragma unroll
+  for (int c = 1; c < R; ++c) o = fmaf(p[c], q[c * QS], o);
+  return o;
+}
+
+// ---------------------------------------------------------------- back-project (ranks 1, 2 and 4)
+// Q_e = M^T P^_e for every edge, down the strided dimension: an item is kLrStrip adjacent columns (one lane
+// each: coalesced row segments) x one slab of kLrSlab rows, the slab's P^ rows of all edges in LDS (a
+// broadcast read), K = ES R accumulators a lane, the four waves interleaved over the slab's rows and joined in
+// wave order through red ([wave][k][lane]: a wave's store has no bank conflict).  A matrix of one slab writes
+// Q itself; otherwise the slab partials go to the workspace for lowrank_slabsum_kernel.  The edges' P^, Q and
+// workspaces are plan[kLrPTotal], plan[kLrMsg2] and plan[kLrWsFloats] apart; PowerSGD is the one edge whose
+// P^ is the head of message 1.
+template <int ES, int R>
+__global__ __launch_bounds__(kLrThreads) void lowrank_backproject_kernel(const float* __restrict__ x,
+                                                                         const float* __restrict__ phat,
+                                                                         float* __restrict__ msg2,
+                                                                         float* __restrict__ ws, int E,
+                                                                         const int64_t* __restrict__ plan) {
+  constexpr int K = ES * R;
+  __shared__ __attribute__((aligned(16))) float Ps[kLrSlab * K];
+  __shared__ float red[kLrWaves][K][kLrStrip];
+  const int64_t* it = plan + plan[kLrOffBp] + kLrItemRow * (int64_t)blockIdx.x;
+  const LrMat M = lr_mat(plan, it[0]);
+  const int64_t col0 = it[1], slab = it[2];
+  const int64_t row0 = slab * kLrSlab;
+  const int nrows = (int)(M.rows - row0 < kLrSlab ? M.rows - row0 : kLrSlab);
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  lr_stage_rows<ES, R>(Ps, phat, plan[kLrPTotal], M, row0, nrows, E);
+  __syncthreads();
+  const int64_t col = col0 + lane;
+  const bool active = col < M.cols;
+  float acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = 0.0f;
+  if (active) {
+    const float* __restrict__ p = x + M.off + row0 * M.cols + col;
+#pragma unroll 4
+    for (int rl = w; rl < nrows; rl += kLrWaves) {
+      const float m = p[rl * M.cols];
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] = fmaf(m, Ps[rl * K + k], acc[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) red[w][k][lane] = acc[k];
+  __syncthreads();
+  if (w == 0 && active) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e = k / R;
+      if (e >= E) continue;
+      float* dst = M.nslab == 1 ? msg2 + e * plan[kLrMsg2] + M.qoff + col * R
+                                : ws + e * plan[kLrWsFloats] + M.wsoff + (slab * M.cols + col) * R;
+      dst[k % R] = ((red[0][k][lane] + red[1][k][lane]) + red[2][k][lane]) + red[3][k][lane];
+    }
+  }
+}
+
+// Q of the matrices of more than one slab, per edge (blockIdx.y): the slab partials in ascending slab order.
+// Defined in lowrank.hip; lowrank_gossip.hip launches the same kernel with one grid row an edge.
+__global__ void lowrank_slabsum_kernel(const float* __restrict__ ws, float* __restrict__ msg2,
+                                       const int64_t* __restrict__ plan);
+
+// ---------------------------------------------------------------- ranks and the launch check (host)
 static bool lr_rank_hi(int32_t r) { return r == 8 || r == 16 || r == 32; }
 static bool lr_rank_ok(int32_t r) { return r == 1 || r == 2 || r == 4 || lr_rank_hi(r); }
 #define LR_RANKS_TEXT "rank must be 1, 2, 4, 8, 16 or 32, got %d"
 
-// Counts (plan == nullptr) or writes the table; returns its length, or a negative status.
-static int64_t lr_build(const int64_t* rows, const int64_t* lens, int32_t nseg, int32_t rank, int64_t* plan) {
-  CHOCO_REQUIRE(rows && lens, "null pointer");
-  CHOCO_REQUIRE(nseg >= 1, "nseg must be at least 1");
-  CHOCO_REQUIRE(lr_rank_ok(rank), LR_RANKS_TEXT, (int)rank);
-  int64_t n = 0;
-  for (int32_t t = 0; t < nseg; ++t) {
-    CHOCO_REQUIRE(rows[t] >= 0 && lens[t] >= 0, "tensor %d: negative size", (int)t);
-    CHOCO_REQUIRE(rows[t] == 0 || lens[t] % rows[t] == 0, "tensor %d: %lld elements are not whole rows of %lld",
-                  (int)t, (long long)lens[t], (long long)rows[t]);
-    n += lens[t];
-    CHOCO_REQUIRE(n < (int64_t)INT32_MAX, "n out of range");
-  }
-  CHOCO_REQUIRE(n > 0, "n out of range");
-  const int64_t R = rank;
-  auto compressed = [&](int32_t t) {
-    if (rows[t] == 0 || lens[t] == 0) return false;
-    const int64_t c = lens[t] / rows[t];
-    return rows[t] * c > R * (rows[t] + c);
-  };
-  auto item_rows = [&](int64_t c) {
-    const int64_t want = kLrItemElems / c;
-    if (lr_rank_hi(rank)) {  // whole 16-row tiles
-      const int64_t tiles = want / kLrTile;
-      return tiles < 1 ? (int64_t)kLrTile : tiles * kLrTile > kLrRowCap ? (int64_t)kLrRowCap : tiles * kLrTile;
-    }
-    return want < kLrWaves ? (int64_t)kLrWaves : want > kLrRowCap ? (int64_t)kLrRowCap : want;
-  };
-  int64_t ncomp = 0, nrow = 0, nbp = 0, nsum = 0;
-  for (int32_t t = 0; t < nseg; ++t) {
-    if (!compressed(t)) {
-      nrow += (lens[t] + kLrCopyChunk - 1) / kLrCopyChunk;
-      continue;
-    }
-    const int64_t r = rows[t], c = lens[t] / r, nslab = (r + kLrSlab - 1) / kLrSlab;
-    ++ncomp;
-    nrow += (r + item_rows(c) - 1) / item_rows(c);
-    nbp += nslab * ((c + kLrStrip - 1) / kLrStrip);
-    if (nslab > 1) nsum += (c * R + kLrThreads - 1) / kLrThreads;
-  }
-  const int64_t off_tensor = kLrHdrLen, off_mat = off_tensor + 4 * (int64_t)nseg, off_row = off_mat + kLrMatRow * ncomp,
-                off_bp = off_row + kLrItemRow * nrow, off_sum = off_bp + kLrItemRow * nbp,
-                total = off_sum + kLrItemRow * nsum;
-  if (!plan) return total;
-  int64_t p_total = 0;
-  for (int32_t t = 0; t < nseg; ++t)
-    if (compressed(t)) p_total += rows[t] * R;
-  int64_t *tr = plan + off_tensor, *mr = plan + off_mat, *ri = plan + off_row, *bi = plan + off_bp, *si = plan + off_sum;
-  int64_t off = 0, poff = 0, qoff = 0, tail = p_total, wsoff = 0, m = 0;
-  for (int32_t t = 0; t < nseg; ++t, tr += 4) {
-    if (!compressed(t)) {
-      tr[0] = 0; tr[1] = tail; tr[2] = -1; tr[3] = off;
-      for (int64_t o = 0; o < lens[t]; o += kLrCopyChunk, ri += kLrItemRow) {
-        ri[0] = -1; ri[1] = off + o; ri[2] = lens[t] - o < kLrCopyChunk ? lens[t] - o : kLrCopyChunk; ri[3] = tail + o;
-      }
-      tail += lens[t];
-      off += lens[t];
-      continue;
-    }
-    const int64_t r = rows[t], c = lens[t] / r, nslab = (r + kLrSlab - 1) / kLrSlab, ir = item_rows(c);
-    tr[0] = 1; tr[1] = poff; tr[2] = qoff; tr[3] = off;
-    mr[0] = off; mr[1] = r; mr[2] = c; mr[3] = poff; mr[4] = qoff; mr[5] = nslab; mr[6] = nslab > 1 ? wsoff : 0;
-    mr[7] = t;
-    mr += kLrMatRow;
-    for (int64_t r0 = 0; r0 < r; r0 += ir, ri += kLrItemRow) {
-      ri[0] = m; ri[1] = r0; ri[2] = r - r0 < ir ? r - r0 : ir; ri[3] = 0;
-    }
-    for (int64_t sl = 0; sl < nslab; ++sl)
-      for (int64_t c0 = 0; c0 < c; c0 += kLrStrip, bi += kLrItemRow) {
-        bi[0] = m; bi[1] = c0; bi[2] = sl; bi[3] = 0;
-      }
-    if (nslab > 1) {
-      for (int64_t e0 = 0; e0 < c * R; e0 += kLrThreads, si += kLrItemRow) {
-        si[0] = m; si[1] = e0; si[2] = c * R - e0 < kLrThreads ? c * R - e0 : kLrThreads; si[3] = 0;
-      }
-      wsoff += nslab * c * R;
-    }
-    poff += r * R;
-    qoff += c * R;
-    off += lens[t];
-    ++m;
-  }
-  int64_t* h = plan;
-  h[kLrMagic] = kLrMagicValue; h[kLrN] = n; h[kLrNseg] = nseg; h[kLrRank] = rank; h[kLrNcomp] = ncomp;
-  h[kLrMsg1] = tail; h[kLrMsg2] = qoff; h[kLrPTotal] = p_total; h[kLrNRow] = nrow; h[kLrNBp] = nbp; h[kLrNSum] = nsum;
-  h[kLrWsFloats] = wsoff; h[kLrOffMat] = off_mat; h[kLrOffRow] = off_row; h[kLrOffBp] = off_bp; h[kLrOffSum] = off_sum;
-  return total;
+// rank -> the kernel's instance: f(int_c<rank>) launches it (dispatch.h)
+template <typename F>
+int lr_dispatch_lo(int rank, F&& f) {
+  return dispatch_list<1, 2, 4>(rank, "rank", f);
+}
+template <typename F>
+int lr_dispatch_hi(int rank, F&& f) {
+  return dispatch_list<8, 16, 32>(rank, "rank", f);
 }
 
 // What every launch checks first, with no HIP call: the host copy of the table against the

@@ -30,36 +30,18 @@
 //     in place in global memory; a thread keeps to its own rows, so only the fp64 reductions
 //     (butterfly, then the waves in order) need barriers.
 // No atomics anywhere: every output is a function of the inputs in an order the table fixes.
-// The table's layout, its builder and the launch check are in lowrank.h, shared with lowrank_mfma.hip:
-// ranks 8, 16 and 32 run project, back-project and decode there on the fp32 matrix instruction, behind
-// the entry points below, and orthogonalise here with kLrHiOrthStage staged rows.
+// The table's layout and the launch check are in lowrank.h, and so is every loop these kernels have in
+// common with lowrank_gossip.hip's: the LDS staging, the row walk (lr_row_walk), project's matrix item
+// (lr_project_rows), the product chain (lr_chain), the Gram-Schmidt sweep (lr_mgs) and the back-project
+// kernel itself; this file keeps what is PowerSGD's own per element.  The slab-sum kernel (which
+// lowrank_gossip.hip launches too) and the table's builder are here.  Ranks 8, 16 and 32 run project,
+// back-project and decode in lowrank_mfma.hip on the fp32 matrix instruction, behind the entry points
+// below, and orthogonalise here with kLrHiOrthStage staged rows.
 #include "lowrank.h"
 
 #include <cmath>
 
 namespace choco {
-
-// a row of up to four columns' factors from the LDS planes: one 16-byte read where j is on the
-// 16-byte grid, else four words
-template <int R>
-CHOCO_DEV void lr_q4(const float* Qs, int j, bool al, float (&q)[R][4]) {
-#pragma unroll
-  for (int c = 0; c < R; ++c) {
-    if (al) {
-      const float4 t = *reinterpret_cast<const float4*>(Qs + c * kLrColBlock + j);
-      q[c][0] = t.x; q[c][1] = t.y; q[c][2] = t.z; q[c][3] = t.w;
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) q[c][u] = Qs[c * kLrColBlock + j + u];
-    }
-  }
-}
-
-// the workgroup stages columns [cb0, cb0 + nb) of a (cols x R) row-major factor as R planes
-template <int R>
-CHOCO_DEV void lr_stage(float* Qs, const float* __restrict__ src, int nb) {
-  for (int i = threadIdx.x; i < nb * R; i += kLrThreads) Qs[(i % R) * kLrColBlock + i / R] = src[i];
-}
 
 // ---------------------------------------------------------------- project
 template <int R>
@@ -70,79 +52,35 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_project_kernel(const float
   __shared__ __attribute__((aligned(16))) float Qs[R * kLrColBlock];
   __shared__ float psum[kLrRowCap * R];
   const int64_t* it = plan + plan[kLrOffRow] + kLrItemRow * (int64_t)blockIdx.x;
-  if (it[0] < 0) {  // a piece of an uncompressed tensor: into the message tail
-    const int64_t off = it[1], tail = it[3];
-    const int cnt = (int)it[2];
-    for (int i = threadIdx.x; i < cnt; i += kLrThreads) msg1[tail + i] = g[off + i];
-    return;
-  }
+  if (it[0] < 0) return lr_copy_item(msg1, it[3], g, it[1], (int)it[2]);
   const LrMat M = lr_mat(plan, it[0]);
   const int64_t row0 = it[1];
   const int nrows = (int)it[2];
-  const int lane = lane_id(), w = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < nrows * R; i += kLrThreads) psum[i] = 0.0f;
-  for (int64_t cb0 = 0; cb0 < M.cols; cb0 += kLrColBlock) {
-    const int nb = (int)(M.cols - cb0 < kLrColBlock ? M.cols - cb0 : kLrColBlock);
-    __syncthreads();
-    lr_stage<R>(Qs, q + M.qoff + cb0 * R, nb);
-    __syncthreads();
-    for (int rl = w; rl < nrows; rl += kLrWaves) {
-      const int64_t a = M.off + (row0 + rl) * M.cols + cb0;
-      const int head0 = (int)((4 - (a & 3)) & 3), head = head0 < nb ? head0 : nb;
-      float acc[R];
-#pragma unroll
-      for (int c = 0; c < R; ++c) acc[c] = 0.0f;
-      if (lane < head) {
-        const float m = g[a + lane] + e[a + lane];
-        e[a + lane] = m;
-#pragma unroll
-        for (int c = 0; c < R; ++c) acc[c] = fmaf(m, Qs[c * kLrColBlock + lane], acc[c]);
-      }
-      const int nvec = (nb - head) >> 2;
-      const bool al = head == 0;
-#pragma unroll 2
-      for (int v = lane; v < nvec; v += 64) {
-        const int j = head + 4 * v;
-        const float4 gv = ld_nt4(g + a + j);
-        const float4 ev = *reinterpret_cast<const float4*>(e + a + j);
+  lr_project_rows<R, R, kLrColBlock>(
+      Qs, psum, q, 0, 1, M, row0, nrows,
+      [&](int64_t i) LR_INLINE {
+        const float m = g[i] + e[i];
+        e[i] = m;
+        return m;
+      },
+      [&](int64_t i) LR_INLINE {
+        const float4 gv = ld_nt4(g + i);
+        const float4 ev = *reinterpret_cast<const float4*>(e + i);
         const float4 m = make_float4(gv.x + ev.x, gv.y + ev.y, gv.z + ev.z, gv.w + ev.w);
-        *reinterpret_cast<float4*>(e + a + j) = m;
-        float qq[R][4];
-        lr_q4<R>(Qs, j, al, qq);
-#pragma unroll
-        for (int c = 0; c < R; ++c)
-          acc[c] = fmaf(m.w, qq[c][3], fmaf(m.z, qq[c][2], fmaf(m.y, qq[c][1], fmaf(m.x, qq[c][0], acc[c]))));
-      }
-      const int j0 = head + 4 * nvec;
-      if (lane < nb - j0) {
-        const float m = g[a + j0 + lane] + e[a + j0 + lane];
-        e[a + j0 + lane] = m;
-#pragma unroll
-        for (int c = 0; c < R; ++c) acc[c] = fmaf(m, Qs[c * kLrColBlock + j0 + lane], acc[c]);
-      }
-#pragma unroll
-      for (int c = 0; c < R; ++c) acc[c] = wave_sum(acc[c]);
-      if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < R; ++c) psum[rl * R + c] += acc[c];
-      }
-    }
-  }
-  __syncthreads();
+        *reinterpret_cast<float4*>(e + i) = m;
+        return m;
+      });
   for (int i = threadIdx.x; i < nrows * R; i += kLrThreads) msg1[M.poff + row0 * R + i] = psum[i];
 }
 
 // ---------------------------------------------------------------- decode
 template <int R>
-CHOCO_DEV float lr_dec1(float* __restrict__ e, float* __restrict__ out, int64_t i, const float (&p)[R], const float* Qs,
-                        int j, float div) {
-  float o = p[0] * Qs[j];
-#pragma unroll
-  for (int c = 1; c < R; ++c) o = fmaf(p[c], Qs[c * kLrColBlock + j], o);
+CHOCO_DEV void lr_dec1(float* __restrict__ e, float* __restrict__ out, int64_t i, const float (&p)[R], const float* Qs,
+                       int j, float div) {
+  const float o = lr_chain<R, kLrColBlock>(p, Qs + j);
   out[i] = o;
   const float avg = o / div;
   e[i] = e[i] - avg;
-  return o;
 }
 
 template <int R>
@@ -154,95 +92,41 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_decode_kernel(float* __res
   __shared__ __attribute__((aligned(16))) float Qs[R * kLrColBlock];
   __shared__ float Ps[kLrRowCap * R];
   const int64_t* it = plan + plan[kLrOffRow] + kLrItemRow * (int64_t)blockIdx.x;
-  if (it[0] < 0) {  // the summed elements of an uncompressed tensor, back from the tail
-    const int64_t off = it[1], tail = it[3];
-    const int cnt = (int)it[2];
-    for (int i = threadIdx.x; i < cnt; i += kLrThreads) out[off + i] = msg1[tail + i];
-    return;
-  }
+  if (it[0] < 0) return lr_copy_item(out, it[1], msg1, it[3], (int)it[2]);
   const LrMat M = lr_mat(plan, it[0]);
   const int64_t row0 = it[1];
   const int nrows = (int)it[2];
-  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const int w = threadIdx.x >> 6;
   for (int i = threadIdx.x; i < nrows * R; i += kLrThreads) Ps[i] = msg1[M.poff + row0 * R + i];
   for (int64_t cb0 = 0; cb0 < M.cols; cb0 += kLrColBlock) {
     const int nb = (int)(M.cols - cb0 < kLrColBlock ? M.cols - cb0 : kLrColBlock);
     __syncthreads();
-    lr_stage<R>(Qs, msg2 + M.qoff + cb0 * R, nb);
+    lr_stage<R, kLrColBlock>(Qs, msg2 + M.qoff + cb0 * R, 0, 1, nb);
     __syncthreads();
     for (int rl = w; rl < nrows; rl += kLrWaves) {
-      const int64_t a = M.off + (row0 + rl) * M.cols + cb0;
-      const int head0 = (int)((4 - (a & 3)) & 3), head = head0 < nb ? head0 : nb;
       float p[R];
 #pragma unroll
       for (int c = 0; c < R; ++c) p[c] = Ps[rl * R + c];
-      if (lane < head) lr_dec1<R>(e, out, a + lane, p, Qs, lane, div);
-      const int nvec = (nb - head) >> 2;
-      const bool al = head == 0;
-#pragma unroll 2
-      for (int v = lane; v < nvec; v += 64) {
-        const int j = head + 4 * v;
-        const float4 m = *reinterpret_cast<const float4*>(e + a + j);
-        float qq[R][4], o[4];
-        lr_q4<R>(Qs, j, al, qq);
+      lr_row_walk(
+          M.off + (row0 + rl) * M.cols + cb0, nb,
+          [&](int64_t i, int j) LR_INLINE { lr_dec1<R>(e, out, i, p, Qs, j, div); },
+          [&](int64_t i, int j, bool al) LR_INLINE {
+            const float4 m = *reinterpret_cast<const float4*>(e + i);
+            float qq[R][4], o[4];
+            lr_q4<R, kLrColBlock>(Qs, j, al, qq);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          o[u] = p[0] * qq[0][u];
-#pragma unroll
-          for (int c = 1; c < R; ++c) o[u] = fmaf(p[c], qq[c][u], o[u]);
-        }
-        *reinterpret_cast<float4*>(out + a + j) = make_float4(o[0], o[1], o[2], o[3]);
-        *reinterpret_cast<float4*>(e + a + j) =
-            make_float4(m.x - o[0] / div, m.y - o[1] / div, m.z - o[2] / div, m.w - o[3] / div);
-      }
-      const int j0 = head + 4 * nvec;
-      if (lane < nb - j0) lr_dec1<R>(e, out, a + j0 + lane, p, Qs, j0 + lane, div);
+            for (int u = 0; u < 4; ++u) o[u] = lr_chain<R, 4>(p, &qq[0][u]);
+            *reinterpret_cast<float4*>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<float4*>(e + i) =
+                make_float4(m.x - o[0] / div, m.y - o[1] / div, m.z - o[2] / div, m.w - o[3] / div);
+          });
     }
   }
 }
 
-// ---------------------------------------------------------------- back-project
-template <int R>
-__global__ __launch_bounds__(kLrThreads) void lowrank_backproject_kernel(const float* __restrict__ Mflat,
-                                                                         const float* __restrict__ msg1,
-                                                                         float* __restrict__ msg2,
-                                                                         float* __restrict__ ws,
-                                                                         const int64_t* __restrict__ plan) {
-  __shared__ __attribute__((aligned(16))) float Ps[kLrSlab * R];
-  __shared__ float red[kLrWaves][kLrStrip][R];
-  const int64_t* it = plan + plan[kLrOffBp] + kLrItemRow * (int64_t)blockIdx.x;
-  const LrMat M = lr_mat(plan, it[0]);
-  const int64_t col0 = it[1], slab = it[2];
-  const int64_t row0 = slab * kLrSlab;
-  const int nrows = (int)(M.rows - row0 < kLrSlab ? M.rows - row0 : kLrSlab);
-  const int lane = lane_id(), w = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < nrows * R; i += kLrThreads) Ps[i] = msg1[M.poff + row0 * R + i];
-  __syncthreads();
-  const int64_t col = col0 + lane;
-  const bool active = col < M.cols;
-  float acc[R];
-#pragma unroll
-  for (int c = 0; c < R; ++c) acc[c] = 0.0f;
-  if (active) {
-    const float* __restrict__ p = Mflat + M.off + row0 * M.cols + col;
-#pragma unroll 4
-    for (int rl = w; rl < nrows; rl += kLrWaves) {
-      const float m = p[rl * M.cols];
-#pragma unroll
-      for (int c = 0; c < R; ++c) acc[c] = fmaf(m, Ps[rl * R + c], acc[c]);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < R; ++c) red[w][lane][c] = acc[c];
-  __syncthreads();
-  if (w == 0 && active) {
-    float* dst = M.nslab == 1 ? msg2 + M.qoff + col * R : ws + M.wsoff + (slab * M.cols + col) * R;
-#pragma unroll
-    for (int c = 0; c < R; ++c) dst[c] = ((red[0][lane][c] + red[1][lane][c]) + red[2][lane][c]) + red[3][lane][c];
-  }
-}
-
-// Q of the matrices of more than one slab: the slab partials in ascending slab order
+// ---------------------------------------------------------------- slab-sum
+// Q of the matrices of more than one slab, per edge (blockIdx.y; PowerSGD: one): the slab partials in
+// ascending slab order
 __global__ __launch_bounds__(kLrThreads) void lowrank_slabsum_kernel(const float* __restrict__ ws,
                                                                      float* __restrict__ msg2,
                                                                      const int64_t* __restrict__ plan) {
@@ -250,9 +134,10 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_slabsum_kernel(const float
   const LrMat M = lr_mat(plan, it[0]);
   const int64_t ne = M.cols * plan[kLrRank], i = it[1] + threadIdx.x;
   if ((int)threadIdx.x >= (int)it[2]) return;
-  float s = ws[M.wsoff + i];
-  for (int64_t sl = 1; sl < M.nslab; ++sl) s += ws[M.wsoff + sl * ne + i];
-  msg2[M.qoff + i] = s;
+  const float* __restrict__ src = ws + blockIdx.y * plan[kLrWsFloats] + M.wsoff;
+  float s = src[i];
+  for (int64_t sl = 1; sl < M.nslab; ++sl) s += src[sl * ne + i];
+  msg2[blockIdx.y * plan[kLrMsg2] + M.qoff + i] = s;
 }
 
 // ---------------------------------------------------------------- orthogonalise
@@ -272,27 +157,113 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_orth_kernel(float* __restr
   for (int i = threadIdx.x; i < ns * R; i += kLrThreads) P[i] = Ps[i];
 }
 
-// rank -> the kernel's instance
-#define LR_BY_RANK(rank, KERNEL, ...)                                                                             \
-  ((rank) == 1 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<1>, __VA_ARGS__)                                           \
-               : (rank) == 2 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<2>, __VA_ARGS__)                             \
-                             : CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<4>, __VA_ARGS__))
-// Diagnostic build only (tools/build_variants.py "lowrank_vector8"): rank 8 on the vector templates,
-// whose 64 KB Q stage still fits -- the A/B against the matrix-instruction kernels.
+// The ranks whose project, back-project and decode are the vector kernels (the others' are
+// lowrank_mfma.hip's), and rank -> the kernel's instance among them.  The diagnostic build
+// (tools/build_variants.py "lowrank_vector8") adds rank 8, whose 64 KB Q stage still fits: the A/B against
+// the matrix-instruction kernels.
+template <int... Rs>
+struct LrRanks {
+  static bool has(int rank) { return ((rank == Rs) || ...); }
+  template <typename F>
+  static int dispatch(int rank, F&& f) {
+    return dispatch_list<Rs...>(rank, "rank", f);
+  }
+};
 #ifdef CHOCO_LOWRANK_VECTOR8
-#define LR_VECTOR8(rank, KERNEL, ...) \
-  if ((rank) == 8) return CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<8>, __VA_ARGS__)
+using LrVector = LrRanks<1, 2, 4, 8>;
 #else
-#define LR_VECTOR8(rank, KERNEL, ...)
+using LrVector = LrRanks<1, 2, 4>;
 #endif
-// orthogonalise is the one kernel both families share: the same structure with fewer staged rows
-#define LR_ORTH_HI(rank, ...)                                                                                     \
-  ((rank) == 8 ? CHOCO_LAUNCH("lowrank_orth_kernel", "lowrank_orth_kernel", (lowrank_orth_kernel<8, kLrHiOrthStage>), \
-                              __VA_ARGS__)                                                                        \
-               : (rank) == 16 ? CHOCO_LAUNCH("lowrank_orth_kernel", "lowrank_orth_kernel",                        \
-                                             (lowrank_orth_kernel<16, kLrHiOrthStage>), __VA_ARGS__)              \
-                              : CHOCO_LAUNCH("lowrank_orth_kernel", "lowrank_orth_kernel",                        \
-                                             (lowrank_orth_kernel<32, kLrHiOrthStage>), __VA_ARGS__))
+
+// ---------------------------------------------------------------- the table (host)
+// Counts (plan == nullptr) or writes the table; returns its length, or a negative status.
+static int64_t lr_build(const int64_t* rows, const int64_t* lens, int32_t nseg, int32_t rank, int64_t* plan) {
+  CHOCO_REQUIRE(rows && lens, "null pointer");
+  CHOCO_REQUIRE(nseg >= 1, "nseg must be at least 1");
+  CHOCO_REQUIRE(lr_rank_ok(rank), LR_RANKS_TEXT, (int)rank);
+  int64_t n = 0;
+  for (int32_t t = 0; t < nseg; ++t) {
+    CHOCO_REQUIRE(rows[t] >= 0 && lens[t] >= 0, "tensor %d: negative size", (int)t);
+    CHOCO_REQUIRE(rows[t] == 0 || lens[t] % rows[t] == 0, "tensor %d: %lld elements are not whole rows of %lld",
+                  (int)t, (long long)lens[t], (long long)rows[t]);
+    n += lens[t];
+    CHOCO_REQUIRE(n < (int64_t)INT32_MAX, "n out of range");
+  }
+  CHOCO_REQUIRE(n > 0, "n out of range");
+  const int64_t R = rank;
+  auto compressed = [&](int32_t t) {
+    if (rows[t] == 0 || lens[t] == 0) return false;
+    const int64_t c = lens[t] / rows[t];
+    return rows[t] * c > R * (rows[t] + c);
+  };
+  auto item_rows = [&](int64_t c) {
+    const int64_t want = kLrItemElems / c;
+    if (lr_rank_hi(rank)) {  // whole 16-row tiles
+      const int64_t tiles = want / kLrTile;
+      return tiles < 1 ? (int64_t)kLrTile : tiles * kLrTile > kLrRowCap ? (int64_t)kLrRowCap : tiles * kLrTile;
+    }
+    return want < kLrWaves ? (int64_t)kLrWaves : want > kLrRowCap ? (int64_t)kLrRowCap : want;
+  };
+  int64_t ncomp = 0, nrow = 0, nbp = 0, nsum = 0;
+  for (int32_t t = 0; t < nseg; ++t) {
+    if (!compressed(t)) {
+      nrow += (lens[t] + kLrCopyChunk - 1) / kLrCopyChunk;
+      continue;
+    }
+    const int64_t r = rows[t], c = lens[t] / r, nslab = (r + kLrSlab - 1) / kLrSlab;
+    ++ncomp;
+    nrow += (r + item_rows(c) - 1) / item_rows(c);
+    nbp += nslab * ((c + kLrStrip - 1) / kLrStrip);
+    if (nslab > 1) nsum += (c * R + kLrThreads - 1) / kLrThreads;
+  }
+  const int64_t off_tensor = kLrHdrLen, off_mat = off_tensor + 4 * (int64_t)nseg, off_row = off_mat + kLrMatRow * ncomp,
+                off_bp = off_row + kLrItemRow * nrow, off_sum = off_bp + kLrItemRow * nbp,
+                total = off_sum + kLrItemRow * nsum;
+  if (!plan) return total;
+  int64_t p_total = 0;
+  for (int32_t t = 0; t < nseg; ++t)
+    if (compressed(t)) p_total += rows[t] * R;
+  int64_t *tr = plan + off_tensor, *mr = plan + off_mat, *ri = plan + off_row, *bi = plan + off_bp, *si = plan + off_sum;
+  int64_t off = 0, poff = 0, qoff = 0, tail = p_total, wsoff = 0, m = 0;
+  for (int32_t t = 0; t < nseg; ++t, tr += 4) {
+    if (!compressed(t)) {
+      tr[0] = 0; tr[1] = tail; tr[2] = -1; tr[3] = off;
+      for (int64_t o = 0; o < lens[t]; o += kLrCopyChunk, ri += kLrItemRow) {
+        ri[0] = -1; ri[1] = off + o; ri[2] = lens[t] - o < kLrCopyChunk ? lens[t] - o : kLrCopyChunk; ri[3] = tail + o;
+      }
+      tail += lens[t];
+      off += lens[t];
+      continue;
+    }
+    const int64_t r = rows[t], c = lens[t] / r, nslab = (r + kLrSlab - 1) / kLrSlab, ir = item_rows(c);
+    tr[0] = 1; tr[1] = poff; tr[2] = qoff; tr[3] = off;
+    mr[0] = off; mr[1] = r; mr[2] = c; mr[3] = poff; mr[4] = qoff; mr[5] = nslab; mr[6] = nslab > 1 ? wsoff : 0;
+    mr[7] = t;
+    mr += kLrMatRow;
+    for (int64_t r0 = 0; r0 < r; r0 += ir, ri += kLrItemRow) {
+      ri[0] = m; ri[1] = r0; ri[2] = r - r0 < ir ? r - r0 : ir; ri[3] = 0;
+    }
+    for (int64_t sl = 0; sl < nslab; ++sl)
+      for (int64_t c0 = 0; c0 < c; c0 += kLrStrip, bi += kLrItemRow) {
+        bi[0] = m; bi[1] = c0; bi[2] = sl; bi[3] = 0;
+      }
+    if (nslab > 1) {
+      for (int64_t e0 = 0; e0 < c * R; e0 += kLrThreads, si += kLrItemRow) {
+        si[0] = m; si[1] = e0; si[2] = c * R - e0 < kLrThreads ? c * R - e0 : kLrThreads; si[3] = 0;
+      }
+      wsoff += nslab * c * R;
+    }
+    poff += r * R;
+    qoff += c * R;
+    off += lens[t];
+    ++m;
+  }
+  int64_t* h = plan;
+  h[kLrMagic] = kLrMagicValue; h[kLrN] = n; h[kLrNseg] = nseg; h[kLrRank] = rank; h[kLrNcomp] = ncomp;
+  h[kLrMsg1] = tail; h[kLrMsg2] = qoff; h[kLrPTotal] = p_total; h[kLrNRow] = nrow; h[kLrNBp] = nbp; h[kLrNSum] = nsum;
+  h[kLrWsFloats] = wsoff; h[kLrOffMat] = off_mat; h[kLrOffRow] = off_row; h[kLrOffBp] = off_bp; h[kLrOffSum] = off_sum;
+  return total;
+}
 
 }  // namespace choco
 
@@ -322,9 +293,11 @@ CHOCO_API int choco_lowrank_project(const float* g, float* e, const float* q, fl
   CHOCO_REQUIRE(aligned16(g) && aligned16(e), "g and e must be 16-byte aligned");
   CHOCO_REQUIRE(aligned4(q) && aligned4(msg1), "q and msg1 must be 4-byte aligned");
   const dim3 grid((unsigned)plan_host[kLrNRow]), block(kLrThreads);
-  LR_VECTOR8(rank, lowrank_project_kernel, grid, block, as_stream(stream), g, e, q, msg1, plan_dev);
-  if (lr_rank_hi(rank)) return lr_hi_project(rank, grid, as_stream(stream), g, e, q, msg1, plan_dev);
-  return LR_BY_RANK(rank, lowrank_project_kernel, grid, block, as_stream(stream), g, e, q, msg1, plan_dev);
+  if (!LrVector::has(rank)) return lr_hi_project(rank, grid, as_stream(stream), g, e, q, msg1, plan_dev);
+  return LrVector::dispatch(rank, [&](auto R) {
+    return CHOCO_LAUNCH("lowrank_project_kernel", "lowrank_project_kernel", lowrank_project_kernel<R>, grid, block,
+                        as_stream(stream), g, e, q, msg1, plan_dev);
+  });
 }
 
 CHOCO_API int choco_lowrank_orthogonalize(float* msg1, int64_t msg1_len, const int64_t* plan_host,
@@ -334,8 +307,16 @@ CHOCO_API int choco_lowrank_orthogonalize(float* msg1, int64_t msg1_len, const i
   CHOCO_REQUIRE(aligned4(msg1), "msg1 must be 4-byte aligned");
   if (plan_host[kLrNcomp] == 0) return CHOCO_OK;
   const dim3 grid((unsigned)plan_host[kLrNcomp]), block(kLrThreads);
-  if (lr_rank_hi(rank)) return LR_ORTH_HI(rank, grid, block, as_stream(stream), msg1, plan_dev);
-  return LR_BY_RANK(rank, lowrank_orth_kernel, grid, block, as_stream(stream), msg1, plan_dev);
+  // the one kernel every rank shares, with fewer staged rows at ranks 8, 16 and 32
+  if (lr_rank_hi(rank))
+    return lr_dispatch_hi(rank, [&](auto R) {
+      return CHOCO_LAUNCH("lowrank_orth_kernel", "lowrank_orth_kernel", (lowrank_orth_kernel<R, kLrHiOrthStage>), grid,
+                          block, as_stream(stream), msg1, plan_dev);
+    });
+  return lr_dispatch_lo(rank, [&](auto R) {
+    return CHOCO_LAUNCH("lowrank_orth_kernel", "lowrank_orth_kernel", lowrank_orth_kernel<R>, grid, block,
+                        as_stream(stream), msg1, plan_dev);
+  });
 }
 
 CHOCO_API int choco_lowrank_backproject(const float* e, const float* msg1, int64_t msg1_len, float* msg2,
@@ -352,16 +333,13 @@ CHOCO_API int choco_lowrank_backproject(const float* e, const float* msg1, int64
   const hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)plan_host[kLrNBp]), block(kLrThreads);
   float* wsf = reinterpret_cast<float*>(ws);
-#ifdef CHOCO_LOWRANK_VECTOR8
-  if (rank == 8)
-    CHOCO_TRY(CHOCO_LAUNCH("lowrank_backproject_kernel", "lowrank_backproject_kernel", lowrank_backproject_kernel<8>, grid,
-                           block, st, e, msg1, msg2, wsf, plan_dev));
-  else
-#endif
-  if (lr_rank_hi(rank))
+  if (!LrVector::has(rank))
     CHOCO_TRY(lr_hi_backproject(rank, grid, st, e, msg1, msg2, wsf, plan_dev));
-  else
-    CHOCO_TRY(LR_BY_RANK(rank, lowrank_backproject_kernel, grid, block, st, e, msg1, msg2, wsf, plan_dev));
+  else  // one edge, whose P^ is the head of message 1
+    CHOCO_TRY(LrVector::dispatch(rank, [&](auto R) {
+      return CHOCO_LAUNCH("lowrank_backproject_kernel", "lowrank_backproject_kernel", (lowrank_backproject_kernel<1, R>),
+                          grid, block, st, e, msg1, msg2, wsf, 1, plan_dev);
+    }));
   if (plan_host[kLrNSum] == 0) return CHOCO_OK;
   return CHOCO_LAUNCH("lowrank_slabsum_kernel", "lowrank_slabsum_kernel", lowrank_slabsum_kernel,
                       dim3((unsigned)plan_host[kLrNSum]), block, st, (const float*)wsf, msg2, plan_dev);
@@ -379,9 +357,10 @@ CHOCO_API int choco_lowrank_decode(float* e, const float* msg1, int64_t msg1_len
   CHOCO_REQUIRE(aligned16(e) && aligned16(flat_out), "e and flat_out must be 16-byte aligned");
   CHOCO_REQUIRE(aligned4(msg1) && aligned4(msg2), "msg1 and msg2 must be 4-byte aligned");
   const dim3 grid((unsigned)plan_host[kLrNRow]), block(kLrThreads);
-  LR_VECTOR8(rank, lowrank_decode_kernel, grid, block, as_stream(stream), e, msg1, msg2, flat_out, (float)divisor, plan_dev);
-  if (lr_rank_hi(rank))
+  if (!LrVector::has(rank))
     return lr_hi_decode(rank, grid, as_stream(stream), e, msg1, msg2, flat_out, (float)divisor, plan_dev);
-  return LR_BY_RANK(rank, lowrank_decode_kernel, grid, block, as_stream(stream), e, msg1, msg2, flat_out,
-                    (float)divisor, plan_dev);
+  return LrVector::dispatch(rank, [&](auto R) {
+    return CHOCO_LAUNCH("lowrank_decode_kernel", "lowrank_decode_kernel", lowrank_decode_kernel<R>, grid, block,
+                        as_stream(stream), e, msg1, msg2, flat_out, (float)divisor, plan_dev);
+  });
 }

@@ -188,11 +188,6 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_orthapply_kernel(float* ms
   }
 }
 
-#define LR_CQ_BY_RANK(rank, KERNEL, ...)                                                     \
-  ((rank) == 8 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<8>, __VA_ARGS__)                      \
-               : (rank) == 16 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<16>, __VA_ARGS__)      \
-                              : CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<32>, __VA_ARGS__))
-
 }  // namespace choco
 
 using namespace choco;
@@ -226,7 +221,12 @@ CHOCO_API int choco_lowrank_orthogonalize_cholqr(float* msg1, int64_t msg1_len, 
   const dim3 items((unsigned)maxslab, (unsigned)ncomp), block(kLrThreads);
   double* wsd = reinterpret_cast<double*>(ws);
   const int64_t t_off = lr_cq_slots(plan_host) * rank * rank;
-  CHOCO_TRY(LR_CQ_BY_RANK(rank, lowrank_gram_kernel, items, block, st, (const float*)msg1, wsd, plan_dev));
-  CHOCO_TRY(LR_CQ_BY_RANK(rank, lowrank_chol_kernel, dim3((unsigned)ncomp), block, st, wsd, t_off, plan_dev));
-  return LR_CQ_BY_RANK(rank, lowrank_orthapply_kernel, items, block, st, msg1, (const double*)(wsd + t_off), plan_dev);
+  return lr_dispatch_hi(rank, [&](auto R) {
+    CHOCO_TRY(CHOCO_LAUNCH("lowrank_gram_kernel", "lowrank_gram_kernel", lowrank_gram_kernel<R>, items, block, st,
+                           (const float*)msg1, wsd, plan_dev));
+    CHOCO_TRY(CHOCO_LAUNCH("lowrank_chol_kernel", "lowrank_chol_kernel", lowrank_chol_kernel<R>, dim3((unsigned)ncomp),
+                           block, st, wsd, t_off, plan_dev));
+    return CHOCO_LAUNCH("lowrank_orthapply_kernel", "lowrank_orthapply_kernel", lowrank_orthapply_kernel<R>, items, block,
+                        st, msg1, (const double*)(wsd + t_off), plan_dev);
+  });
 }

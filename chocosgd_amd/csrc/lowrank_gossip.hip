@@ -17,15 +17,17 @@
 //
 // Templated on (ES, R): ES = E rounded up to 1, 2, 4 or 8 edge slots, R the rank, K = ES R <= 8
 // planes / accumulators.  A padded slot's planes are zeros in LDS and nothing of it is ever stored.
-//   * project: the wave-per-row walk of lowrank_project_kernel (16-byte loads on the flat buffer's
-//     16-byte grid, scalar head and tail, a fixed butterfly, the column blocks' sums added in
-//     ascending order) with all E Qs' column blocks in LDS as K planes; the block is 2048 columns
-//     up to K = 4 and 1024 at K = 8 (K planes x block x 4 B = 32 KB beside the 8 KB of row sums).
-//   * back-project: 64 columns x one 256-row slab an item, the slab's P^ rows of all edges in LDS
-//     (a broadcast read), K accumulators a lane, the four waves joined in wave order, slab partials
-//     summed in ascending slab order by lowrank_gossip_slabsum_kernel.
-//   * apply: K planes of dQ through LDS in the same column blocks, the item's P^ rows of all edges
-//     in LDS; per element each edge's product is lr_dec1's column-order fmaf chain, then
+//   * project: PowerSGD's project on K planes (lowrank.h, lr_project_rows: the wave-per-row walk with
+//     16-byte loads on the flat buffer's 16-byte grid, scalar head and tail, a fixed butterfly, the
+//     column blocks' sums added in ascending order) with all E Qs' column blocks in LDS; the block is
+//     2048 columns up to K = 4 and 1024 at K = 8 (K planes x block x 4 B = 32 KB beside the 8 KB of row
+//     sums).
+//   * back-project: PowerSGD's kernel and slab-sum kernel themselves (lowrank.h,
+//     lowrank_backproject_kernel<ES, R>; PowerSGD is its one-edge instance): 64 columns x one 256-row slab
+//     an item, the slab's P^ rows of all edges in LDS, K accumulators a lane, slab partials summed in
+//     ascending slab order by a grid of (items, E).
+//   * apply: K planes of dQ through LDS in the same column blocks and the same walk (lr_row_walk), the
+//     item's P^ rows of all edges in LDS; per element each edge's product is lr_chain, decode's, then
 //     u = c_0 o_0, u = u + c_e o_e in ascending e (a multiply and an add, not fused), x = x + u.
 //     c_e = -w_e at the edge's low end and +w_e at its high end: with bit-identical P^_e and dQ_e at
 //     both ends (orthogonalise and diff see the same operands in the same order) the two ends'
@@ -45,42 +47,6 @@ constexpr int lg_slots(int E) { return E <= 1 ? 1 : E <= 2 ? 2 : E <= 4 ? 4 : 8;
 struct LgWeights {
   float c[kLgMaxK], w[kLgMaxK];
 };
-
-// up to four columns of all K planes: one 16-byte LDS read a plane where j is on the 16-byte grid
-template <int K, int CB>
-CHOCO_DEV void lg_q4(const float* Qs, int j, bool al, float (&q)[K][4]) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    if (al) {
-      const float4 t = *reinterpret_cast<const float4*>(Qs + k * CB + j);
-      q[k][0] = t.x; q[k][1] = t.y; q[k][2] = t.z; q[k][3] = t.w;
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) q[k][u] = Qs[k * CB + j + u];
-    }
-  }
-}
-
-// the workgroup stages columns [cb0, cb0 + nb) of every edge's (cols x R) row-major factor at
-// `src + e * stride` as planes e R .. e R + R - 1
-template <int R, int CB>
-CHOCO_DEV void lg_stage(float* Qs, const float* __restrict__ src, int64_t stride, int E, int nb) {
-  for (int e = 0; e < E; ++e) {
-    const float* __restrict__ s = src + e * stride;
-    for (int i = threadIdx.x; i < nb * R; i += kLrThreads) Qs[(e * R + i % R) * CB + i / R] = s[i];
-  }
-}
-
-// rows [row0, row0 + nrows) of every edge's P^ of matrix M as Ps[row][K]; a padded slot's are zeros
-template <int ES, int R>
-CHOCO_DEV void lg_stage_rows(float* Ps, const float* __restrict__ phat, int64_t p_total, const LrMat& M, int64_t row0,
-                             int nrows, int E) {
-  constexpr int K = ES * R;
-  for (int i = threadIdx.x; i < nrows * K; i += kLrThreads) {
-    const int rl = i / K, k = i % K, e = k / R;
-    Ps[i] = e < E ? phat[e * p_total + M.poff + (row0 + rl) * R + k % R] : 0.0f;
-  }
-}
 
 // ---------------------------------------------------------------- project
 template <int ES, int R>
@@ -105,52 +71,10 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_gossip_project_kernel(cons
   const LrMat M = lr_mat(plan, it[0]);
   const int64_t row0 = it[1];
   const int nrows = (int)it[2];
-  const int lane = lane_id(), w = threadIdx.x >> 6;
   for (int i = E * R * CB + threadIdx.x; i < K * CB; i += kLrThreads) Qs[i] = 0.0f;  // the padded slots' planes
-  for (int i = threadIdx.x; i < nrows * K; i += kLrThreads) psum[i] = 0.0f;
-  for (int64_t cb0 = 0; cb0 < M.cols; cb0 += CB) {
-    const int nb = (int)(M.cols - cb0 < CB ? M.cols - cb0 : CB);
-    __syncthreads();
-    lg_stage<R, CB>(Qs, q + M.qoff + cb0 * R, m2, E, nb);
-    __syncthreads();
-    for (int rl = w; rl < nrows; rl += kLrWaves) {
-      const int64_t a = M.off + (row0 + rl) * M.cols + cb0;
-      const int head0 = (int)((4 - (a & 3)) & 3), head = head0 < nb ? head0 : nb;
-      float acc[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) acc[k] = 0.0f;
-      if (lane < head) {
-        const float m = x[a + lane];
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc[k] = fmaf(m, Qs[k * CB + lane], acc[k]);
-      }
-      const int nvec = (nb - head) >> 2;
-      const bool al = head == 0;
-#pragma unroll 2
-      for (int v = lane; v < nvec; v += 64) {
-        const int j = head + 4 * v;
-        const float4 m = *reinterpret_cast<const float4*>(x + a + j);
-        float qq[K][4];
-        lg_q4<K, CB>(Qs, j, al, qq);
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-          acc[k] = fmaf(m.w, qq[k][3], fmaf(m.z, qq[k][2], fmaf(m.y, qq[k][1], fmaf(m.x, qq[k][0], acc[k]))));
-      }
-      const int j0 = head + 4 * nvec;
-      if (lane < nb - j0) {
-        const float m = x[a + j0 + lane];
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc[k] = fmaf(m, Qs[k * CB + j0 + lane], acc[k]);
-      }
-#pragma unroll
-      for (int k = 0; k < K; ++k) acc[k] = wave_sum(acc[k]);
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) psum[rl * K + k] += acc[k];
-      }
-    }
-  }
-  __syncthreads();
+  lr_project_rows<R, K, CB>(
+      Qs, psum, q, m2, E, M, row0, nrows, [&](int64_t i) LR_INLINE { return x[i]; },
+      [&](int64_t i) LR_INLINE { return *reinterpret_cast<const float4*>(x + i); });
   for (int i = threadIdx.x; i < nrows * K; i += kLrThreads) {
     const int rl = i / K, k = i % K, e = k / R;
     if (e < E) msg1[e * m1 + M.poff + (row0 + rl) * R + k % R] = psum[i];
@@ -186,67 +110,6 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_gossip_orth_kernel(const f
   for (int i = threadIdx.x; i < ns * R; i += kLrThreads) P[i] = Ps[i];
 }
 
-// ---------------------------------------------------------------- back-project
-template <int ES, int R>
-__global__ __launch_bounds__(kLrThreads) void lowrank_gossip_backproject_kernel(const float* __restrict__ x,
-                                                                                const float* __restrict__ phat,
-                                                                                float* __restrict__ msg2,
-                                                                                float* __restrict__ ws, int E,
-                                                                                const int64_t* __restrict__ plan) {
-  constexpr int K = ES * R;
-  __shared__ __attribute__((aligned(16))) float Ps[kLrSlab * K];
-  __shared__ float red[kLrWaves][K][kLrStrip];
-  const int64_t* it = plan + plan[kLrOffBp] + kLrItemRow * (int64_t)blockIdx.x;
-  const LrMat M = lr_mat(plan, it[0]);
-  const int64_t col0 = it[1], slab = it[2];
-  const int64_t row0 = slab * kLrSlab;
-  const int nrows = (int)(M.rows - row0 < kLrSlab ? M.rows - row0 : kLrSlab);
-  const int lane = lane_id(), w = threadIdx.x >> 6;
-  lg_stage_rows<ES, R>(Ps, phat, plan[kLrPTotal], M, row0, nrows, E);
-  __syncthreads();
-  const int64_t col = col0 + lane;
-  const bool active = col < M.cols;
-  float acc[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) acc[k] = 0.0f;
-  if (active) {
-    const float* __restrict__ p = x + M.off + row0 * M.cols + col;
-#pragma unroll 4
-    for (int rl = w; rl < nrows; rl += kLrWaves) {
-      const float m = p[rl * M.cols];
-#pragma unroll
-      for (int k = 0; k < K; ++k) acc[k] = fmaf(m, Ps[rl * K + k], acc[k]);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < K; ++k) red[w][k][lane] = acc[k];
-  __syncthreads();
-  if (w == 0 && active) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const int e = k / R;
-      if (e >= E) continue;
-      float* dst = M.nslab == 1 ? msg2 + e * plan[kLrMsg2] + M.qoff + col * R
-                                : ws + e * plan[kLrWsFloats] + M.wsoff + (slab * M.cols + col) * R;
-      dst[k % R] = ((red[0][k][lane] + red[1][k][lane]) + red[2][k][lane]) + red[3][k][lane];
-    }
-  }
-}
-
-// Q' of the matrices of more than one slab, per edge (blockIdx.y): the slab partials in ascending order
-__global__ __launch_bounds__(kLrThreads) void lowrank_gossip_slabsum_kernel(const float* __restrict__ ws,
-                                                                            float* __restrict__ msg2,
-                                                                            const int64_t* __restrict__ plan) {
-  const int64_t* it = plan + plan[kLrOffSum] + kLrItemRow * (int64_t)blockIdx.x;
-  const LrMat M = lr_mat(plan, it[0]);
-  const int64_t ne = M.cols * plan[kLrRank], i = it[1] + threadIdx.x;
-  if ((int)threadIdx.x >= (int)it[2]) return;
-  const float* __restrict__ src = ws + blockIdx.y * plan[kLrWsFloats] + M.wsoff;
-  float s = src[i];
-  for (int64_t sl = 1; sl < M.nslab; ++sl) s += src[sl * ne + i];
-  msg2[blockIdx.y * plan[kLrMsg2] + M.qoff + i] = s;
-}
-
 // ---------------------------------------------------------------- diff
 // one workgroup per (matrix, edge): dQ = Q'(lo end) - Q'(hi end) into dq; the edge's Q state takes
 // it unless every element is zero (an edge that once agrees exactly would otherwise be dead for good)
@@ -280,10 +143,7 @@ CHOCO_DEV float lg_update(const float (&p)[ES * R], const float (&qc)[ES * R], c
 #pragma unroll
   for (int e = 0; e < ES; ++e) {
     if (e < E) {
-      float o = p[e * R] * qc[e * R];
-#pragma unroll
-      for (int c = 1; c < R; ++c) o = fmaf(p[e * R + c], qc[e * R + c], o);
-      const float t = W.c[e] * o;
+      const float t = W.c[e] * lr_chain<R>(p + e * R, qc + e * R);
       u = e == 0 ? t : u + t;
     }
   }
@@ -316,85 +176,54 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_gossip_apply_kernel(float*
   const LrMat M = lr_mat(plan, it[0]);
   const int64_t row0 = it[1];
   const int nrows = (int)it[2];
-  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const int w = threadIdx.x >> 6;
   for (int i = E * R * CB + threadIdx.x; i < K * CB; i += kLrThreads) Qs[i] = 0.0f;  // the padded slots' planes
-  lg_stage_rows<ES, R>(Ps, phat, plan[kLrPTotal], M, row0, nrows, E);
+  lr_stage_rows<ES, R>(Ps, phat, plan[kLrPTotal], M, row0, nrows, E);
   for (int64_t cb0 = 0; cb0 < M.cols; cb0 += CB) {
     const int nb = (int)(M.cols - cb0 < CB ? M.cols - cb0 : CB);
     __syncthreads();
-    lg_stage<R, CB>(Qs, dq + M.qoff + cb0 * R, plan[kLrMsg2], E, nb);
+    lr_stage<R, CB>(Qs, dq + M.qoff + cb0 * R, plan[kLrMsg2], E, nb);
     __syncthreads();
     for (int rl = w; rl < nrows; rl += kLrWaves) {
-      const int64_t a = M.off + (row0 + rl) * M.cols + cb0;
-      const int head0 = (int)((4 - (a & 3)) & 3), head = head0 < nb ? head0 : nb;
-      float p[K], qc[K];
+      float p[K];
 #pragma unroll
       for (int k = 0; k < K; ++k) p[k] = Ps[rl * K + k];
-      if (lane < head) {
+      lr_row_walk(
+          M.off + (row0 + rl) * M.cols + cb0, nb,
+          [&](int64_t i, int j) LR_INLINE {
+            float qc[K];
 #pragma unroll
-        for (int k = 0; k < K; ++k) qc[k] = Qs[k * CB + lane];
-        x[a + lane] = x[a + lane] + lg_update<ES, R>(p, qc, W, E);
-      }
-      const int nvec = (nb - head) >> 2;
-      const bool al = head == 0;
-#pragma unroll 2
-      for (int v = lane; v < nvec; v += 64) {
-        const int j = head + 4 * v;
-        const float4 m = *reinterpret_cast<const float4*>(x + a + j);
-        float qq[K][4], o[4];
-        lg_q4<K, CB>(Qs, j, al, qq);
+            for (int k = 0; k < K; ++k) qc[k] = Qs[k * CB + j];
+            x[i] = x[i] + lg_update<ES, R>(p, qc, W, E);
+          },
+          [&](int64_t i, int j, bool al) LR_INLINE {
+            const float4 m = *reinterpret_cast<const float4*>(x + i);
+            float qq[K][4], qc[K], o[4];
+            lr_q4<K, CB>(Qs, j, al, qq);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+            for (int u = 0; u < 4; ++u) {
 #pragma unroll
-          for (int k = 0; k < K; ++k) qc[k] = qq[k][u];
-          o[u] = lg_update<ES, R>(p, qc, W, E);
-        }
-        *reinterpret_cast<float4*>(x + a + j) = make_float4(m.x + o[0], m.y + o[1], m.z + o[2], m.w + o[3]);
-      }
-      const int j0 = head + 4 * nvec;
-      if (lane < nb - j0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) qc[k] = Qs[k * CB + j0 + lane];
-        x[a + j0 + lane] = x[a + j0 + lane] + lg_update<ES, R>(p, qc, W, E);
-      }
+              for (int k = 0; k < K; ++k) qc[k] = qq[k][u];
+              o[u] = lg_update<ES, R>(p, qc, W, E);
+            }
+            *reinterpret_cast<float4*>(x + i) = make_float4(m.x + o[0], m.y + o[1], m.z + o[2], m.w + o[3]);
+          });
     }
   }
 }
 
 // ---------------------------------------------------------------- launches
-// (edge slots, rank) -> the kernel's instance; the nine pairs with ES R <= 8
-#define LG_CASE(ES_, R_, KERNEL, ...) \
-  if (es == ES_ && rank == R_) return CHOCO_LAUNCH(#KERNEL, #KERNEL, (KERNEL<ES_, R_>), __VA_ARGS__)
-#define LG_LAUNCH(KERNEL, ...)                 \
-  do {                                         \
-    const int es = lg_slots(E);                \
-    LG_CASE(1, 1, KERNEL, __VA_ARGS__);        \
-    LG_CASE(2, 1, KERNEL, __VA_ARGS__);        \
-    LG_CASE(4, 1, KERNEL, __VA_ARGS__);        \
-    LG_CASE(8, 1, KERNEL, __VA_ARGS__);        \
-    LG_CASE(1, 2, KERNEL, __VA_ARGS__);        \
-    LG_CASE(2, 2, KERNEL, __VA_ARGS__);        \
-    LG_CASE(4, 2, KERNEL, __VA_ARGS__);        \
-    LG_CASE(1, 4, KERNEL, __VA_ARGS__);        \
-    LG_CASE(2, 4, KERNEL, __VA_ARGS__);        \
-    return fail(CHOCO_ERR_INVALID, "no instance for %d edges at rank %d", (int)E, (int)rank); \
-  } while (0)
-#define LG_BY_RANK(rank, KERNEL, ...)                                                   \
-  ((rank) == 1 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<1>, __VA_ARGS__)                 \
-               : (rank) == 2 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<2>, __VA_ARGS__)   \
-                             : CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<4>, __VA_ARGS__))
-
-static int lg_project(int32_t rank, int E, dim3 grid, hipStream_t st, const float* x, const float* q, float* msg1,
-                      const int64_t* plan) {
-  LG_LAUNCH(lowrank_gossip_project_kernel, grid, dim3(kLrThreads), st, x, q, msg1, E, plan);
-}
-static int lg_backproject(int32_t rank, int E, dim3 grid, hipStream_t st, const float* x, const float* phat, float* msg2,
-                          float* ws, const int64_t* plan) {
-  LG_LAUNCH(lowrank_gossip_backproject_kernel, grid, dim3(kLrThreads), st, x, phat, msg2, ws, E, plan);
-}
-static int lg_apply(int32_t rank, int E, dim3 grid, hipStream_t st, float* x, const float* phat, const float* dq,
-                    const float* recv1, LgWeights W, const int64_t* plan) {
-  LG_LAUNCH(lowrank_gossip_apply_kernel, grid, dim3(kLrThreads), st, x, phat, dq, recv1, W, E, plan);
+// (edge slots, rank) -> the kernel's instance, f(int_c<ES>, int_c<R>): the nine pairs with ES R <= 8
+template <typename F>
+int lg_dispatch(int32_t rank, int E, F&& f) {
+  return dispatch_list<1, 2, 4, 8>(lg_slots(E), "edge slots", [&](auto ES) {
+    return lr_dispatch_lo(rank, [&](auto R) {
+      if constexpr (ES * R <= kLgMaxK)
+        return f(ES, R);
+      else
+        return fail(CHOCO_ERR_INVALID, "no instance for %d edges at rank %d", (int)E, (int)rank);
+    });
+  });
 }
 
 // what every gossip launch checks first: lr_check, then the width
@@ -426,7 +255,11 @@ CHOCO_API int choco_lowrank_gossip_project(const float* x, const float* q, float
   CHOCO_REQUIRE(q || plan_host[kLrMsg2] == 0, "null pointer");
   CHOCO_REQUIRE(aligned16(x), "x must be 16-byte aligned");
   CHOCO_REQUIRE(aligned4(q) && aligned4(msg1), "q and msg1 must be 4-byte aligned");
-  return lg_project(rank, n_edges, dim3((unsigned)plan_host[kLrNRow]), as_stream(stream), x, q, msg1, plan_dev);
+  return lg_dispatch(rank, n_edges, [&](auto ES, auto R) {
+    return CHOCO_LAUNCH("lowrank_gossip_project_kernel", "lowrank_gossip_project_kernel",
+                        (lowrank_gossip_project_kernel<ES, R>), dim3((unsigned)plan_host[kLrNRow]), dim3(kLrThreads),
+                        as_stream(stream), x, q, msg1, n_edges, plan_dev);
+  });
 }
 
 CHOCO_API int choco_lowrank_gossip_orthogonalize(const float* msg1_own, const float* msg1_recv, int64_t msg1_len,
@@ -439,8 +272,10 @@ CHOCO_API int choco_lowrank_gossip_orthogonalize(const float* msg1_own, const fl
   CHOCO_REQUIRE(phat, "null pointer");
   CHOCO_REQUIRE(aligned4(msg1_own) && aligned4(msg1_recv) && aligned4(phat), "misaligned pointer");
   const dim3 grid((unsigned)plan_host[kLrNcomp], (unsigned)n_edges), block(kLrThreads);
-  return LG_BY_RANK(rank, lowrank_gossip_orth_kernel, grid, block, as_stream(stream), msg1_own, msg1_recv, phat, lo_mask,
-                    plan_dev);
+  return lr_dispatch_lo(rank, [&](auto R) {
+    return CHOCO_LAUNCH("lowrank_gossip_orth_kernel", "lowrank_gossip_orth_kernel", lowrank_gossip_orth_kernel<R>, grid,
+                        block, as_stream(stream), msg1_own, msg1_recv, phat, lo_mask, plan_dev);
+  });
 }
 
 CHOCO_API int choco_lowrank_gossip_backproject(const float* x, const float* phat, int64_t msg1_len, float* msg2,
@@ -458,9 +293,13 @@ CHOCO_API int choco_lowrank_gossip_backproject(const float* x, const float* phat
   CHOCO_REQUIRE(aligned4(x) && aligned4(phat) && aligned4(msg2) && aligned16(ws), "misaligned pointer");
   const hipStream_t st = as_stream(stream);
   float* wsf = reinterpret_cast<float*>(ws);
-  CHOCO_TRY(lg_backproject(rank, n_edges, dim3((unsigned)plan_host[kLrNBp]), st, x, phat, msg2, wsf, plan_dev));
+  CHOCO_TRY(lg_dispatch(rank, n_edges, [&](auto ES, auto R) {
+    return CHOCO_LAUNCH("lowrank_gossip_backproject_kernel", "lowrank_gossip_backproject_kernel",
+                        (lowrank_backproject_kernel<ES, R>), dim3((unsigned)plan_host[kLrNBp]), dim3(kLrThreads), st, x,
+                        phat, msg2, wsf, n_edges, plan_dev);
+  }));
   if (plan_host[kLrNSum] == 0) return CHOCO_OK;
-  return CHOCO_LAUNCH("lowrank_gossip_slabsum_kernel", "lowrank_gossip_slabsum_kernel", lowrank_gossip_slabsum_kernel,
+  return CHOCO_LAUNCH("lowrank_gossip_slabsum_kernel", "lowrank_gossip_slabsum_kernel", lowrank_slabsum_kernel,
                       dim3((unsigned)plan_host[kLrNSum], (unsigned)n_edges), dim3(kLrThreads), st, (const float*)wsf,
                       msg2, plan_dev);
 }
@@ -475,8 +314,10 @@ CHOCO_API int choco_lowrank_gossip_diff(const float* msg2_own, const float* msg2
   CHOCO_REQUIRE(msg2_own && msg2_recv && q && dq, "null pointer");
   CHOCO_REQUIRE(aligned4(msg2_own) && aligned4(msg2_recv) && aligned4(q) && aligned4(dq), "misaligned pointer");
   const dim3 grid((unsigned)plan_host[kLrNcomp], (unsigned)n_edges), block(kLrThreads);
-  return LG_BY_RANK(rank, lowrank_gossip_diff_kernel, grid, block, as_stream(stream), msg2_own, msg2_recv, q, dq, lo_mask,
-                    plan_dev);
+  return lr_dispatch_lo(rank, [&](auto R) {
+    return CHOCO_LAUNCH("lowrank_gossip_diff_kernel", "lowrank_gossip_diff_kernel", lowrank_gossip_diff_kernel<R>, grid,
+                        block, as_stream(stream), msg2_own, msg2_recv, q, dq, lo_mask, plan_dev);
+  });
 }
 
 CHOCO_API int choco_lowrank_gossip_apply(float* x, const float* phat, const float* dq, const float* msg1_recv,
@@ -495,6 +336,9 @@ CHOCO_API int choco_lowrank_gossip_apply(float* x, const float* phat, const floa
     W.w[e] = (float)weights[e];
     W.c[e] = (lo_mask >> e) & 1u ? -W.w[e] : W.w[e];
   }
-  return lg_apply(rank, n_edges, dim3((unsigned)plan_host[kLrNRow]), as_stream(stream), x, phat, dq, msg1_recv, W,
-                  plan_dev);
+  return lg_dispatch(rank, n_edges, [&](auto ES, auto R) {
+    return CHOCO_LAUNCH("lowrank_gossip_apply_kernel", "lowrank_gossip_apply_kernel", (lowrank_gossip_apply_kernel<ES, R>),
+                        dim3((unsigned)plan_host[kLrNRow]), dim3(kLrThreads), as_stream(stream), x, phat, dq, msg1_recv, W,
+                        n_edges, plan_dev);
+  });
 }

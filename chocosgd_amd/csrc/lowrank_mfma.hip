@@ -11,8 +11,9 @@
 // 16-wide result tiles; rank 8 is one whose upper eight rank columns are fed zeros (free in a
 // loop that waits for memory).
 //
-// The table, the messages, the slab scheme, lowrank_slabsum_kernel and orthogonalise are
-// lowrank.hip's; a row item is whole 16-row tiles here.  Q goes through LDS in blocks of
+// The table, the messages, the slab scheme, lowrank_slabsum_kernel, orthogonalise and the copy of an
+// uncompressed tensor's piece (lr_copy_item) are lowrank.hip's and lowrank.h's; a row item is whole
+// 16-row tiles here.  Q goes through LDS in blocks of
 // kLrHiColBlock columns in the message's own [col][r] layout, the row stride padded by 4 words so
 // that the lanes of a read fall on 64 different banks.  A lane (i, kq) always touches M in
 // 16-byte groups of four consecutive columns, a row's 64 columns (project, decode) or a row's 64
@@ -160,12 +161,7 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_project_mfma_kernel(const 
   __shared__ float Qs[kLrHiColBlock * LrHi<R>::QS];
   __shared__ float red[kLrWaves * kLrTile * LrHi<R>::RN];
   const int64_t* it = plan + plan[kLrOffRow] + kLrItemRow * (int64_t)blockIdx.x;
-  if (it[0] < 0) {  // a piece of an uncompressed tensor: into the message tail
-    const int64_t off = it[1], tail = it[3];
-    const int cnt = (int)it[2];
-    for (int i = threadIdx.x; i < cnt; i += kLrThreads) msg1[tail + i] = g[off + i];
-    return;
-  }
+  if (it[0] < 0) return lr_copy_item(msg1, it[3], g, it[1], (int)it[2]);
   const LrMat M = lr_mat(plan, it[0]);
   if (lr_rows_aligned(g, M) && lr_rows_aligned(e, M))
     lr_project_item<R, true>(g, e, q, msg1, M, it[1], (int)it[2], Qs, red);
@@ -223,12 +219,7 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_decode_mfma_kernel(float* 
                                                                          const int64_t* __restrict__ plan) {
   __shared__ float Qs[kLrHiColBlock * LrHi<R>::QS];
   const int64_t* it = plan + plan[kLrOffRow] + kLrItemRow * (int64_t)blockIdx.x;
-  if (it[0] < 0) {  // the summed elements of an uncompressed tensor, back from the tail
-    const int64_t off = it[1], tail = it[3];
-    const int cnt = (int)it[2];
-    for (int i = threadIdx.x; i < cnt; i += kLrThreads) out[off + i] = msg1[tail + i];
-    return;
-  }
+  if (it[0] < 0) return lr_copy_item(out, it[1], msg1, it[3], (int)it[2]);
   const LrMat M = lr_mat(plan, it[0]);
   if (lr_rows_aligned(e, M) && lr_rows_aligned(out, M))
     lr_decode_item<R, true>(e, msg1, msg2, out, div, M, it[1], (int)it[2], Qs);
@@ -309,24 +300,28 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_backproject_mfma_kernel(co
 }
 
 // ---------------------------------------------------------------- the launches
-#define LR_HI_BY_RANK(rank, KERNEL, ...)                                                     \
-  ((rank) == 8 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<8>, __VA_ARGS__)                      \
-               : (rank) == 16 ? CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<16>, __VA_ARGS__)      \
-                              : CHOCO_LAUNCH(#KERNEL, #KERNEL, KERNEL<32>, __VA_ARGS__))
-
 int lr_hi_project(int32_t rank, dim3 grid, hipStream_t st, const float* g, float* e, const float* q, float* msg1,
                   const int64_t* plan) {
-  return LR_HI_BY_RANK(rank, lowrank_project_mfma_kernel, grid, dim3(kLrThreads), st, g, e, q, msg1, plan);
+  return lr_dispatch_hi(rank, [&](auto R) {
+    return CHOCO_LAUNCH("lowrank_project_mfma_kernel", "lowrank_project_mfma_kernel", lowrank_project_mfma_kernel<R>, grid,
+                        dim3(kLrThreads), st, g, e, q, msg1, plan);
+  });
 }
 
 int lr_hi_backproject(int32_t rank, dim3 grid, hipStream_t st, const float* e, const float* msg1, float* msg2, float* ws,
                       const int64_t* plan) {
-  return LR_HI_BY_RANK(rank, lowrank_backproject_mfma_kernel, grid, dim3(kLrThreads), st, e, msg1, msg2, ws, plan);
+  return lr_dispatch_hi(rank, [&](auto R) {
+    return CHOCO_LAUNCH("lowrank_backproject_mfma_kernel", "lowrank_backproject_mfma_kernel",
+                        lowrank_backproject_mfma_kernel<R>, grid, dim3(kLrThreads), st, e, msg1, msg2, ws, plan);
+  });
 }
 
 int lr_hi_decode(int32_t rank, dim3 grid, hipStream_t st, float* e, const float* msg1, const float* msg2, float* out,
                  float div, const int64_t* plan) {
-  return LR_HI_BY_RANK(rank, lowrank_decode_mfma_kernel, grid, dim3(kLrThreads), st, e, msg1, msg2, out, div, plan);
+  return lr_dispatch_hi(rank, [&](auto R) {
+    return CHOCO_LAUNCH("lowrank_decode_mfma_kernel", "lowrank_decode_mfma_kernel", lowrank_decode_mfma_kernel<R>, grid,
+                        dim3(kLrThreads), st, e, msg1, msg2, out, div, plan);
+  });
 }
 
 }  // namespace choco

@@ -143,6 +143,34 @@ def test_two_endpoints(r):
     assert not torch.equal(Q[0], flat(a["q"]))
 
 
+# odd column counts (rows off the 16-byte grid: head and tail run); 2049 columns, one over the LDS column block;
+# 257 rows, two slabs (the slab sum runs); one uncompressed tensor
+ONE_EDGE_SHAPES = [(7,), (9, 11), (7, 257), (5, 5), (5, 2049), (257, 6)]
+
+
+@pytest.mark.parametrize("r", [1, 2, 4])
+def test_one_edge_is_powersgd(r):
+    """At one edge PowerGossip's passes are PowerSGD's (codec.LowRankPlan on the same table): the same row walk, the
+    same back-project and slab-sum kernels, the same product chain, so the same bits."""
+    gossip, L, _, _, a = setup(r, 1, ONE_EDGE_SHAPES, seed=6)
+    sgd, x, q, phat, dq, recv1 = gossip.table, a["x"], a["q"][0], a["phat"][0], a["dq"][0], a["recv1"][0]
+    msg1 = np.concatenate([phat, recv1[gossip.p_total:]])  # [P^ | anything]
+    got, want = sentinel(1, L.msg1_len), sentinel(1, L.msg1_len)
+    gossip.project(dev(x), dev(q), got)
+    sgd.project(dev(x), torch.zeros(L.n, device=DEV), dev(q), want)  # M = x + 0
+    assert same_bits(got.cpu().numpy(), want.cpu().numpy()), "project: the whole of message 1"
+    got, want = sentinel(1, L.msg2_len), sentinel(1, L.msg2_len)
+    gossip.backproject(dev(x), dev(phat), got)
+    sgd.backproject(dev(x), dev(msg1), want)
+    assert same_bits(got.cpu().numpy(), want.cpu().numpy()), "back-project"
+    # apply at the low end with weight 1 (c = -1) against decode with divisor 1: -1 * o and o / 1 are exact
+    got, want = dev(x), dev(x)
+    gossip.apply(got, dev(phat), dev(dq), dev(recv1), [1.0], 1)
+    sgd.decode(want, dev(msg1), dev(dq), sentinel(1, L.n), 1.0)
+    got, want = got.cpu().numpy(), want.cpu().numpy()
+    assert all(same_bits(got[f], want[f]) for f, *_ in L.matrices()), "apply against decode, the compressed matrices"
+
+
 class Peers:
     """Worker 1's exchange: prepared Gaussian peer messages, the same values for every model."""
     rank = 1
