@@ -198,6 +198,17 @@ SIGNATURES = {
                                            _c_i32, _c_i32, _vp]),
     "choco_lowrank_gossip_apply": (_c_i32, [_vp, _vp, _vp, _vp, _c_i64, _c_i64, _p_f64, ctypes.c_uint32, _p_i64, _vp,
                                             _c_i64, _c_i32, _c_i32, _vp]),
+    "choco_lowrank_gossip_wide_workspace_size": (_c_sz, [_p_i64, _c_i32]),
+    "choco_lowrank_gossip_wide_project": (_c_i32, [_vp, _vp, _vp, _c_i64, _c_i64, _p_i64, _vp, _c_i64, _c_i32, _c_i32,
+                                                   _vp]),
+    "choco_lowrank_gossip_wide_orthogonalize": (_c_i32, [_vp, _vp, _c_i64, _vp, ctypes.c_uint32, _p_i64, _vp, _c_i64,
+                                                         _c_i32, _c_i32, _vp]),
+    "choco_lowrank_gossip_wide_backproject": (_c_i32, [_vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_sz, _p_i64, _vp, _c_i64,
+                                                       _c_i32, _c_i32, _vp]),
+    "choco_lowrank_gossip_wide_diff": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, ctypes.c_uint32, _p_i64, _vp, _c_i64,
+                                                _c_i32, _c_i32, _vp]),
+    "choco_lowrank_gossip_wide_apply": (_c_i32, [_vp, _vp, _vp, _vp, _c_i64, _c_i64, _p_f64, ctypes.c_uint32, _p_i64, _vp,
+                                                 _c_i64, _c_i32, _c_i32, _vp]),
     "choco_params_consensus_launches": (_c_i32, [_c_i32, _c_i32]),
     "choco_params_consensus_workspace_size": (_c_sz, [_c_i32, _c_i64]),
     "choco_params_consensus": (_c_i32, [_pp, _pp, _p_i64, _p_i32, _c_i32, _vp, _vp, _c_i64, _c_f64, _c_i32, _vp, _vp,

@@ -174,3 +174,52 @@ class LowRankGossipPlan:
                                                        self._e(msg1_recv, self.msg1_len, "msg1_recv"), self.msg1_len,
                                                        self.msg2_len, w, int(lo_mask), *self._tail()),
                    "choco_lowrank_gossip_apply")
+
+
+GOSSIP_WIDE_MAX_WIDTH = 32  # n_edges * rank the matrix-instruction PowerGossip kernels serve
+
+
+class LowRankGossipWidePlan(LowRankGossipPlan):
+    """LowRankGossipPlan's five launches where it refuses: any rank of LOWRANK_RANKS with n_edges * rank <= 32 and
+    (n_edges * rank > 8 or rank >= 8), on the fp32 matrix instruction (include/choco_codec.h, "low-rank gossip,
+    wide"; csrc/lowrank_gossip_mfma.hip).  The same buffers, layouts, signatures and lo_mask; anything else raises."""
+
+    def __init__(self, shapes, rank, n_edges, device):
+        self.table = t = LowRankPlan(shapes, rank, device)
+        self.rank, self.n_edges = t.rank, int(n_edges)
+        width = self.n_edges * self.rank
+        if self.n_edges < 1 or width > GOSSIP_WIDE_MAX_WIDTH or (width <= GOSSIP_MAX_WIDTH and self.rank < 8):
+            raise RuntimeError(f"LowRankGossipWidePlan: n_edges * rank must be in ({GOSSIP_MAX_WIDTH}, "
+                               f"{GOSSIP_WIDE_MAX_WIDTH}], or rank at least 8, got {n_edges} edges at rank {rank} "
+                               "(DESIGN.md section 8)")
+        self.n, self.msg1_len, self.msg2_len, self.p_total = t.n, t.msg1_len, t.msg2_len, t.tail_off
+        self.ws_bytes = int(_c.lib().choco_lowrank_gossip_wide_workspace_size(t.plan_host, self.n_edges))
+
+    def _call(self, name, *args):
+        _lib.check(getattr(_c.lib(), "choco_lowrank_gossip_wide_" + name)(*args, *self._tail()),
+                   "choco_lowrank_gossip_wide_" + name)
+
+    def project(self, x, q, msg1):
+        self._call("project", self.table._flat(x, self.n, "x"), self._e(q, self.msg2_len, "q"),
+                   self._e(msg1, self.msg1_len, "msg1"), self.msg1_len, self.msg2_len)
+
+    def orthogonalize(self, msg1_own, msg1_recv, phat, lo_mask):
+        self._call("orthogonalize", self._e(msg1_own, self.msg1_len, "msg1_own"), self._e(msg1_recv, self.msg1_len, "msg1_recv"),
+                   self.msg1_len, self._e(phat, self.p_total, "phat"), int(lo_mask))
+
+    def backproject(self, x, phat, msg2):
+        ws = _c.workspace(self.table.plan_dev.device, "lowrank_gossip", self.ws_bytes)
+        self._call("backproject", self.table._flat(x, self.n, "x"), self._e(phat, self.p_total, "phat"), self.msg1_len,
+                   self._e(msg2, self.msg2_len, "msg2"), self.msg2_len, _c._ptr(ws), ws.numel())
+
+    def diff(self, msg2_own, msg2_recv, q, dq, lo_mask):
+        self._call("diff", self._e(msg2_own, self.msg2_len, "msg2_own"), self._e(msg2_recv, self.msg2_len, "msg2_recv"),
+                   self.msg1_len, self.msg2_len, self._e(q, self.msg2_len, "q"), self._e(dq, self.msg2_len, "dq"), int(lo_mask))
+
+    def apply(self, x, phat, dq, msg1_recv, weights, lo_mask):
+        if len(weights) != self.n_edges:
+            raise RuntimeError(f"LowRankGossipWidePlan.apply: {self.n_edges} weights expected, got {len(weights)}")
+        w = (ctypes.c_double * self.n_edges)(*[float(v) for v in weights])
+        self._call("apply", self.table._flat(x, self.n, "x"), self._e(phat, self.p_total, "phat"),
+                   self._e(dq, self.msg2_len, "dq"), self._e(msg1_recv, self.msg1_len, "msg1_recv"), self.msg1_len,
+                   self.msg2_len, w, int(lo_mask))

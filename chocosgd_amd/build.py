@@ -35,11 +35,12 @@ HIPCC_FLAGS = [
 # compiler would otherwise pair up; they stay the same plain v_add_f32 / v_sub_f32 as lowrank.hip's,
 # so the error memory is produced by the same instructions at every rank.  lowrank_cholqr.hip is
 # fp64 throughout but for its one narrowing store; it is built like the rest of the family.
-# lowrank_gossip.hip: the two ends of an edge must produce negated updates from the same chains.
+# lowrank_gossip.hip: the two ends of an edge must produce negated updates from the same chains;
+# lowrank_gossip_mfma.hip: its x = x + d sits between a 16-byte load and store like lowrank_mfma.hip's lines.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"signstep.hip": NO_PACKED_FP32, "vote.hip": NO_PACKED_FP32, "lowrank.hip": NO_PACKED_FP32,
                "lowrank_mfma.hip": NO_PACKED_FP32, "lowrank_cholqr.hip": NO_PACKED_FP32,
-               "lowrank_gossip.hip": NO_PACKED_FP32}
+               "lowrank_gossip.hip": NO_PACKED_FP32, "lowrank_gossip_mfma.hip": NO_PACKED_FP32}
 
 
 def _hipcc():

@@ -2087,4 +2087,5 @@ def is_pow2_minus1(s):
 from ._signvote import (MAX_VOTERS, params_sign_step, params_sign_step_launches, plan_sign_step,  # noqa: E402,F401
                         sign_vote)
 # ----------------------------------------------------------------------------- low-rank (PowerSGD)
-from ._lowrank import GOSSIP_MAX_WIDTH, LOWRANK_ORTH_METHODS, LOWRANK_RANKS, LowRankGossipPlan, LowRankPlan  # noqa: E402,F401
+from ._lowrank import (GOSSIP_MAX_WIDTH, GOSSIP_WIDE_MAX_WIDTH, LOWRANK_ORTH_METHODS, LOWRANK_RANKS,  # noqa: E402,F401
+                       LowRankGossipPlan, LowRankGossipWidePlan, LowRankPlan)

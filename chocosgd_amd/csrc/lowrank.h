@@ -1,7 +1,7 @@
 // What the low-rank files share.  All of them (lowrank.hip: PowerSGD at ranks 1, 2 and 4 on the vector ALUs;
 // lowrank_mfma.hip: ranks 8, 16 and 32 on the fp32 matrix instruction; lowrank_cholqr.hip: Cholesky-QR
-// orthogonalisation at ranks 8, 16 and 32; lowrank_gossip.hip: PowerGossip, batched over a worker's edges)
-// read one tile table: its layout, the check every launch makes first and the rank lists are here.
+// orthogonalisation at ranks 8, 16 and 32; lowrank_gossip.hip: PowerGossip, batched over a worker's edges up to
+// E r = 8; lowrank_gossip_mfma.hip: the same up to E r = 32 on the matrix instruction) read one tile table: its layout, the check every launch makes first and the rank lists are here.
 // lowrank.hip and lowrank_gossip.hip are one kernel family, and what they have in common stands here once:
 // the Gram-Schmidt sweep, the LDS staging, the wave-per-row walk over a column block, project's matrix item,
 // the per-element product chain, and the back-project kernel, which both launch (as they do lowrank.hip's
@@ -289,6 +289,49 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_backproject_kernel(const f
 __global__ void lowrank_slabsum_kernel(const float* __restrict__ ws, float* __restrict__ msg2,
                                        const int64_t* __restrict__ plan);
 
+// ---------------------------------------------------------------- matrix-instruction tiles (device)
+// lowrank_mfma.hip and lowrank_gossip_mfma.hip: v_mfma_f32_16x16x4_f32 and the 16-byte groups its lanes touch.
+typedef float lr_f32x4 __attribute__((ext_vector_type(4)));
+CHOCO_DEV lr_f32x4 lr_mfma(float a, float b, lr_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// Four consecutive elements at p of which the first nv exist (nv = 0: none, and no access).  AL:
+// p is 16-byte aligned and nv is 0 or 4.
+template <bool AL, bool NT>
+CHOCO_DEV float4 lr_ld4(const float* p, int nv) {
+  float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (AL) {
+    if (nv > 0) v = NT ? ld_nt4(p) : *reinterpret_cast<const float4*>(p);
+  } else {
+    if (nv > 0) v.x = NT ? __builtin_nontemporal_load(p) : p[0];
+    if (nv > 1) v.y = NT ? __builtin_nontemporal_load(p + 1) : p[1];
+    if (nv > 2) v.z = NT ? __builtin_nontemporal_load(p + 2) : p[2];
+    if (nv > 3) v.w = NT ? __builtin_nontemporal_load(p + 3) : p[3];
+  }
+  return v;
+}
+template <bool AL>
+CHOCO_DEV void lr_st4(float* p, int nv, float4 v) {
+  if (AL) {
+    if (nv > 0) *reinterpret_cast<float4*>(p) = v;
+  } else {
+    if (nv > 0) p[0] = v.x;
+    if (nv > 1) p[1] = v.y;
+    if (nv > 2) p[2] = v.z;
+    if (nv > 3) p[3] = v.w;
+  }
+}
+// how many of the four columns from col on exist in a row of `cols`, none for a row that does not
+CHOCO_DEV int lr_nv(bool row_ok, int64_t cols, int64_t col) {
+  const int64_t left = cols - col;
+  return !row_ok || left <= 0 ? 0 : left < 4 ? (int)left : 4;
+}
+CHOCO_DEV float lr_comp(const float4& v, int u) { return u == 0 ? v.x : u == 1 ? v.y : u == 2 ? v.z : v.w; }
+
+// whether every row of the matrix starts on the 16-byte grid of `base`
+CHOCO_DEV bool lr_rows_aligned(const float* base, const LrMat& M) {
+  return ((reinterpret_cast<uintptr_t>(base + M.off) & 15u) == 0) && (M.cols & 3) == 0;
+}
+
 // ---------------------------------------------------------------- ranks and the launch check (host)
 static bool lr_rank_hi(int32_t r) { return r == 8 || r == 16 || r == 32; }
 static bool lr_rank_ok(int32_t r) { return r == 1 || r == 2 || r == 4 || lr_rank_hi(r); }
@@ -330,5 +373,13 @@ int lr_hi_backproject(int32_t rank, dim3 grid, hipStream_t st, const float* e, c
                       const int64_t* plan);
 int lr_hi_decode(int32_t rank, dim3 grid, hipStream_t st, float* e, const float* msg1, const float* msg2, float* out,
                  float div, const int64_t* plan);
+
+
+// PowerGossip's orthogonalise and diff, one workgroup per (matrix, edge) of `grid` at any rank of the list
+// (lowrank_gossip.hip): lowrank_gossip_mfma.hip's entry points launch them too.
+int lg_orth(int32_t rank, dim3 grid, hipStream_t st, const float* own, const float* recv, float* phat, uint32_t lo_mask,
+            const int64_t* plan);
+int lg_diff(int32_t rank, dim3 grid, hipStream_t st, const float* own, const float* recv, float* q, float* dq,
+            uint32_t lo_mask, const int64_t* plan);
 
 }  // namespace choco

@@ -83,13 +83,14 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_gossip_project_kernel(cons
 
 // ---------------------------------------------------------------- orthogonalise
 // one workgroup per (matrix, edge): dP = P(lo end) - P(hi end), one fp32 subtraction per element
-// formed by the thread that owns the row in lr_mgs, then lowrank_orth_kernel's sweep
-template <int R>
+// formed by the thread that owns the row in lr_mgs, then lowrank_orth_kernel's sweep; like it, with
+// kLrHiOrthStage staged rows at ranks 8, 16 and 32 (the wide family, lowrank_gossip_mfma.hip)
+template <int R, int STAGE = kLrOrthStage>
 __global__ __launch_bounds__(kLrThreads) void lowrank_gossip_orth_kernel(const float* __restrict__ own,
                                                                          const float* __restrict__ recv,
                                                                          float* __restrict__ phat, uint32_t lo_mask,
                                                                          const int64_t* __restrict__ plan) {
-  __shared__ float Ps[kLrOrthStage * R];
+  __shared__ float Ps[STAGE * R];
   __shared__ double red[kLrWaves][R];
   const LrMat M = lr_mat(plan, blockIdx.x);
   const int e = blockIdx.y;
@@ -99,14 +100,14 @@ __global__ __launch_bounds__(kLrThreads) void lowrank_gossip_orth_kernel(const f
   const float* __restrict__ b = (lo ? recv : own) + at1;
   float* P = phat + e * plan[kLrPTotal] + M.poff;
   for (int64_t i = threadIdx.x; i < M.rows; i += kLrThreads) {
-    float* r = i < kLrOrthStage ? Ps + i * R : P + i * R;
+    float* r = i < STAGE ? Ps + i * R : P + i * R;
 #pragma unroll
     for (int c = 0; c < R; ++c) r[c] = a[i * R + c] - b[i * R + c];
   }
   __syncthreads();
-  lr_mgs<R, kLrOrthStage>(P, M.rows, Ps, red);
+  lr_mgs<R, STAGE>(P, M.rows, Ps, red);
   __syncthreads();
-  const int ns = (int)(M.rows < kLrOrthStage ? M.rows : kLrOrthStage);
+  const int ns = (int)(M.rows < STAGE ? M.rows : STAGE);
   for (int i = threadIdx.x; i < ns * R; i += kLrThreads) P[i] = Ps[i];
 }
 
@@ -237,6 +238,29 @@ static int lg_check(const int64_t* plan_host, const void* plan_dev, int64_t n, i
   return CHOCO_OK;
 }
 
+// orthogonalise and diff are per (matrix, edge) at rank r, whatever the width: both families launch these
+int lg_orth(int32_t rank, dim3 grid, hipStream_t st, const float* own, const float* recv, float* phat, uint32_t lo_mask,
+            const int64_t* plan) {
+  if (lr_rank_hi(rank))
+    return lr_dispatch_hi(rank, [&](auto R) {
+      return CHOCO_LAUNCH("lowrank_gossip_orth_kernel", "lowrank_gossip_orth_kernel",
+                          (lowrank_gossip_orth_kernel<R, kLrHiOrthStage>), grid, dim3(kLrThreads), st, own, recv, phat,
+                          lo_mask, plan);
+    });
+  return lr_dispatch_lo(rank, [&](auto R) {
+    return CHOCO_LAUNCH("lowrank_gossip_orth_kernel", "lowrank_gossip_orth_kernel", lowrank_gossip_orth_kernel<R>, grid,
+                        dim3(kLrThreads), st, own, recv, phat, lo_mask, plan);
+  });
+}
+
+int lg_diff(int32_t rank, dim3 grid, hipStream_t st, const float* own, const float* recv, float* q, float* dq,
+            uint32_t lo_mask, const int64_t* plan) {
+  return dispatch_list<1, 2, 4, 8, 16, 32>(rank, "rank", [&](auto R) {
+    return CHOCO_LAUNCH("lowrank_gossip_diff_kernel", "lowrank_gossip_diff_kernel", lowrank_gossip_diff_kernel<R>, grid,
+                        dim3(kLrThreads), st, own, recv, q, dq, lo_mask, plan);
+  });
+}
+
 }  // namespace choco
 
 using namespace choco;
@@ -271,11 +295,8 @@ CHOCO_API int choco_lowrank_gossip_orthogonalize(const float* msg1_own, const fl
   if (plan_host[kLrNcomp] == 0) return CHOCO_OK;
   CHOCO_REQUIRE(phat, "null pointer");
   CHOCO_REQUIRE(aligned4(msg1_own) && aligned4(msg1_recv) && aligned4(phat), "misaligned pointer");
-  const dim3 grid((unsigned)plan_host[kLrNcomp], (unsigned)n_edges), block(kLrThreads);
-  return lr_dispatch_lo(rank, [&](auto R) {
-    return CHOCO_LAUNCH("lowrank_gossip_orth_kernel", "lowrank_gossip_orth_kernel", lowrank_gossip_orth_kernel<R>, grid,
-                        block, as_stream(stream), msg1_own, msg1_recv, phat, lo_mask, plan_dev);
-  });
+  return lg_orth(rank, dim3((unsigned)plan_host[kLrNcomp], (unsigned)n_edges), as_stream(stream), msg1_own, msg1_recv,
+                 phat, lo_mask, plan_dev);
 }
 
 CHOCO_API int choco_lowrank_gossip_backproject(const float* x, const float* phat, int64_t msg1_len, float* msg2,
@@ -313,11 +334,8 @@ CHOCO_API int choco_lowrank_gossip_diff(const float* msg2_own, const float* msg2
   if (plan_host[kLrNcomp] == 0) return CHOCO_OK;
   CHOCO_REQUIRE(msg2_own && msg2_recv && q && dq, "null pointer");
   CHOCO_REQUIRE(aligned4(msg2_own) && aligned4(msg2_recv) && aligned4(q) && aligned4(dq), "misaligned pointer");
-  const dim3 grid((unsigned)plan_host[kLrNcomp], (unsigned)n_edges), block(kLrThreads);
-  return lr_dispatch_lo(rank, [&](auto R) {
-    return CHOCO_LAUNCH("lowrank_gossip_diff_kernel", "lowrank_gossip_diff_kernel", lowrank_gossip_diff_kernel<R>, grid,
-                        block, as_stream(stream), msg2_own, msg2_recv, q, dq, lo_mask, plan_dev);
-  });
+  return lg_diff(rank, dim3((unsigned)plan_host[kLrNcomp], (unsigned)n_edges), as_stream(stream), msg2_own, msg2_recv, q,
+                 dq, lo_mask, plan_dev);
 }
 
 CHOCO_API int choco_lowrank_gossip_apply(float* x, const float* phat, const float* dq, const float* msg1_recv,

@@ -20,13 +20,12 @@
 // columns of the strip (back-project) being one 256-byte segment.  A matrix whose rows are all
 // on the 16-byte grid (its start is, and cols % 4 == 0) runs the 16-byte instantiation; any other
 // the guarded scalar one (the rows of a tile then differ in alignment).
-// No atomics: every sum's order is fixed by the table and the rank.
+// No atomics: every sum's order is fixed by the table and the rank.  The instruction's wrapper and the guarded
+// 16-byte accesses (lr_mfma, lr_ld4, lr_st4, lr_nv, lr_rows_aligned) are in lowrank.h, shared with
+// lowrank_gossip_mfma.hip.
 #include "lowrank.h"
 
 namespace choco {
-
-typedef float lr_f32x4 __attribute__((ext_vector_type(4)));
-CHOCO_DEV lr_f32x4 lr_mfma(float a, float b, lr_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 template <int R>
 struct LrHi {
@@ -35,44 +34,6 @@ struct LrHi {
   static constexpr int QS = R + 4;                // LDS row stride of Q: 4 QS = 16 (mod 32), QS = 4 (mod 8)
   static constexpr int PS = R == 32 ? 48 : R;     // LDS row stride of P^ in back-project: the four k rows 16 banks apart
 };
-
-// Four consecutive elements at p of which the first nv exist (nv = 0: none, and no access).  AL:
-// p is 16-byte aligned and nv is 0 or 4.
-template <bool AL, bool NT>
-CHOCO_DEV float4 lr_ld4(const float* p, int nv) {
-  float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (AL) {
-    if (nv > 0) v = NT ? ld_nt4(p) : *reinterpret_cast<const float4*>(p);
-  } else {
-    if (nv > 0) v.x = NT ? __builtin_nontemporal_load(p) : p[0];
-    if (nv > 1) v.y = NT ? __builtin_nontemporal_load(p + 1) : p[1];
-    if (nv > 2) v.z = NT ? __builtin_nontemporal_load(p + 2) : p[2];
-    if (nv > 3) v.w = NT ? __builtin_nontemporal_load(p + 3) : p[3];
-  }
-  return v;
-}
-template <bool AL>
-CHOCO_DEV void lr_st4(float* p, int nv, float4 v) {
-  if (AL) {
-    if (nv > 0) *reinterpret_cast<float4*>(p) = v;
-  } else {
-    if (nv > 0) p[0] = v.x;
-    if (nv > 1) p[1] = v.y;
-    if (nv > 2) p[2] = v.z;
-    if (nv > 3) p[3] = v.w;
-  }
-}
-// how many of the four columns from col on exist in a row of `cols`, none for a row that does not
-CHOCO_DEV int lr_nv(bool row_ok, int64_t cols, int64_t col) {
-  const int64_t left = cols - col;
-  return !row_ok || left <= 0 ? 0 : left < 4 ? (int)left : 4;
-}
-CHOCO_DEV float lr_comp(const float4& v, int u) { return u == 0 ? v.x : u == 1 ? v.y : u == 2 ? v.z : v.w; }
-
-// whether every row of the matrix starts on the 16-byte grid of `base`
-CHOCO_DEV bool lr_rows_aligned(const float* base, const LrMat& M) {
-  return ((reinterpret_cast<uintptr_t>(base + M.off) & 15u) == 0) && (M.cols & 3) == 0;
-}
 
 // the workgroup stages columns [cb0, cb0 + nb) of a (cols x R) row-major factor at src as
 // kLrHiColBlock rows of QS words, the rows past nb zero (a zero of M times them must stay zero)

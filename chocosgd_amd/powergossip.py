@@ -28,10 +28,12 @@ One step (X: the flat buffer of the parameters after the local update):
 
 Steps 4 and 7 see the same two operands in the same order at both ends, so P^_e, dQ_e and the stored Q_e
 are bit-identical at the two ends of an edge and the two updates are each other's negation up to the
-final add.  `fused_step(...)` runs the step as codec.LowRankGossipPlan's launches (csrc/lowrank_gossip.hip),
-each of which passes over X once for ALL edges, where E * rank <= 8; `step_loop(...)` is the same step as
-one torch op per line, in the tensors' own precision (fp64 models stay fp64): the readable contract, and
-the path for CPU tensors, wider E * rank and anything the batched kernels do not take.
+final add.  `fused_step(...)` runs the step as batched launches, each of which passes over X once for ALL
+edges: codec.LowRankGossipPlan's (csrc/lowrank_gossip.hip) where E * rank <= 8 at rank <= 4, else
+codec.LowRankGossipWidePlan's on the fp32 matrix instruction (csrc/lowrank_gossip_mfma.hip) where E * rank <= 32;
+`step_loop(...)` is the same step as one torch op per line, in the tensors' own precision (fp64 models stay
+fp64): the readable contract, and the path for CPU tensors, E * rank > 32 and anything the batched kernels do
+not take.
 """
 import torch
 
@@ -53,8 +55,9 @@ class PowerGossipCompressor(object):
 
     def state(self, shapes, device, dtype=torch.float32):
         """The worker's state for this layout, created on first use: .q, (E, msg2_len), row e = [Q_e,0 |
-        Q_e,1 | ..], and, on a ROCm device in fp32 with E * rank <= 8, .plan (codec.LowRankGossipPlan).
-        Another layout, device or dtype later on raises."""
+        Q_e,1 | ..], and, on a ROCm device in fp32, .plan: codec.LowRankGossipPlan where it applies (E * rank <= 8
+        at rank <= 4), else codec.LowRankGossipWidePlan where E * rank <= 32, else None.  Another layout, device
+        or dtype later on raises."""
         shapes = [tuple(int(d) for d in s) for s in shapes]
         if self.shapes is None:
             rows = []
@@ -64,15 +67,26 @@ class PowerGossipCompressor(object):
                 rows.append(torch.cat([torch.randn(torch.Size(s).numel() // s[0], self.rank, generator=gen).reshape(-1)
                                        for s in shapes if powersgd.is_compressed(s, self.rank)] + [torch.empty(0)]))
             self.q = torch.stack(rows).to(device=device, dtype=dtype) if rows else torch.empty(0, 0, device=device, dtype=dtype)
-            width = len(self.neighbors) * self.rank
-            if self.q.is_cuda and dtype == torch.float32 and 1 <= width <= codec.GOSSIP_MAX_WIDTH and self.rank <= 4:
-                self.plan = codec.LowRankGossipPlan(shapes, self.rank, len(self.neighbors), device)
+            cls = plan_class(self.rank, len(self.neighbors))
+            if self.q.is_cuda and dtype == torch.float32 and cls is not None:
+                self.plan = cls(shapes, self.rank, len(self.neighbors), device)
             self.shapes = shapes
         elif shapes != self.shapes or self.q.device != torch.device(device) or self.q.dtype != dtype:
             raise RuntimeError("PowerGossipCompressor: the edges' Q were created for another layout "
                                f"({len(self.shapes)} tensors on {self.q.device}, {self.q.dtype}); use one compressor "
                                "per model")
         return self
+
+
+def plan_class(rank, n_edges):
+    """The batched kernel family of a worker with n_edges edges at this rank: the narrow plan where it applies,
+    the wide plan where E * rank <= 32, None (step_loop) otherwise."""
+    width = n_edges * rank
+    if 1 <= width <= codec.GOSSIP_MAX_WIDTH and rank <= 4:
+        return codec.LowRankGossipPlan
+    if 1 <= width <= codec.GOSSIP_WIDE_MAX_WIDTH:
+        return codec.LowRankGossipWidePlan
+    return None
 
 
 def step_loop(compressor, param_groups, param_names, state):
@@ -140,8 +154,10 @@ def fused_step(compressor, param_groups, param_names, state, master=None, clip_n
     lowrank_gossip_project_kernel, the exchange of message 1, lowrank_gossip_orth_kernel,
     lowrank_gossip_backproject_kernel (and the slab-sum launch), the exchange of message 2,
     lowrank_gossip_diff_kernel, lowrank_gossip_apply_kernel and the batched unpack of X into the parameters.
-    Every kernel that touches X passes over it once for all E edges.  Returns n_bits = 32 E (msg1_len +
-    msg2_len).  Tensors the kernels do not take, no neighbours, or E * rank > 8 run step_loop.
+    Beyond E * rank = 8 or rank 4, up to E * rank = 32, project, back-project and apply are
+    lowrank_gossip_{project,backproject,apply}_mfma_kernel (plan_class).  Every kernel that touches X passes
+    over it once for all E edges.  Returns n_bits = 32 E (msg1_len + msg2_len).  Tensors the kernels do not
+    take, no neighbours, or E * rank > 32 run step_loop.
 
     Not part of this step, each refused: master=, clip_norm=, loss_scale= and
     rounding=."""
@@ -154,7 +170,7 @@ def fused_step(compressor, param_groups, param_names, state, master=None, clip_n
     entries = utils.step_entries(param_groups, param_names, what)
     params = [p for _, p in entries]
     nbrs, E = compressor.neighbors, len(compressor.neighbors)
-    if not 1 <= E * compressor.rank <= codec.GOSSIP_MAX_WIDTH or compressor.rank > 4 or not params[0].is_cuda:
+    if plan_class(compressor.rank, E) is None or not params[0].is_cuda:
         return step_loop(compressor, param_groups, param_names, state)
     flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=params[0].device)
     plan = utils._sgd_fill(entries, state, True, flat)

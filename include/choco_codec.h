@@ -1381,6 +1381,48 @@ int choco_lowrank_gossip_apply(float* x, const float* phat, const float* dq, con
                                int64_t msg2_len, const double* weights, uint32_t lo_mask, const int64_t* plan_host,
                                const int64_t* plan_dev, int64_t n, int32_t rank, int32_t n_edges, void* stream);
 
+/* ------------------------------------------- low-rank gossip, wide
+ * The same five calls where the ones above refuse: any rank of 1, 2, 4, 8, 16, 32 and n_edges >= 1 with
+ * n_edges * rank <= 32 and (n_edges * rank > 8 or rank >= 8), so n_edges <= 32.  Project, back-project and
+ * apply run on the fp32 matrix instruction (v_mfma_f32_16x16x4_f32): the edges' factors are one concatenated
+ * factor of K = n_edges * rank columns, padded with zero columns to 16 (K <= 16) or 32, which are never stored.
+ * The argument lists, the buffers' edge-major layouts, lo_mask, the table (at `rank`, unchanged) and the checks
+ * before the first launch are those of the namesakes; weights holds n_edges doubles.
+ *   choco_lowrank_gossip_wide_project        "lowrank_gossip_project_mfma_kernel".  An element of P_e is a
+ *                                            cols-term fp32 dot product in a fixed order.
+ *   choco_lowrank_gossip_wide_orthogonalize  the namesake's kernel and arithmetic at `rank`.
+ *   choco_lowrank_gossip_wide_backproject    "lowrank_gossip_backproject_mfma_kernel", then
+ *                                            "lowrank_gossip_slabsum_kernel".  ws:
+ *                                            choco_lowrank_gossip_wide_workspace_size(table, n_edges) bytes.
+ *   choco_lowrank_gossip_wide_diff           the namesake's kernel and arithmetic at `rank`.
+ *   choco_lowrank_gossip_wide_apply          "lowrank_gossip_apply_mfma_kernel".  Compressed, per element:
+ *                                            d = sum over e and c of fl(c_e P^_e[row][c]) dQ_e[col][c], summed
+ *                                            inside the matrix instruction from zero, then x = fl(x + d).
+ *                                            Uncompressed: the namesake's mix, for up to 32 edges.
+ * With both ends of an edge passing each other's messages and complementary lo_mask bits, phat[e], dq[e] and
+ * q[e] are bit-identical at the two ends, and, the other edges' terms aside, the updates d are exact negations
+ * (the ends feed exactly negated operands to a sum that starts at zero).  No atomics; the same inputs give the
+ * same bits.  A bad call returns CHOCO_ERR_INVALID and launches nothing. */
+size_t choco_lowrank_gossip_wide_workspace_size(const int64_t* plan_host, int32_t n_edges);
+int choco_lowrank_gossip_wide_project(const float* x, const float* q, float* msg1, int64_t msg1_len, int64_t msg2_len,
+                                      const int64_t* plan_host, const int64_t* plan_dev, int64_t n, int32_t rank,
+                                      int32_t n_edges, void* stream);
+int choco_lowrank_gossip_wide_orthogonalize(const float* msg1_own, const float* msg1_recv, int64_t msg1_len,
+                                            float* phat, uint32_t lo_mask, const int64_t* plan_host,
+                                            const int64_t* plan_dev, int64_t n, int32_t rank, int32_t n_edges,
+                                            void* stream);
+int choco_lowrank_gossip_wide_backproject(const float* x, const float* phat, int64_t msg1_len, float* msg2,
+                                          int64_t msg2_len, void* ws, size_t ws_bytes, const int64_t* plan_host,
+                                          const int64_t* plan_dev, int64_t n, int32_t rank, int32_t n_edges,
+                                          void* stream);
+int choco_lowrank_gossip_wide_diff(const float* msg2_own, const float* msg2_recv, int64_t msg1_len, int64_t msg2_len,
+                                   float* q, float* dq, uint32_t lo_mask, const int64_t* plan_host,
+                                   const int64_t* plan_dev, int64_t n, int32_t rank, int32_t n_edges, void* stream);
+int choco_lowrank_gossip_wide_apply(float* x, const float* phat, const float* dq, const float* msg1_recv,
+                                    int64_t msg1_len, int64_t msg2_len, const double* weights, uint32_t lo_mask,
+                                    const int64_t* plan_host, const int64_t* plan_dev, int64_t n, int32_t rank,
+                                    int32_t n_edges, void* stream);
+
 /* ------------------------------------------- consensus evaluation
  * The reference's --evaluate_consensus (pcode/distributed_running_cv.py:110-115, :239-243):
  * the model averaged over the workers (agg_model(copy, op="avg"),
