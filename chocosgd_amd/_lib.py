@@ -122,6 +122,16 @@ SIGNATURES = {
                                            _c_i64, _c_i64, _vp, _vp]),
     "choco_qsgd_decompress_accumulate_range": (_c_i32, [_pp, _pp, _p_f32, _c_i32, _c_i32, _c_i64, _vp, _c_i32,
                                                         _c_i32, _c_i32, _c_i64, _c_i64, _vp, _vp, _vp]),
+    "choco_qsgd_bucket_packed_bytes": (_c_i64, [_c_i64, _c_i32, _c_i32]),
+    "choco_qsgd_bucket_compress": (_c_i32, [_vp, _vp, _c_i64, _c_i32, _c_i32, _c_i32, _vp, _c_u64, _c_u64, _vp, _vp,
+                                            _vp]),
+    "choco_gossip_qsgd_bucket_compress": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i32, _c_i32, _c_i32, _vp,
+                                                   _c_u64, _c_u64, _vp, _vp, _vp]),
+    "choco_qsgd_bucket_decode": (_c_i32, [_vp, _c_i64, _c_i32, _c_i32, _c_i32, _vp, _vp]),
+    "choco_qsgd_bucket_decompress_accumulate": (_c_i32, [_pp, _p_f32, _c_i32, _c_i32, _c_i64, _c_i32, _c_i32,
+                                                         _c_i32, _vp, _vp, _vp]),
+    "choco_qsgd_bucket_recv_gossip_compress": (_c_i32, [_pp, _p_f32, _c_i32, _c_i32, _vp, _vp, _vp, _c_f32, _c_i64,
+                                                        _c_i32, _c_i32, _c_i32, _vp, _c_u64, _c_u64, _vp, _vp]),
     "choco_gossip_step": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _vp]),
     "choco_params_launches": (_c_i32, [_c_i32]),
     "choco_params_pack": (_c_i32, [_pp, _p_i64, _p_i32, _c_i32, _vp, _c_i64, _vp]),

@@ -2089,3 +2089,8 @@ from ._signvote import (MAX_VOTERS, params_sign_step, params_sign_step_launches,
 # ----------------------------------------------------------------------------- low-rank (PowerSGD)
 from ._lowrank import (GOSSIP_MAX_WIDTH, GOSSIP_WIDE_MAX_WIDTH, LOWRANK_ORTH_METHODS, LOWRANK_RANKS,  # noqa: E402,F401
                        LowRankGossipPlan, LowRankGossipWidePlan, LowRankPlan)
+# ----------------------------------------------------------------------------- bucketed QSGD
+# codec.qsgd_bucket_* stand in _qsgd_bucket.py (it needs the names above, hence the import down here)
+from ._qsgd_bucket import (QSGD_BUCKETS, qsgd_bucket_accumulate, qsgd_bucket_compress,  # noqa: E402,F401
+                           qsgd_bucket_decode, qsgd_bucket_packed_bytes, qsgd_bucket_recv_gossip_compress,
+                           qsgd_bucket_split, qsgd_bucket_wire)

@@ -22,15 +22,13 @@
 //                         Infinity Cache instead of HBM.
 #include "choco_common.h"
 #include "dispatch.h"
+#include "qsgd_common.h"
 
 #include <algorithm>
 #include <math.h>
 
 namespace choco {
 
-constexpr int kQThreads = 256;
-constexpr int kQPer = 8;                         // elements per thread in the quantize/decode passes
-constexpr int kQTile = kQThreads * kQPer;        // 2048
 // elements per workgroup in the norm pass (a multiple of 8192): 49152 -> ~2040 workgroups
 // at 100M, one round of 8 per CU (r03 A/B: 32768 and 65536 slower); smaller inputs take
 // smaller tiles down to 8192, so that the grid still has ~2048 workgroups (norm_tile)
@@ -42,7 +40,6 @@ static int64_t norm_tile(int64_t n) {
 }
 constexpr int kNormSegLds = 64;  // a tile spanning fewer segments sums them in LDS first
 static_assert(kNormTile % kNormTileMin == 0 && kNormTileMin % 8192 == 0, "whole load rounds per norm tile");
-constexpr int kQMaxMsg = kMaxMsg;
 constexpr int kAccRep = 8;  // replicas of the fp64 norm accumulators (the fused receive pass)
 
 struct QsgdWs {
@@ -50,14 +47,6 @@ struct QsgdWs {
   unsigned int pad[63];
   // double acc[nseg] at +256
 };
-
-static int container_bits(int q) {
-  int cw = 1;
-  while (cw < q) cw <<= 1;
-  return cw;
-}
-
-static int64_t plane_bytes(int64_t n, int cw) { return (int64_t)align_up((size_t)((n + 7) / 8) * cw, 16); }
 
 CHOCO_DEV float dval(const float* __restrict__ x, const float* __restrict__ xh, int64_t i) {
   return xh ? x[i] - xh[i] : x[i];
@@ -259,77 +248,6 @@ __global__ __launch_bounds__(kQThreads) void qsgd_norm_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------- pass 2: quantize + pack
-template <int CW>
-CHOCO_DEV void store_levels(uint8_t* __restrict__ plane, int64_t t, const uint32_t (&lv)[kQPer]) {
-  if (CW == 16) {
-    uint4 v;
-    v.x = lv[0] | (lv[1] << 16);
-    v.y = lv[2] | (lv[3] << 16);
-    v.z = lv[4] | (lv[5] << 16);
-    v.w = lv[6] | (lv[7] << 16);
-    reinterpret_cast<uint4*>(plane)[t] = v;
-  } else {
-    uint64_t acc = 0;
-#pragma unroll
-    for (int c = 0; c < kQPer; ++c) acc |= (uint64_t)lv[c] << (c * CW);
-    if (CW == 8) reinterpret_cast<uint64_t*>(plane)[t] = acc;
-    if (CW == 4) reinterpret_cast<uint32_t*>(plane)[t] = (uint32_t)acc;
-    if (CW == 2) reinterpret_cast<uint16_t*>(plane)[t] = (uint16_t)acc;
-    if (CW == 1) plane[t] = (uint8_t)acc;
-  }
-}
-
-// A group's packed levels as loaded (CW * 8 bits: 1 to 4 words) and one level of them: the
-// fused receive keeps the packed form in registers (8 unpacked levels per message and group
-// did not fit).
-template <int CW>
-struct LevelWords {
-  uint32_t w[CW == 16 ? 4 : (CW == 8 ? 2 : 1)];
-};
-template <int CW>
-CHOCO_DEV LevelWords<CW> load_level_words(const uint8_t* __restrict__ plane, int64_t t) {
-  LevelWords<CW> r;
-  if (CW == 16) {
-    const uint4 v = reinterpret_cast<const uint4*>(plane)[t];
-    r.w[0] = v.x; r.w[CW == 16 ? 1 : 0] = v.y; r.w[CW == 16 ? 2 : 0] = v.z; r.w[CW == 16 ? 3 : 0] = v.w;
-  } else if (CW == 8) {
-    const uint2 v = reinterpret_cast<const uint2*>(plane)[t];
-    r.w[0] = v.x; r.w[CW == 8 ? 1 : 0] = v.y;
-  } else if (CW == 4) {
-    r.w[0] = reinterpret_cast<const uint32_t*>(plane)[t];
-  } else if (CW == 2) {
-    r.w[0] = reinterpret_cast<const uint16_t*>(plane)[t];
-  } else {
-    r.w[0] = plane[t];
-  }
-  return r;
-}
-template <int CW>
-CHOCO_DEV uint32_t level_of(const LevelWords<CW>& r, int c) {
-  const int bit = c * CW;
-  return (r.w[bit >> 5] >> (bit & 31)) & ((CW == 16 ? 0x10000u : (1u << CW)) - 1u);
-}
-
-template <int CW>
-CHOCO_DEV void load_levels(const uint8_t* __restrict__ plane, int64_t t, uint32_t (&lv)[kQPer]) {
-  if (CW == 16) {
-    const uint4 v = reinterpret_cast<const uint4*>(plane)[t];
-    lv[0] = v.x & 0xFFFFu; lv[1] = v.x >> 16;
-    lv[2] = v.y & 0xFFFFu; lv[3] = v.y >> 16;
-    lv[4] = v.z & 0xFFFFu; lv[5] = v.z >> 16;
-    lv[6] = v.w & 0xFFFFu; lv[7] = v.w >> 16;
-  } else {
-    uint64_t acc = 0;
-    if (CW == 8) acc = reinterpret_cast<const uint64_t*>(plane)[t];
-    if (CW == 4) acc = reinterpret_cast<const uint32_t*>(plane)[t];
-    if (CW == 2) acc = reinterpret_cast<const uint16_t*>(plane)[t];
-    if (CW == 1) acc = plane[t];
-    const uint32_t mask = (1u << CW) - 1u;
-#pragma unroll
-    for (int c = 0; c < kQPer; ++c) lv[c] = (uint32_t)(acc >> (c * CW)) & mask;
-  }
-}
-
 CHOCO_DEV int tile_seg(const int64_t* __restrict__ seg_off, int nseg, int64_t e0, int64_t e1, int* s_seg) {
   if (threadIdx.x == 0) {
     s_seg[0] = nseg > 1 ? seg_of(seg_off, nseg, e0) : 0;
@@ -337,55 +255,6 @@ CHOCO_DEV int tile_seg(const int64_t* __restrict__ seg_off, int nseg, int64_t e0
   }
   __syncthreads();
   return s_seg[0];
-}
-
-// s * |d| / norm, correctly rounded, without the IEEE division expansion per
-// element.  With y = RN(1/norm) (one real division per thread) and q0 = RN(t * y)
-// (within one ulp of t / norm), r = fma(-q0, norm, t) is exact and
-// RN(q0 + r * y) is RN(t / norm) (Markstein's theorem) as long as nothing
-// underflows or overflows: the fast form is taken for norm in [2^-30, 2^96] and
-// q0 in [2^-60, 2^7] (then t >= 2^-90 and r stays normal), zeros give +0 as
-// 0/norm does, and everything else (tiny quotients, NaN/inf, extreme norms, a
-// pinned norm below |d|) takes the real division.  Checked against fp32 division on 3e9 (t, norm) pairs (random over
-// the guarded range + exhaustive t for 12 norm mantissas) and bit-exact against
-// the oracle in the GPU tests.
-struct QDiv {
-  float norm, y;
-  bool fast;
-  uint32_t tlo_m1;  // bits(T_lo) - 1, T_lo = 2^-60 norm (1 + 2^-20): t >= T_lo implies q0 >= 2^-60
-  CHOCO_DEV void init(float nrm) {
-    norm = nrm;
-    y = 1.0f / nrm;
-    fast = nrm >= 0x1p-30f && nrm <= 0x1p96f;
-    tlo_m1 = __float_as_uint(nrm * 0x1.00001p-60f) - 1u;
-  }
-  // The guard, per 8-element group: instead of testing every element's q0
-  // against [2^-60, 2^7] (three compares and four scalar mask operations per element),
-  // the group keeps min(bits(t) - 1) and max(bits(q0)) in two VALU ops per element and
-  // tests them once.  Conservative: t != 0 with t < T_lo covers every q0 < 2^-60 (and
-  // some above it), bits(q0) > bits(2^7) covers q0 > 2^7, inf and NaN; a flagged group
-  // takes the IEEE division for all its elements, so the result is the same as a per-element
-  // guard's (q0 in [2^-60, 2^7] or t == 0, norm in range).
-  CHOCO_DEV float quot_nocheck(float t, uint32_t& tmin_m1, uint32_t& qmax) const {
-    const float q0 = t * y;
-    const float r = fmaf(-q0, norm, t);
-    tmin_m1 = min(tmin_m1, __float_as_uint(t) - 1u);
-    qmax = max(qmax, __float_as_uint(q0));
-    return fmaf(r, y, q0);
-  }
-  CHOCO_DEV bool group_slow(uint32_t tmin_m1, uint32_t qmax) const {
-    return !fast || tmin_m1 < tlo_m1 || qmax > 0x43000000u;
-  }
-};
-
-// The container value of a level: NaN -> 0, levels >= s -> s (a pinned norm below
-// |d|), as one branch-free clamp (fmaxf(NaN, 0) = 0); levels are >= 0 and integral.
-CHOCO_DEV uint32_t level_code(float lvl, float sf) { return (uint32_t)fminf(fmaxf(lvl, 0.0f), sf); }
-
-// One quantized element: level (clamped container value, 0 for NaN), sign bit.
-CHOCO_DEV float qlevel(float lf, float u) {
-  const float pl = floorf(lf);                                // previous_level
-  return pl + ((u < (lf - pl)) ? 1.0f : 0.0f);                // + is_next_level
 }
 
 // Quantize + pack.  A 256-thread workgroup owns an 8192-element tile; thread t
@@ -396,15 +265,6 @@ CHOCO_DEV float qlevel(float lf, float u) {
 // VALU-bound, not HBM-bound, in its round-1 form (SplitMix64 per pair + the
 // IEEE division per element: 123 us at 100M with the tail re-read from the
 // Infinity Cache); see DESIGN.md §4 for the measured steps.
-constexpr int kQG = 4;                                  // groups per thread
-// The uniform stream of thread slot t's groups g, g + 1 (g even) of a tile: 16 uniforms
-// each, two streams per slot (choco_common.h Xoro128; oracle qsgd_uniforms_at).
-CHOCO_DEV uint64_t qstream_id(int64_t tile, int g, uint32_t t) {
-  return ((uint64_t)tile << 9) | ((uint64_t)(g >> 1) << 8) | t;
-}
-constexpr int kQStreamTile = kQThreads * kQPer * kQG;   // 8192 elements per workgroup
-static_assert(kQStreamTile == 8192, "the uniform-stream mapping (choco_common.h) assumes 8192-element tiles");
-
 // A tile that crosses a segment boundary or ends the buffer: element by element,
 // in stream order (the same uniforms as the fast path), per-element segment
 // parameters and the real division.  Kept out of line: it is rare and would

@@ -240,13 +240,47 @@ class CHOCOQuantizationCompressor(_CHOCOBase):
     [norms header, range 0, range 1, ...]."""
 
     def __init__(self, *args, **kargs):
+        self.bucket_size = self._bucket_args(*args, **kargs)  # refusals first: nothing is bound yet
         super().__init__(*args, **kargs)
         self.exchange_chunks = int(self.kargs.get("exchange_chunks", 1))
+
+    @staticmethod
+    def _bucket_args(aggregator=None, comm_op="", comm_device=None, compress_ratio=None, quantize_level=None,
+                     *_rest, exchange_chunks=1, bucket_size=512, **_kargs):
+        """comm_op "quantize_qsgd_bucket": the bucketed max-norm quantizer's bucket size (keyword
+        bucket_size, default 512), None for any other op.  What the bucketed op does not do is
+        refused here by name, not run as the per-tensor quantizer."""
+        if "bucket" not in comm_op:
+            return None
+        if int(exchange_chunks) > 1:
+            raise RuntimeError("comm_op quantize_qsgd_bucket: exchange_chunks > 1 is not implemented")
+        if int(quantize_level) == 32:
+            raise NotImplementedError("comm_op quantize_qsgd_bucket has no quantize_level = 32 passthrough")
+        if int(bucket_size) not in codec.QSGD_BUCKETS:
+            raise RuntimeError(f"bucket_size must be one of {codec.QSGD_BUCKETS}, got {bucket_size}")
+        return int(bucket_size)
+
+    def _compress_bucket(self, sync_buffer, x, xh, lay, q, g):
+        """One launch: the one-pass compress (the consensus step fused where `gossip` gives it),
+        or, with a deferred receive pending, the whole step -- receive, consensus step, message."""
+        message = codec.qsgd_bucket_wire(lay.n, q, self.bucket_size, x.device)  # written in place by the kernel
+        pend = self._take_pending(x, xh, g, lay)
+        if pend is not None:
+            codec.qsgd_bucket_recv_gossip_compress(pend[0], pend[1], pend[2], x, g[0], xh, g[1], q,
+                                                   bucket=self.bucket_size, is_biased=self.is_biased,
+                                                   seed=self._draw_seed(), out=message)
+        else:
+            codec.qsgd_bucket_compress(x, q, bucket=self.bucket_size, is_biased=self.is_biased, xhat=xh,
+                                       seed=self._draw_seed(), gossip=g, out=message)
+        self._qsgd_keys(sync_buffer, x, message)
 
     def compress(self, sync_buffer):
         x, xh, lay = self._flat_inputs(sync_buffer)
         q = int(self.quantize_level)
         g = self._gossip(sync_buffer)
+        if self.bucket_size is not None:
+            sync_buffer.pop("chunked", None)
+            return self._compress_bucket(sync_buffer, x, xh, lay, q, g)
         if q == 32 or self.exchange_chunks > 1:
             self._flush_before_pass(g)  # (never deferred on these paths)
         if q != 32 and self.exchange_chunks > 1:
@@ -299,7 +333,11 @@ class CHOCOQuantizationCompressor(_CHOCOBase):
         self.aggregator_fn.complete_wait(sync_buffer["sync_reqs"])
         ranks, plan = self._receive_plan(sync_buffer, neighbor_hat_params, neighbors_info)
         weights, self_slot, memory, xhat_self, _ = plan
-        msgs = [m for _, _, m in self._qsgd_received(sync_buffer, ((r, memory) for r in ranks))]
+        if self.bucket_size is not None:  # whole messages: the scales lead, there is no norms header
+            msgs = [m for _, _, m in _received(sync_buffer["synced_message"], ((r, memory) for r in ranks),
+                                               lambda m: m)]
+        else:
+            msgs = [m for _, _, m in self._qsgd_received(sync_buffer, ((r, memory) for r in ranks))]
         if int(self.quantize_level) == 32:
             for i, (v, w) in enumerate(zip(msgs, weights)):
                 if i == self_slot:
@@ -311,6 +349,10 @@ class CHOCOQuantizationCompressor(_CHOCOBase):
         self._apply(msgs, *plan)
 
     def _apply(self, parts, weights, self_slot, memory, xhat_self, lay):
+        if self.bucket_size is not None:
+            return codec.qsgd_bucket_accumulate(parts, weights, self_slot, lay.n, int(self.quantize_level), memory,
+                                                bucket=self.bucket_size, xhat_self=xhat_self,
+                                                is_biased=self.is_biased)
         codec.qsgd_accumulate(parts, weights, self_slot, lay.n, int(self.quantize_level), memory,
                               xhat_self=xhat_self, is_biased=self.is_biased, seg_off=lay.seg_off, nseg=lay.nseg)
 

@@ -111,13 +111,29 @@ class QuantizationCompressor(object):
         _, _, dense = codec.qsgd_compress(x_flat, q, is_biased=is_biased, seed=_draw_seed(), want_dense=True)
         return _home(dense.view_as(xd), home)
 
+    def get_qsgd_bucket(self, x, s, bucket_size=512, is_biased=False):
+        """The bucketed max-norm quantizer (include/choco_codec.h "bucketed QSGD"): the dense
+        decode of x quantized in buckets of `bucket_size` flat elements."""
+        if not codec.is_pow2_minus1(int(s)):
+            raise RuntimeError(f"QSGD level count s={s} must be 2^q - 1 with 1 <= q <= 16")
+        q = int(round(math.log2(int(s) + 1)))
+        xd, home = _on_device(x)
+        x_flat = xd.reshape(-1).contiguous()
+        _, dense = codec.qsgd_bucket_compress(x_flat, q, bucket=bucket_size, is_biased=is_biased, seed=_draw_seed(),
+                                              want_dense=True)
+        return _home(dense.view_as(xd), home)
+
     def qsgd_quantize_numpy(self, x, s, is_biased=False):
         """numpy in / numpy out; computed on the current ROCm device."""
         t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
         return self.get_qsgd(t, s, is_biased).numpy()
 
     def compress(self, arr, op, quantize_level, is_biased):
-        if quantize_level != 32:
+        if "bucket" in op:
+            if quantize_level == 32:
+                raise NotImplementedError("the bucketed quantizer has no quantize_level = 32 passthrough")
+            values = self.get_qsgd_bucket(arr, 2 ** quantize_level - 1, is_biased=is_biased)
+        elif quantize_level != 32:
             s = 2 ** quantize_level - 1
             values = self.get_qsgd(arr, s, is_biased)
         else:

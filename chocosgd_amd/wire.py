@@ -288,6 +288,12 @@ class _SparseConsumer(_Consumer):
 
 
 class _QsgdConsumer(_Consumer):
+    def __init__(self, *args, **kargs):
+        super().__init__(*args, **kargs)
+        if "bucket" in self.comm_op:  # not silently the per-tensor quantizer
+            raise NotImplementedError(f"comm_op={self.comm_op!r}: the bucketed quantizer is CHOCO's only "
+                                      "(CHOCOCompressor); DCD, ECD and DeepSqueeze take quantize_qsgd")
+
     def sync(self, sync_buffer):
         sync_buffer["synced_message"] = self._send(sync_buffer["flatten_updates"].buffer)
 

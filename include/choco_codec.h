@@ -514,6 +514,69 @@ int choco_qsgd_decompress_accumulate_range(const uint8_t* const* packed_list, co
                                            int64_t e0, int64_t e1, float* xhat_self, float* memory,
                                            void* stream);
 
+/* ------------------------------------------------------- bucketed QSGD
+ * The practical variant of the QSGD paper (Alistarh et al. 2017, section 4): the flat buffer
+ * is quantized in BUCKETS of B elements, each scaled by its own maximum.  The variance bound
+ * min(d / s^2, sqrt(d) / s) ||x||^2 then has d = B instead of the tensor's length, and a
+ * bucket's scale needs no pass of its own: the compressor is one pass, and the whole CHOCO
+ * step (receive, consensus step, message) one kernel.  No workspace anywhere.
+ *   n >= 1 elements; q in [1, 16], s = 2^q - 1; container width cw = the power of two >= q;
+ *   bucket B in {128, 256, 512, 1024, 2048}.
+ *   Bucket b is the flat elements [b B, min((b + 1) B, n)); tensor boundaries are ignored;
+ *   nb = ceil(n / B).
+ * For every element e of bucket b, with d = x - xhat (x alone when xhat is NULL):
+ *   m_b     = max |d| over the bucket's non-NaN elements (fmaxf), 0 if there are none
+ *   lf      = ((float)s * |d|) / m_b            (fp32, the division correctly rounded)
+ *   level   = min(floor(lf) + (u < lf - floor(lf)), s),  NaN -> 0
+ *             (an all-zero bucket, 0 / 0, quantizes and decodes to zeros; the clamp matters:
+ *             RN(s * m) / m can land one ulp above s)
+ *   u       = u_in[e] if given, else the uniform stream of element e described under QSGD
+ *             above, unchanged (key from (seed, offset); oracle qsgd_uniforms_at)
+ *   sign bit set iff d < 0
+ *   decoded v = +-((c * m_b) * level) / (float)s, left to right, one rounding per operation;
+ *             c = 1, or with is_biased c = (float)(1.0 / (min(B / s^2, sqrt(B) / s) + 1.0))
+ *             in doubles: the same constant for every bucket, a short last one included.
+ * A bucket that holds an infinity has m_b = inf and decodes to NaN throughout (inf * 0): the
+ * plain arithmetic of the formula, confined to that bucket, not special-cased.
+ * Message: [scales: nb fp32, padded to 16 B | level plane | sign plane], the two planes
+ * exactly those of choco_qsgd_packed_bytes(n, q); choco_qsgd_bucket_packed_bytes(n, q, B) =
+ * align16(4 nb) + choco_qsgd_packed_bytes(n, q) bytes (0 for arguments out of range), every
+ * byte of it written.
+ *
+ * compress: message (and dense_out = v, nullable) of x - xhat.  gossip_..._compress: the
+ * consensus step first, x_new = x + gamma (memory - xhat) written back with choco_gossip_step's
+ * expression, d = x_new - xhat.  decode: out = v.  decompress_accumulate: for each message m
+ * in order, xhat_self += v_m if m == self_slot (xhat_self NULL: no self message), memory +=
+ * (float)weights[m] * v_m (two roundings), as choco_qsgd_decompress_accumulate.
+ * recv_gossip_compress: per element that accumulate for the previous step's messages, then
+ * x += gamma (memory - xhat) on the updated values, then compress on x_new - xhat_new into
+ * message_out -- one pass over x, xhat and memory, bit-identical to decompress_accumulate,
+ * choco_gossip_step, compress in sequence.
+ *
+ * Every call checks its arguments before the launch and without a HIP call
+ * (CHOCO_ERR_INVALID, choco_last_error names the reason): null pointers, n outside
+ * [1, 2^31 - 1), q outside [1, 16], a bucket outside the list, nmsg outside 1..8, self_slot
+ * outside [-1, nmsg), pointers off 16-byte alignment, and an output message that overlaps
+ * x, xhat, memory or (recv_gossip_compress) an input message. */
+int64_t choco_qsgd_bucket_packed_bytes(int64_t n, int32_t q, int32_t bucket);
+int choco_qsgd_bucket_compress(const float* x, const float* xhat, int64_t n, int32_t q, int32_t bucket,
+                               int32_t is_biased, const float* u_in, uint64_t seed, uint64_t offset,
+                               uint8_t* message, float* dense_out, void* stream);
+int choco_gossip_qsgd_bucket_compress(float* x, const float* memory, const float* xhat, float gamma, int64_t n,
+                                      int32_t q, int32_t bucket, int32_t is_biased, const float* u_in,
+                                      uint64_t seed, uint64_t offset, uint8_t* message, float* dense_out,
+                                      void* stream);
+int choco_qsgd_bucket_decode(const uint8_t* message, int64_t n, int32_t q, int32_t bucket, int32_t is_biased,
+                             float* out, void* stream);
+int choco_qsgd_bucket_decompress_accumulate(const uint8_t* const* messages, const float* weights, int32_t nmsg,
+                                            int32_t self_slot, int64_t n, int32_t q, int32_t bucket,
+                                            int32_t is_biased, float* xhat_self, float* memory, void* stream);
+int choco_qsgd_bucket_recv_gossip_compress(const uint8_t* const* messages, const float* weights, int32_t nmsg,
+                                           int32_t self_slot, float* x, float* memory, float* xhat, float gamma,
+                                           int64_t n, int32_t q, int32_t bucket, int32_t is_biased,
+                                           const float* u_in, uint64_t seed, uint64_t offset,
+                                           uint8_t* message_out, void* stream);
+
 /* ------------------------------------------------------- gossip step
  * update_params_from_neighbor (pcode/optim/utils.py:67-72):
  *   x += (float)gamma * (memory - xhat)   (three roundings, as torch does). */
