@@ -132,6 +132,14 @@ SIGNATURES = {
                                                          _c_i32, _vp, _vp, _vp]),
     "choco_qsgd_bucket_recv_gossip_compress": (_c_i32, [_pp, _p_f32, _c_i32, _c_i32, _vp, _vp, _vp, _c_f32, _c_i64,
                                                         _c_i32, _c_i32, _c_i32, _vp, _c_u64, _c_u64, _vp, _vp]),
+    "choco_mx_packed_bytes": (_c_i64, [_c_i64, _c_i32]),
+    "choco_mx_compress": (_c_i32, [_vp, _vp, _c_i64, _c_i32, _c_i32, _c_u64, _c_u64, _vp, _vp, _vp]),
+    "choco_gossip_mx_compress": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _c_i32, _c_i32, _c_u64, _c_u64, _vp, _vp,
+                                          _vp]),
+    "choco_mx_decode": (_c_i32, [_vp, _c_i64, _c_i32, _vp, _vp]),
+    "choco_mx_decompress_accumulate": (_c_i32, [_pp, _p_f32, _c_i32, _c_i32, _c_i64, _c_i32, _vp, _vp, _vp]),
+    "choco_mx_recv_gossip_compress": (_c_i32, [_pp, _p_f32, _c_i32, _c_i32, _vp, _vp, _vp, _c_f32, _c_i64, _c_i32,
+                                               _c_i32, _c_u64, _c_u64, _vp, _vp]),
     "choco_gossip_step": (_c_i32, [_vp, _vp, _vp, _c_f32, _c_i64, _vp]),
     "choco_params_launches": (_c_i32, [_c_i32]),
     "choco_params_pack": (_c_i32, [_pp, _p_i64, _p_i32, _c_i32, _vp, _c_i64, _vp]),

@@ -2094,3 +2094,6 @@ from ._lowrank import (GOSSIP_MAX_WIDTH, GOSSIP_WIDE_MAX_WIDTH, LOWRANK_ORTH_MET
 from ._qsgd_bucket import (QSGD_BUCKETS, qsgd_bucket_accumulate, qsgd_bucket_compress,  # noqa: E402,F401
                            qsgd_bucket_decode, qsgd_bucket_packed_bytes, qsgd_bucket_recv_gossip_compress,
                            qsgd_bucket_split, qsgd_bucket_wire)
+# ----------------------------------------------------------------------------- MX wire (FP4 / FP8 blocks)
+from ._mx import (MX_LEVELS, mx_accumulate, mx_compress, mx_decode, mx_packed_bytes,  # noqa: E402,F401
+                  mx_recv_gossip_compress, mx_split, mx_wire)

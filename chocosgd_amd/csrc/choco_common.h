@@ -102,6 +102,12 @@ inline bool elem_aligned(const void* p, uintptr_t esz) { return (reinterpret_cas
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// whether [a, a + abytes) and [b, b + bbytes) share a byte (a null pointer overlaps nothing)
+inline bool overlaps(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return a && b && pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
+}
+
 // ---------------------------------------------------------------- argument checks
 // Shared by the entry points; every check runs before the first HIP call.
 // A flat buffer of n elements in nseg segments, and the 16-byte alignment of `bufs`
@@ -420,11 +426,16 @@ struct Xoro128 {
     s0 = splitmix64_mix(z);
     s1 = splitmix64_mix(z + kGoldenGamma);
   }
-  // next output; u0/u1 = its two 24-bit uniforms
-  CHOCO_DEV void next2(float& u0, float& u1) {
+  // next output, all 64 bits (mx.hip: the random operands of two stochastic conversions)
+  CHOCO_DEV uint64_t next() {
     const uint64_t a = s0, r = a + s1, t = s1 ^ a;
     s0 = rotl64(a, 24) ^ t ^ (t << 16);
     s1 = rotl64(t, 37);
+    return r;
+  }
+  // next output; u0/u1 = its two 24-bit uniforms
+  CHOCO_DEV void next2(float& u0, float& u1) {
+    const uint64_t r = next();
     const uint32_t hi = (uint32_t)(r >> 32), lo = (uint32_t)r;
     u0 = u24(hi >> 8);
     u1 = u24(__builtin_amdgcn_alignbit(hi, lo, 16) & 0xFFFFFFu);

@@ -164,18 +164,6 @@ CHOCO_DEV void bucket_quant_rows(const float (&d)[NG][kQPer], int64_t tile, int 
   }
 }
 
-CHOCO_DEV void unpack8(const float4& a, const float4& b, float (&v)[kQPer]) {
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-CHOCO_DEV void load8(const float* p, float (&v)[kQPer]) {
-  unpack8(*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4), v);
-}
-CHOCO_DEV void store8(float* p, const float (&v)[kQPer]) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-}
-
 // The accumulate of one 8-element group: for each message in order, x_hat_self += v
 // (self_slot), memory += (float)w * v (two roundings).
 template <int CW, int NM>
@@ -479,11 +467,6 @@ static int check_qb(int64_t n, int32_t q, int32_t bucket) {
   CHOCO_REQUIRE(q >= 1 && q <= 16, "quantize level q must be in [1, 16], got %d", q);
   CHOCO_REQUIRE(bucket_log2(bucket) > 0, "bucket must be one of 128, 256, 512, 1024, 2048, got %d", bucket);
   return CHOCO_OK;
-}
-
-static bool overlaps(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return a && b && pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
 }
 
 // c: 1, or 1.0 / (min(B / s**2, sqrt(B) / s) + 1.0) in doubles -- sparsification.py:96-97 with the

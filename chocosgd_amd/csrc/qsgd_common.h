@@ -141,6 +141,19 @@ CHOCO_DEV float qlevel(float lf, float u) {
   return pl + ((u < (lf - pl)) ? 1.0f : 0.0f);                // + is_next_level
 }
 
+// A thread's 8-element group as two 16-byte accesses (the bucketed and the MX kernels).
+CHOCO_DEV void unpack8(const float4& a, const float4& b, float (&v)[kQPer]) {
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+CHOCO_DEV void load8(const float* p, float (&v)[kQPer]) {
+  unpack8(*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4), v);
+}
+CHOCO_DEV void store8(float* p, const float (&v)[kQPer]) {
+  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+
 constexpr int kQG = 4;                                  // groups per thread
 // The uniform stream of thread slot t's groups g, g + 1 (g even) of a tile: 16 uniforms
 // each, two streams per slot (choco_common.h Xoro128; oracle qsgd_uniforms_at).

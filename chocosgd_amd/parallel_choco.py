@@ -241,6 +241,8 @@ class CHOCOQuantizationCompressor(_CHOCOBase):
 
     def __init__(self, *args, **kargs):
         self.bucket_size = self._bucket_args(*args, **kargs)  # refusals first: nothing is bound yet
+        self.mx = self._mx_args(*args, **kargs)
+        self.whole_message = self.mx or self.bucket_size is not None  # scales lead: no norms header, one launch
         super().__init__(*args, **kargs)
         self.exchange_chunks = int(self.kargs.get("exchange_chunks", 1))
 
@@ -260,25 +262,41 @@ class CHOCOQuantizationCompressor(_CHOCOBase):
             raise RuntimeError(f"bucket_size must be one of {codec.QSGD_BUCKETS}, got {bucket_size}")
         return int(bucket_size)
 
+    @staticmethod
+    def _mx_args(aggregator=None, comm_op="", comm_device=None, compress_ratio=None, quantize_level=None,
+                 *_rest, exchange_chunks=1, **_kargs):
+        """comm_op "quantize_mx" (the block-scaled FP4 / FP8 wire): True, after refusing by name what it
+        does not do; False for any other op."""
+        if "mx" not in comm_op:
+            return False
+        if int(exchange_chunks) > 1:
+            raise RuntimeError("comm_op quantize_mx: exchange_chunks > 1 is not implemented")
+        if int(quantize_level) not in codec.MX_LEVELS:
+            raise RuntimeError(f"comm_op quantize_mx takes quantize_level 4 (E2M1) or 8 (E4M3), got {quantize_level}")
+        return True
+
     def _compress_bucket(self, sync_buffer, x, xh, lay, q, g):
         """One launch: the one-pass compress (the consensus step fused where `gossip` gives it),
         or, with a deferred receive pending, the whole step -- receive, consensus step, message."""
-        message = codec.qsgd_bucket_wire(lay.n, q, self.bucket_size, x.device)  # written in place by the kernel
-        pend = self._take_pending(x, xh, g, lay)
-        if pend is not None:
-            codec.qsgd_bucket_recv_gossip_compress(pend[0], pend[1], pend[2], x, g[0], xh, g[1], q,
-                                                   bucket=self.bucket_size, is_biased=self.is_biased,
-                                                   seed=self._draw_seed(), out=message)
+        if self.mx:
+            message, kw = codec.mx_wire(lay.n, q, x.device), {}  # written in place by the kernel
+            step, compress = codec.mx_recv_gossip_compress, codec.mx_compress
         else:
-            codec.qsgd_bucket_compress(x, q, bucket=self.bucket_size, is_biased=self.is_biased, xhat=xh,
-                                       seed=self._draw_seed(), gossip=g, out=message)
+            message, kw = codec.qsgd_bucket_wire(lay.n, q, self.bucket_size, x.device), dict(bucket=self.bucket_size)
+            step, compress = codec.qsgd_bucket_recv_gossip_compress, codec.qsgd_bucket_compress
+        pend = self._take_pending(x, xh, g, lay)
+        kw.update(is_biased=self.is_biased, seed=self._draw_seed(), out=message)
+        if pend is not None:
+            step(pend[0], pend[1], pend[2], x, g[0], xh, g[1], q, **kw)
+        else:
+            compress(x, q, xhat=xh, gossip=g, **kw)
         self._qsgd_keys(sync_buffer, x, message)
 
     def compress(self, sync_buffer):
         x, xh, lay = self._flat_inputs(sync_buffer)
         q = int(self.quantize_level)
         g = self._gossip(sync_buffer)
-        if self.bucket_size is not None:
+        if self.whole_message:
             sync_buffer.pop("chunked", None)
             return self._compress_bucket(sync_buffer, x, xh, lay, q, g)
         if q == 32 or self.exchange_chunks > 1:
@@ -333,7 +351,7 @@ class CHOCOQuantizationCompressor(_CHOCOBase):
         self.aggregator_fn.complete_wait(sync_buffer["sync_reqs"])
         ranks, plan = self._receive_plan(sync_buffer, neighbor_hat_params, neighbors_info)
         weights, self_slot, memory, xhat_self, _ = plan
-        if self.bucket_size is not None:  # whole messages: the scales lead, there is no norms header
+        if self.whole_message:  # the scales lead, there is no norms header
             msgs = [m for _, _, m in _received(sync_buffer["synced_message"], ((r, memory) for r in ranks),
                                                lambda m: m)]
         else:
@@ -349,6 +367,9 @@ class CHOCOQuantizationCompressor(_CHOCOBase):
         self._apply(msgs, *plan)
 
     def _apply(self, parts, weights, self_slot, memory, xhat_self, lay):
+        if self.mx:
+            return codec.mx_accumulate(parts, weights, self_slot, lay.n, int(self.quantize_level), memory,
+                                       xhat_self=xhat_self)
         if self.bucket_size is not None:
             return codec.qsgd_bucket_accumulate(parts, weights, self_slot, lay.n, int(self.quantize_level), memory,
                                                 bucket=self.bucket_size, xhat_self=xhat_self,

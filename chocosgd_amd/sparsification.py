@@ -128,8 +128,20 @@ class QuantizationCompressor(object):
         t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
         return self.get_qsgd(t, s, is_biased).numpy()
 
+    def get_mx(self, x, q, is_biased=False):
+        """The MX wire's dense decode (include/choco_codec.h "MX wire"): x in blocks of 32 flat
+        elements as E2M1 (q = 4) or E4M3 (q = 8) codes times a power-of-two block scale."""
+        if int(q) not in codec.MX_LEVELS:
+            raise RuntimeError(f"quantize_mx takes quantize_level 4 (E2M1) or 8 (E4M3), got {q}")
+        xd, home = _on_device(x)
+        _, dense = codec.mx_compress(xd.reshape(-1).contiguous(), int(q), is_biased=is_biased, seed=_draw_seed(),
+                                     want_dense=True)
+        return _home(dense.view_as(xd), home)
+
     def compress(self, arr, op, quantize_level, is_biased):
-        if "bucket" in op:
+        if "mx" in op:
+            values = self.get_mx(arr, quantize_level, is_biased)
+        elif "bucket" in op:
             if quantize_level == 32:
                 raise NotImplementedError("the bucketed quantizer has no quantize_level = 32 passthrough")
             values = self.get_qsgd_bucket(arr, 2 ** quantize_level - 1, is_biased=is_biased)

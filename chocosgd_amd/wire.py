@@ -293,6 +293,9 @@ class _QsgdConsumer(_Consumer):
         if "bucket" in self.comm_op:  # not silently the per-tensor quantizer
             raise NotImplementedError(f"comm_op={self.comm_op!r}: the bucketed quantizer is CHOCO's only "
                                       "(CHOCOCompressor); DCD, ECD and DeepSqueeze take quantize_qsgd")
+        if "mx" in self.comm_op:
+            raise NotImplementedError(f"comm_op={self.comm_op!r}: the MX wire (quantize_mx) is CHOCO's only "
+                                      "(CHOCOCompressor); DCD, ECD and DeepSqueeze take quantize_qsgd")
 
     def sync(self, sync_buffer):
         sync_buffer["synced_message"] = self._send(sync_buffer["flatten_updates"].buffer)

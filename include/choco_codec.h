@@ -577,6 +577,57 @@ int choco_qsgd_bucket_recv_gossip_compress(const uint8_t* const* messages, const
                                            const float* u_in, uint64_t seed, uint64_t offset,
                                            uint8_t* message_out, void* stream);
 
+/* ------------------------------------------------------- MX wire (block-scaled FP4 / FP8)
+ * The OCP microscaling layout on gfx950's scaled conversions: the flat buffer d = x - xhat (x
+ * alone when xhat is NULL) in BLOCKS of 32 consecutive elements (tensor boundaries ignored, the
+ * last block may be short), each with one power-of-two scale byte (E8M0) and one code per
+ * element: q = 4 is E2M1 (grid 0, .5, 1, 1.5, 2, 3, 4, 6; vmax = 6), q = 8 is E4M3 (OCP, bias
+ * 7, subnormals, vmax = 448).  4.25 or 8.25 bits per element.
+ *   amax  = max |d| of the block, with biased exponent field E + 127 and mantissa field m
+ *   e     = the smallest integer with amax <= vmax 2^e, from the bits alone:
+ *           E - 2 + (m > 0x400000) (E2M1), E - 8 + (m > 0x600000) (E4M3), clamped at -127
+ *           (fp32 denormals count as E = -127); nothing ever saturates
+ *   byte  = e + 127; a block that holds an inf or a NaN: 0xFF
+ *   code  = the sign-magnitude code of d / 2^e (the sign of d kept, zeros included), rounded
+ *           to nearest even (sr = 0: deterministic, contractive) or stochastically (sr != 0:
+ *           unbiased).  A block with byte 0 (amax = 0) or 0xFF sends all-zero codes.
+ *   E2M1: element i in nibble i & 1 of code byte i >> 1, low nibble first; E4M3: in byte i.
+ *   decoded v = grid[code] 2^e with code's sign, exact in fp32; NaN throughout a 0xFF block.
+ * Stochastic rounding is the hardware's: with lo <= |d| / 2^e < hi the bracketing grid values,
+ * f = (|d| / 2^e - lo) / (hi - lo) and a 32-bit random operand r, the magnitude goes up iff
+ * floor(f 2^32) + r >= 2^32.  r comes from the QSGD uniform stream's generator, unchanged
+ * (key from (seed, offset), one xoroshiro128+ stream per 16 elements; see QSGD above): a
+ * stream's conversion c -- its c-th element (E4M3: 16 conversions) or element pair (E2M1: 8)
+ * -- takes the high (c even) or low (c odd) half of output c >> 1; of an E2M1 pair the first
+ * element uses r, the second r rotated left by one bit.  A message is a function of (d, sr,
+ * seed, offset) alone.
+ * Message: [scale bytes: ceil(n / 32), padded to 16 B | codes: ceil(n q / 8) bytes, padded to
+ * 16 B] = choco_mx_packed_bytes(n, q) bytes (0 for arguments out of range), every byte written.
+ *
+ * The entry points are bucketed QSGD's: compress (message and dense_out = v, nullable),
+ * gossip_..._compress (the consensus step first, in the same pass), decode, decompress_accumulate
+ * (xhat_self += v_m for m == self_slot, memory += (float)weights[m] * v_m, two roundings, in
+ * message order) and recv_gossip_compress (that accumulate, x += gamma (memory - xhat), then
+ * compress, in one pass; bit-identical to the three calls in sequence).  No workspace.
+ * Every call checks its arguments before the launch and without a HIP call (CHOCO_ERR_INVALID):
+ * null pointers, n outside [1, 2^31 - 1), q other than 4 or 8, nmsg outside 1..8, self_slot
+ * outside [-1, nmsg), pointers off 16-byte alignment, an output message that overlaps x, xhat,
+ * memory or an input message. */
+int64_t choco_mx_packed_bytes(int64_t n, int32_t q);
+int choco_mx_compress(const float* x, const float* xhat, int64_t n, int32_t q, int32_t sr, uint64_t seed,
+                      uint64_t offset, uint8_t* message, float* dense_out, void* stream);
+int choco_gossip_mx_compress(float* x, const float* memory, const float* xhat, float gamma, int64_t n, int32_t q,
+                             int32_t sr, uint64_t seed, uint64_t offset, uint8_t* message, float* dense_out,
+                             void* stream);
+int choco_mx_decode(const uint8_t* message, int64_t n, int32_t q, float* out, void* stream);
+int choco_mx_decompress_accumulate(const uint8_t* const* messages, const float* weights, int32_t nmsg,
+                                   int32_t self_slot, int64_t n, int32_t q, float* xhat_self, float* memory,
+                                   void* stream);
+int choco_mx_recv_gossip_compress(const uint8_t* const* messages, const float* weights, int32_t nmsg,
+                                  int32_t self_slot, float* x, float* memory, float* xhat, float gamma, int64_t n,
+                                  int32_t q, int32_t sr, uint64_t seed, uint64_t offset, uint8_t* message_out,
+                                  void* stream);
+
 /* ------------------------------------------------------- gossip step
  * update_params_from_neighbor (pcode/optim/utils.py:67-72):
  *   x += (float)gamma * (memory - xhat)   (three roundings, as torch does). */
